@@ -17,7 +17,11 @@ operator (132 651 000 rows, 16.6 M rows / 116 M nnz per GPU); at N=2 and 4 it is
 those 16.6 M rows per GPU (323^3 and 407^3: weak scaling, isotropic like the 512^3 problem itself),
 neighbours exchange about one plane of the cube per side.
 
-Extra objects: `roofline` (kernel time from HIP events recorded on the compute stream around the timed launches; `bound` says
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...,
+`config`).  `--dump-outputs DIR` writes y = A x of the last timed step as DIR/y.npy (float64; at more than one rank, or where the
+vector exceeds the budget, every rank writes its rows or a fixed seeded sample of them).  Everything else runs only with `--full`:
+
+Extra objects (`--full`): `roofline` (kernel time from HIP events recorded on the compute stream around the timed launches; `bound` says
 whether the working set is Infinity-Cache or HBM resident; the streaming ceiling of the operator's stored bytes is measured in the
 same run -- `peak_measured`, `frac_of_measured` <= 1 -- and is what a cache-resident operator's `frac` is taken against),
 `spmv_irregular` (N=1: BASELINE configs[4] at 1 M rows -- the reference's SiH4 replicated, tests/irregular.py), `vcycle_256` (N=1:
@@ -54,6 +58,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: roofline and streaming "
+                    "ceiling, SpMV self-check, HBM-resident and irregular SpMV legs, V-cycle / pCG legs, CPU baseline, and at N>1 the finer partition")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write y = A x of the last timed step to DIR/*.npy (float64)")
     ap.add_argument("--grid-m", "--m", dest="m", type=int, default=None, help="grid points per side (reference laplacian3D argument); default 128 at "
                     "--gpus 1 (BASELINE configs[1]) and 512 at --gpus N>1 (configs[3] at N=8; at N=2/4 the cube with the same rows per GPU)")
     ap.add_argument("--hbm-m", "--m-hbm", dest="m_hbm", type=int, default=256, help="grid of the secondary HBM-resident SpMV figure at --gpus 1 (0 = skip)")
@@ -75,6 +82,23 @@ def parse():
                     help="N>1: skip the second SpMV measurement (and the second 128^3 leg) under the opt-in finer row partition (`value_balanced`)")
     ap.add_argument("--balanced-buckets", type=int, default=4096, help="N>1: row buckets of the opt-in finer partition (the reference uses nparts^2)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 48 * 2 ** 20      # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(np, path, y, rank, world):
+    """--dump-outputs: this rank's y = A x (what a caller of sgpu_spmv receives) as float64.  A slice beyond its share of
+    DUMP_BYTES is written as a fixed sample instead: the rows a generator seeded by the rank picks (ascending, stored next to
+    the values as float64), so that two builds compare value for value."""
+    os.makedirs(path, exist_ok=True)
+    name = "y" if world == 1 else f"y_rank{rank}"
+    cap = DUMP_BYTES // 16 // world                        # (values + row ids of a sample)
+    if len(y) > cap:
+        rows = np.sort(np.random.default_rng(1000 + rank).choice(len(y), cap, replace=False))
+        np.save(os.path.join(path, f"{name}_sample_rows.npy"), rows.astype(np.float64))
+        y, name = y[rows], f"{name}_sample"
+    np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(y, dtype=np.float64))
 
 
 def cpu_baseline_reference(m, seconds, cores):
@@ -630,8 +654,10 @@ def main():
     if spmv_dog is not None:
         spmv_dog.cancel()
     op, info, kernel_name, ms_kernel, wall, B_local = R["op"], R["info"], R["kernel_name"], R["ms_kernel"], R["wall"], R["B_local"]
+    if args.dump_outputs:
+        dump_outputs(np, args.dump_outputs, R["y"].download(), rank, world)
 
-    err, _ = verify_spmv(np, host, A, op, R["x"], R["y"], R["g0"])        # outside the timed region
+    err = verify_spmv(np, host, A, op, R["x"], R["y"], R["g0"])[0] if args.full else 0.0      # outside the timed region
 
     def reduce_measurement(Rx, errx):
         """-> (max error, max wall, total algorithmic bytes, rows per rank, remote nnz per rank, nnz per rank)"""
@@ -657,7 +683,7 @@ def main():
     err, wall, B_total, rows_all, halo_all, nnz_all = reduce_measurement(R, err)
 
     balanced = None
-    if world > 1 and not args.no_balanced:
+    if world > 1 and args.full and not args.no_balanced:
         # The reference's partitioner works on nparts^2 row buckets (src/saena_matrix_repart.cpp:43-170): a rank gets 7-9 of 64
         # buckets at N = 8, 3-5 of 16 at N = 4.  The same SpMV measurement under the OPT-IN finer histogram
         # (saena_matrix_set_partition_buckets): reported next to `value`, never instead of it.
@@ -681,9 +707,6 @@ def main():
     out = None
     if rank == 0:
         sec_per_step = wall / args.steps
-        achieved = B_local / (ms_kernel * 1e-3) / 1e9
-        ws = stored_bytes(info, kernel_name)
-        traffic, traffic_src, traffic_kernel = pmc_traffic(m, world, kernel_name)
         out = {
             "metric": f"fine-level SpMV effective GB/s (3D 7-pt Poisson {grid_s}, fp64)",
             "value": round(B_total / sec_per_step / 1e9, 2),
@@ -723,13 +746,17 @@ def main():
                    if world > 1 else {}),
             },
             **({"value_balanced": balanced["value"], "balanced_partition": balanced} if balanced else {}),
-            "check": {"what": "y = A x of one more SpMV against the host-formed product from the layout arrays, halo values included; "
-                              "max over all ranks of max_i |y_gpu - y_host| / max_i sum_j |a_ij x_j|",
-                      "max_rel_err": err, "ok": bool(err <= 1e-13)},
-            "roofline": roofline_object(capi, info, kernel_name, ms_kernel, B_local, achieved, ws, traffic, traffic_src, max(20, args.steps // 4), traffic_kernel),
         }
+        if args.full:
+            achieved = B_local / (ms_kernel * 1e-3) / 1e9
+            ws = stored_bytes(info, kernel_name)
+            traffic, traffic_src, traffic_kernel = pmc_traffic(m, world, kernel_name)
+            out["check"] = {"what": "y = A x of one more SpMV against the host-formed product from the layout arrays, halo values included; "
+                                    "max over all ranks of max_i |y_gpu - y_host| / max_i sum_j |a_ij x_j|",
+                            "max_rel_err": err, "ok": bool(err <= 1e-13)}
+            out["roofline"] = roofline_object(capi, info, kernel_name, ms_kernel, B_local, achieved, ws, traffic, traffic_src, max(20, args.steps // 4), traffic_kernel)
     # free the big operator's vectors before the legs allocate theirs
-    if world == 1 and not multi and args.m_hbm and args.m_hbm != m:
+    if world == 1 and not multi and args.full and args.m_hbm and args.m_hbm != m:
         # the same measurement on an operator beyond the Infinity Cache (Poisson 256^3: 16.4 M rows, 114 M nnz, 1.7 GB
         # algorithmic -- also the per-GPU share of configs[3])
         A3 = host.Matrix(comm)
@@ -752,10 +779,10 @@ def main():
         A3.free()
         del R3, A3
 
-    if world == 1 and not multi and args.irregular_blocks:
+    if world == 1 and not multi and args.full and args.irregular_blocks:
         out["spmv_irregular"] = irregular_leg(capi, host, np, comm, args.irregular_blocks, sync_all)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not multi and not args.no_vcycle:
             out["vcycle"] = vcycle_leg(capi, host, A, m)
         if world == 1 and not multi and not args.no_vcycle and not args.no_config2_vcycle and m == 128:
@@ -768,7 +795,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(m, args.cpu_seconds)
 
-    if multi and not args.no_vcycle:
+    if multi and args.full and not args.no_vcycle:
         # V-cycle / pCG over all ranks, halos over RCCL.  Runs under a watchdog and a fatal-signal printer: whatever
         # happens in here, rank 0 still prints the SpMV line measured above -- and the process then ends with a
         # NON-ZERO status (3 for a watchdog expiry or an exception, 128 + signal for a fatal signal), so the launcher

@@ -5,7 +5,7 @@ import sys
 
 ms = [int(a) for a in sys.argv[1:]] or [48, 64, 96, 128, 160, 192, 256]
 for m in ms:
-    out = subprocess.run([sys.executable, "bench.py", "--m", str(m), "--no-vcycle", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--m", str(m), "--no-vcycle", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     d = json.loads(out.stdout.strip().splitlines()[-1])
     r = d["roofline"]
     print(f"m={m:4d} rows={d['config']['rows_per_gpu']:9d} algorithmic {r['algorithmic_bytes'] / 1e6:8.1f} MB  {r['kernel']:34s} "

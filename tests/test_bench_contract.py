@@ -1,6 +1,10 @@
 """The bench line's contract (driver + judge read these keys), checked on the committed line of this round."""
 import json
 import os
+import subprocess
+import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -105,3 +109,31 @@ def test_committed_kernel_trace_agrees_with_the_bench_line():
             assert cand, hk
             avg_us = float(max(cand, key=lambda r: int(r["Calls"]))["AverageNs"]) / 1e3
             assert abs(avg_us - h["us_per_launch"]) <= 0.05 * avg_us, (avg_us, h["us_per_launch"])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_timed_output(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: ONE JSON line with the headline keys and K timed
+    steps, none of the --full legs, and DIR/y.npy = A x of the last timed step (x(g) = sin(0.001 g)) against the oracle's product."""
+    import numpy as np
+    from oracle import oracle as orc
+    m = 64
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3", "--grid-m", str(m), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["n_gpus"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and f"{m}^3" in d["metric"]
+    for k in ("roofline", "check", "spmv_hbm_resident", "spmv_irregular", "vcycle", "vcycle_256", "cpu_baseline"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["y.npy"]
+    y = np.load(tmp_path / "y.npy")
+    entries, M = orc.laplacian3d(m)
+    assert y.dtype == np.float64 and y.shape == (M,)
+    x = np.sin(0.001 * np.arange(M))
+    want = orc.OracleOp(entries, M, M, orc.split_even(M, 1)).matvec(x)
+    entries["val"] = np.abs(entries["val"])
+    bound = orc.OracleOp(entries, M, M, orc.split_even(M, 1)).matvec(np.abs(x))
+    assert np.max(np.abs(y - want)) <= 1e-13 * np.max(bound)

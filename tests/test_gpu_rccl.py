@@ -35,7 +35,7 @@ def test_rccl_loopback(torch_first, mode):
 
 
 def _bench_rehearsal(nproc, extra, timeout=900):
-    """`bench.py --gpus N` exactly as the driver launches it, with all ranks on this one card: SAENA_BENCH_NO_RCCL=1
+    """`bench.py --gpus N --full` as the driver launches it, with all ranks on this one card: SAENA_BENCH_NO_RCCL=1
     routes halos through the host transport (RCCL refuses two ranks per device)."""
     import socket
     with socket.socket() as sk:
@@ -43,7 +43,7 @@ def _bench_rehearsal(nproc, extra, timeout=900):
         port = sk.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SAENA_BENCH_NO_RCCL="1", SAENA_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "bench.py", "--gpus", str(nproc), "--steps", "10", "--warmup", "2"] + extra
+           "--master-port", str(port), "bench.py", "--gpus", str(nproc), "--steps", "10", "--warmup", "2", "--full"] + extra
     return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -160,7 +160,7 @@ def test_bench_two_ranks_at_the_full_per_rank_size_of_configs3():
     print(f"two ranks: {t_two:.0f} s wall, host setup of the configs[3] hierarchy {w['host_setup_s']} s")
     # the same problem at one rank
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    one = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--grid-m", "323", "--hbm-m", "0", "--irregular-blocks", "0", "--no-cpu-baseline", "--steps", "10", "--warmup", "2"],
+    one = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--grid-m", "323", "--hbm-m", "0", "--irregular-blocks", "0", "--no-cpu-baseline", "--steps", "10", "--warmup", "2", "--full"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stdout[-2000:] + one.stderr[-3000:]
     o = json.loads([ln for ln in one.stdout.splitlines() if ln.strip()][-1])["vcycle"]

@@ -9,7 +9,7 @@ export SAENA_BENCH_VARIANT=$V
 i=0
 for C in FETCH_SIZE WRITE_SIZE TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum; do
     i=$((i+1))
-    timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $D/pass$i -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-vcycle > $D/pass$i.log 2>&1 || { tail -3 $D/pass$i.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $D/pass$i -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-vcycle > $D/pass$i.log 2>&1 || { tail -3 $D/pass$i.log; exit 1; }
 done
 python3 - "$D" "$V" > "$OUT" <<'PY'
 import csv, glob, json, sys

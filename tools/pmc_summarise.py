@@ -23,7 +23,7 @@ write = mean["WRITE_SIZE"] * 1024.0
 rd, rd32 = mean["TCC_EA0_RDREQ_sum"], mean["TCC_EA0_RDREQ_32B_sum"]
 fetch = 2.0 * fetch_raw                               # gfx950: counted as 64 B per request, the requests are 128 B
 out = {
-    "command": f"SAENA_BENCH_VARIANT={variant} rocprofv3 --pmc <C> --output-format csv -- python3 bench.py --steps 40 --warmup 5 "
+    "command": f"SAENA_BENCH_VARIANT={variant} rocprofv3 --pmc <C> --output-format csv -- python3 bench.py --full --steps 40 --warmup 5 "
                "--no-cpu-baseline --no-vcycle (tools/pmc_spmv.sh: one pass per counter group, kernel pinned)",
     "kernel": kernel, "workload": "Poisson 128^3 SpMV, 1 MI355X",
     "counters": {k: {"n": len(v), "mean": mean[k], "min": min(v), "max": max(v)} for k, v in sorted(c.items())},

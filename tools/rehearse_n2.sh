@@ -5,7 +5,7 @@
 O=${1:-gpurun_out/rehearse_n2}; mkdir -p $O
 export SAENA_SETUP_TIMING=1 SAENA_BENCH_NO_RCCL=1 SAENA_BENCH_DEVICE=0 HSA_ENABLE_IPC_MODE_LEGACY=0
 S=$(date +%s)
-timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 --vcycle-timeout 900 > $O/bench_n2_323.json 2> $O/bench_n2_323.err
+timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 --full --vcycle-timeout 900 > $O/bench_n2_323.json 2> $O/bench_n2_323.err
 echo "rc=$? wall=$(( $(date +%s) - S )) s"
 python3 - "$O" <<'P'
 import json, re, sys, collections
