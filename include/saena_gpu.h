@@ -144,10 +144,13 @@ int sgpu_op_set_lanes_per_row(sgpu_op *op, int lanes);
  * workgroup (operators that qualify for 11 and whose pattern offsets fall into at most 16 clusters that fit 80 KiB of LDS
  * together with the table); 16 k_csr_xldsr: k_csr_xlds with FOUR consecutive rows per group step (4 / 8 / 16 lanes per
  * group) -- irregular operators of a few dozen entries per row, where one row per step leaves the kernel waiting on the
- * latency of a row (BASELINE configs[4] scaled to 1 M rows).
- * 7, 8, 9 and 11 to 15 are
- * built from a host copy of the values that the library keeps only until the plan-time autotune (SGPU_ERR_ARG
- * afterwards, and where the form does not apply) */
+ * latency of a row (BASELINE configs[4] scaled to 1 M rows); 17 k_vidx: k_sellp with its values as 8-bit codes into a
+ * dictionary per workgroup of 256 rows -- 1 B per entry instead of 8, the same products and row sums (operators that qualify for
+ * 11 with ONE pattern table and hold at most 256 distinct values, as bit patterns, in every group of 256 rows: constant-
+ * coefficient stencils and their level-0 transfers; "k_vidx<rowbase>" on the rowbase table; SAENA_NO_VALUE_INDEX=1 keeps it
+ * out of the autotune).
+ * 12 and 13 are built from a host copy of the values that the library keeps only until the plan-time autotune
+ * (SGPU_ERR_ARG afterwards); every form returns SGPU_ERR_ARG where it does not apply */
 int sgpu_op_set_variant(sgpu_op *op, int variant);
 int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_name);
 /* time the (variant, lanes) candidates that apply to this operator and keep the fastest (plan-time autotune; no

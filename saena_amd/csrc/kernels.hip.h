@@ -81,6 +81,11 @@ struct SpmvArgs {
     int                   st_plain;  // non-temporal launches: store y with plain stores all the same (it is the next sweep's x)
     int                   uw;        // k_sellp / k_sellp2: every slice has this many positions (0: read the slice pointers) -- a slice's values then
                                      // start at s * uw * rows-per-slice and the value loads depend on nothing the wave has to fetch first
+    // value-indexed row patterns (k_vidx): an 8-bit code per entry into a dictionary of at most VI_MAX values per workgroup
+    const unsigned char  *vcode;     // slices of 64 rows, groups of 8 positions: [slice][j / 8][lane][j % 8]
+    const int            *vcptr;     // byte start of every slice in vcode (nslices + 1), unless uw (then slice s starts at s * uw * 64)
+    const double         *vdict;     // the workgroups' dictionaries back to back ...
+    const int            *vdptr;     // ... workgroup b owns vdict[vdptr[b] .. vdptr[b + 1])
     // in-kernel fork to the halo stream (multi-rank interior launch only, else nullptr): block 0 stores
     // *flag_x = seq when it starts -- stream order: everything earlier on the compute stream is complete, so
     // the halo stream's pack, which polls the flag, may read x.
@@ -789,6 +794,71 @@ __global__ __launch_bounds__(WIDE ? SPW_BLOCK : BLOCK) void k_sellp(const SpmvAr
     }
     if (r < nrows) epilogue<EPI, HALO, NT>(a, r, sum);
     }
+}
+
+// ---------------------------------------------------------------------------
+// K1v: VALUE-INDEXED row patterns (CSR-VI, Kourtis et al.) -- k_sellp with its 8-byte values replaced by 8-bit codes into a
+// dictionary of the workgroup's distinct values.  After k_sellp removed the column stream, the values were 111 of the 147 MB the
+// cache-resident 128^3 fine level stores; its boundary-stripped Laplacian holds TWO distinct values.  Every entry still streams a
+// byte of its own (no assumption that rows repeat their values, unlike k_rowt); a code decodes to the exact fp64 bit pattern, so
+// the products and the sequential row sum are k_sellp's: bit-identical results.
+// a.vcode: codes, position-major per slice in groups of 8 positions -- a lane's 8 codes are one 8-byte load, a wave's 512 B
+// contiguous; a.vcptr / a.uw: slice starts; a.vdict / a.vdptr: the dictionaries, staged in LDS behind the pattern table (<= 2 KiB);
+// a.dst / a.ptab / pt_w / pt_n / a.rbase: k_sellp's pattern ids, table and (rowbase) first columns; a.nblk: slices.
+// One workgroup = 4 slices = 256 rows = one dictionary (k_vi_build below); the operator is refused where any workgroup holds more than
+// VI_MAX distinct values.
+constexpr int VI_MAX = 256;
+template <int EPI, bool HALO, bool NT>
+__global__ __launch_bounds__(BLOCK) void k_vidx(const SpmvArgs a, int nrows) {
+    extern __shared__ int ptab_lds[];
+    if constexpr (HALO) fork_signal(a);
+    constexpr int SPB = BLOCK / 64;
+    const int lane = threadIdx.x & 63;
+    const int ngrp = (a.nblk + SPB - 1) / SPB;
+    const int b0 = xcd_remap(blockIdx.x, ngrp);
+    const int tn = a.pt_n * (a.pt_w + 1);
+    double *dict = reinterpret_cast<double *>(ptab_lds + ((tn + 1) & ~1));      // (8-byte aligned behind the table)
+    for (int i = threadIdx.x; i < tn; i += BLOCK) ptab_lds[i] = a.ptab[i];
+    {
+        const int d0 = a.vdptr[b0], dn = a.vdptr[b0 + 1] - d0;                  // dn <= VI_MAX = BLOCK
+        if ((int)threadIdx.x < dn) dict[threadIdx.x] = a.vdict[d0 + threadIdx.x];
+    }
+    __syncthreads();
+    const int s = __builtin_amdgcn_readfirstlane(b0 * SPB + ((int)threadIdx.x >> 6));
+    if (s >= a.nblk) return;
+    const int r = s * 64 + lane;
+    int cp, w8;
+    if (a.uw) { w8 = a.uw; cp = s * w8 * 64; }            // uniform slices: the code loads depend on nothing the wave has to fetch first
+    else { cp = a.vcptr[s]; w8 = (a.vcptr[s + 1] - cp) >> 6; }
+    int pid = 0;
+    if (r < nrows) { if constexpr (NT) pid = __builtin_nontemporal_load(a.dst + r); else pid = a.dst[r]; }
+    const int *pt = ptab_lds + pid * (a.pt_w + 1);
+    const int len = r < nrows ? pt[0] : 0;
+    ++pt;
+    const int wmax = a.pt_w - 1;
+    const int rf = a.rbase ? (r < nrows ? a.rbase[r] : 0) : r;
+    auto colof = [&](int j) { const int c = rf + pt[j < wmax ? j : wmax]; return j < len ? c : 0; };
+    const bool ntv = NT && s >= a.nt_from;
+    const uint2 *c8 = reinterpret_cast<const uint2 *>(a.vcode + cp) + lane;
+    double sum = 0.0;
+    for (int j = 0; j < w8; j += 8) {
+        uint2 cc;
+        {
+            const sk_u2v *cq = reinterpret_cast<const sk_u2v *>(c8 + (j >> 3) * 64);
+            sk_u2v v;
+            if (ntv) v = __builtin_nontemporal_load(cq); else v = *cq;
+            cc.x = v.x; cc.y = v.y;
+        }
+        double xx[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xx[u] = a.x[colof(j + u)];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {                      // positions past the row's length (code 0) are never added
+            const unsigned code = ((u < 4 ? cc.x : cc.y) >> (8 * (u & 3))) & 0xffu;
+            if (j + u < len) sum += dict[code] * xx[u];
+        }
+    }
+    if (r < nrows) epilogue<EPI, HALO, NT>(a, r, sum);
 }
 
 // ---------------------------------------------------------------------------
@@ -1807,6 +1877,85 @@ __global__ __launch_bounds__(BLOCK) void k_sell_scatter(const T *__restrict__ sr
             dst[o] = src[q0 + j];
         }
     }
+}
+
+// ---- setup: the 8-bit value codes and per-workgroup dictionaries of k_vidx, on the device ----
+// One workgroup per group of 256 rows (k_vidx's workgroup), a thread per row walking its CSR entries.  The distinct values go into
+// an LDS hash of VI_HASH 64-bit keys, compared as bit patterns (+0.0 / -0.0 stay apart, NaN payloads are kept); the all-ones pattern
+// is the empty-slot key and, should it occur as a value, has a slot of its own.  Every slot keeps its value's first position in
+// slice order ((slice, position, lane): the order the kernel streams the entries in); a value's code is the number of values that
+// occur before it -- codes in order of first occurrence, independent of the hash's insertion race.  Where the group holds more
+// than VI_MAX values *overflow is set (the host then refuses the operator).  Writes: dict_tmp[b * VI_MAX + code], count[b], and
+// each entry's code at its place in the code array (zero-filled beforehand: padding keeps code 0).
+constexpr int VI_HASH = 512;
+__device__ __forceinline__ unsigned vi_hash(unsigned long long k) { return (unsigned)((k * 0x9E3779B97F4A7C15ull) >> 55); }   // 9 bits: VI_HASH slots
+__global__ __launch_bounds__(BLOCK) void k_vi_build(const double *__restrict__ val, const int *__restrict__ row_ptr, const int *__restrict__ cptr,
+                                                   int uw8, int M, unsigned char *__restrict__ code, double *__restrict__ dict_tmp,
+                                                   int *__restrict__ count, int *__restrict__ overflow) {
+    constexpr unsigned long long EMPTY = ~0ull;
+    __shared__ unsigned long long key[VI_HASH];
+    __shared__ int first[VI_HASH + 1];                    // [VI_HASH]: the all-ones pattern
+    __shared__ int rank[VI_HASH + 1];
+    __shared__ int bad;
+    for (int i = threadIdx.x; i < VI_HASH; i += BLOCK) key[i] = EMPTY;
+    for (int i = threadIdx.x; i <= VI_HASH; i += BLOCK) first[i] = 0x7fffffff;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    const int r = blockIdx.x * BLOCK + threadIdx.x;
+    const int sl = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int p0 = r < M ? row_ptr[r] : 0, n = r < M ? row_ptr[r + 1] - p0 : 0;
+    // the slot of value bits k: insert (find == false) or look up (find == true); -1: the table is full
+    auto slot = [&](unsigned long long k, bool find) -> int {
+        if (k == EMPTY) return VI_HASH;
+        unsigned h = vi_hash(k);
+        for (int t = 0; t < VI_HASH; ++t, h = (h + 1) & (VI_HASH - 1)) {
+            if (find) { if (key[h] == k) return (int)h; continue; }
+            const unsigned long long prev = atomicCAS(&key[h], EMPTY, k);
+            if (prev == EMPTY || prev == k) return (int)h;
+        }
+        return -1;
+    };
+    for (int j = 0; j < n; ++j) {
+        const unsigned long long k = (unsigned long long)__double_as_longlong(val[p0 + j]);
+        const int h = slot(k, false);
+        if (h < 0) { bad = 1; break; }
+        atomicMin(&first[h], (sl * 65536 + j) * 64 + lane);            // (j < 65536: rows of sliced ELLPACK)
+    }
+    __syncthreads();
+    // codes: the rank of every used slot by first position (distinct positions: no ties)
+    for (int i = threadIdx.x; i <= VI_HASH; i += BLOCK) {
+        const int f = first[i];
+        int k = 0;
+        if (f != 0x7fffffff)
+            for (int q = 0; q <= VI_HASH; ++q) k += first[q] < f ? 1 : 0;
+        rank[i] = k;
+        if (f != 0x7fffffff) {
+            if (k >= VI_MAX) bad = 1;
+            else dict_tmp[(size_t)blockIdx.x * VI_MAX + k] = i == VI_HASH ? __longlong_as_double((long long)EMPTY) : __longlong_as_double((long long)key[i]);
+        }
+    }
+    __syncthreads();
+    if (bad) {
+        if (threadIdx.x == 0) { count[blockIdx.x] = 0; atomicOr(overflow, 1); }
+        return;
+    }
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int q = 0; q <= VI_HASH; ++q) c += first[q] != 0x7fffffff ? 1 : 0;
+        count[blockIdx.x] = c;
+    }
+    if (r >= M) return;
+    const int s = r >> 6;
+    const size_t cs = uw8 ? (size_t)s * uw8 * 64 : (size_t)cptr[s];
+    for (int j = 0; j < n; ++j) {
+        const unsigned long long k = (unsigned long long)__double_as_longlong(val[p0 + j]);
+        code[cs + ((size_t)(j >> 3) * 64 + lane) * 8 + (j & 7)] = (unsigned char)rank[slot(k, true)];
+    }
+}
+// the workgroups' dictionaries back to back: dict[dptr[b] + k] = dict_tmp[b * VI_MAX + k]
+__global__ __launch_bounds__(BLOCK) void k_vi_compact(const double *__restrict__ dict_tmp, const int *__restrict__ dptr, double *__restrict__ dict) {
+    const int b = blockIdx.x, n = dptr[b + 1] - dptr[b];
+    if ((int)threadIdx.x < n) dict[dptr[b] + threadIdx.x] = dict_tmp[(size_t)b * VI_MAX + threadIdx.x];
 }
 
 // ---- setup: the 16-bit column codes of k_csr_cc16 / k_sell, on the device (round 4) ----

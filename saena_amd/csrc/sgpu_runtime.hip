@@ -174,7 +174,20 @@ struct CsrPart {
     int64_t         sp_bytes = 0;      // values + pattern ids + x + y as this form stores them
     bool            sp_ok = false, sp_wide = false;   // sp_wide: a table per group of 1024 rows (k_sellp<WIDE>; sp_w = the largest, in ints)
     char            sp_tried = 0;
-    void free_sellp() { hipFree(sp_pat); hipFree(sp_tab); hipFree(sp_wgptr); hipFree(sp_rbase); sp_pat = nullptr; sp_tab = nullptr; sp_wgptr = nullptr; sp_rbase = nullptr; sp_ok = false; sp_wide = false; sp_tried = 0; }      // (and k_sellpx with it: free_sell)
+    // value-indexed row patterns (variant 17, k_vidx): 8-bit codes into per-workgroup dictionaries instead of the values; shares
+    // sp_pat / sp_tab / sp_rbase (freed with them)
+    unsigned char  *vi_code = nullptr;
+    int            *vi_cptr = nullptr, *vi_dptr = nullptr;
+    double         *vi_dict = nullptr;
+    int             vi_uw8 = 0;           // every slice has this many code positions (a multiple of 8), or 0: read vi_cptr
+    int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
+    bool            vi_ok = false;
+    char            vi_tried = 0;
+    void free_vidx() {
+        hipFree(vi_code); hipFree(vi_cptr); hipFree(vi_dptr); hipFree(vi_dict);
+        vi_code = nullptr; vi_cptr = vi_dptr = nullptr; vi_dict = nullptr; vi_ok = false; vi_tried = 0;
+    }
+    void free_sellp() { free_vidx(); hipFree(sp_pat); hipFree(sp_tab); hipFree(sp_wgptr); hipFree(sp_rbase); sp_pat = nullptr; sp_tab = nullptr; sp_wgptr = nullptr; sp_rbase = nullptr; sp_ok = false; sp_wide = false; sp_tried = 0; }      // (and k_sellpx with it: free_sell)
     // the column codes of k_sell alone (k_sellp keeps the values and the slice pointers)
     void free_sell_columns() {
         hipFree(sl_col); hipFree(sl_len); hipFree(sl_base); hipFree(sl_segptr);
@@ -1093,6 +1106,70 @@ int build_sellpx(CsrPart &P) {
     return SGPU_OK;
 }
 
+// k_vidx on top of build_sellp's pattern ids (one table, not the per-workgroup tables of sp_wide): the values as 8-bit codes into a
+// dictionary per workgroup of 256 rows, built on the device from the CSR values (k_vi_build).  Slices of 64 rows, each padded to its
+// longest row rounded up to 8 positions.  The operator is refused where a workgroup holds more than VI_MAX distinct values.
+int build_vidx(CsrPart &P) {
+    if (P.vi_ok || P.vi_tried || !P.sp_ok || P.sp_wide || P.h_rp.empty() || !P.val || !P.row_ptr) return SGPU_OK;
+    P.vi_tried = 1;
+    const int M = P.nrows;
+    if (M == 0) return SGPU_OK;
+    const int ns = (M + 63) / 64, ngrp = (ns + 3) / 4;
+    std::vector<int> ptr((size_t)ns + 1, 0);
+    int64_t tot = 0;
+    bool uniform = true;
+    int w8_0 = 0;
+    for (int s = 0; s < ns; ++s) {
+        int w = 0;
+        for (int r = s * 64; r < std::min(M, s * 64 + 64); ++r) w = std::max(w, P.h_rp[(size_t)r + 1] - P.h_rp[(size_t)r]);
+        const int w8 = (w + 7) & ~7;
+        if (s == 0) w8_0 = w8;
+        else if (w8 != w8_0 && !(s == ns - 1 && w8 < w8_0)) uniform = false;     // (a narrower last slice is padded up)
+        tot += (int64_t)w8 * 64;
+        if (tot > (int64_t)INT32_MAX - 1024) return SGPU_OK;
+        ptr[(size_t)s + 1] = (int)tot;
+    }
+    if (uniform && w8_0 > 0 && (int64_t)ns * w8_0 * 64 <= (int64_t)INT32_MAX - 1024) tot = (int64_t)ns * w8_0 * 64;
+    else uniform = false;
+    const size_t nb = (size_t)tot + 512;
+    if (hipMalloc(reinterpret_cast<void **>(&P.vi_code), nb) != hipSuccess) { P.vi_code = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nb); }
+    HIPCHK(hipMemsetAsync(P.vi_code, 0, nb, g.cs));
+    if (!uniform) CHK(dev_upload(&P.vi_cptr, ptr.data(), ptr.size()));
+    DevBuf tmp;
+    int *d_cnt = nullptr, *d_flag = nullptr;
+    CHK(tmp.alloc((size_t)ngrp * sk::VI_MAX));
+    if (hipMalloc(reinterpret_cast<void **>(&d_cnt), ((size_t)ngrp + 1) * sizeof(int)) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc failed");
+    struct F { int *p; ~F() { hipFree(p); } } fcnt{d_cnt};
+    d_flag = d_cnt + ngrp;
+    HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g.cs));
+    SGPU_LAUNCH(sk::k_vi_build, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)P.val, (const int *)P.row_ptr, (const int *)P.vi_cptr,
+                uniform ? w8_0 : 0, M, P.vi_code, tmp.p, d_cnt, d_flag);
+    HIPCHK(hipGetLastError());
+    std::vector<int> cnt((size_t)ngrp + 1);
+    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
+    HIPCHK(hipStreamSynchronize(g.cs));
+    if (cnt[(size_t)ngrp]) {                                   // a workgroup holds more than VI_MAX distinct values: refused
+        if (std::getenv("SAENA_SETUP_TIMING")) fprintf(stderr, "[sgpu] value-indexed form refused: a workgroup of 256 rows holds more than %d distinct values\n", sk::VI_MAX);
+        hipFree(P.vi_code); hipFree(P.vi_cptr); P.vi_code = nullptr; P.vi_cptr = nullptr;
+        return SGPU_OK;
+    }
+    std::vector<int> dptr((size_t)ngrp + 1, 0);
+    int dmax = 0;
+    for (int b = 0; b < ngrp; ++b) { dptr[(size_t)b + 1] = dptr[(size_t)b] + cnt[(size_t)b]; dmax = std::max(dmax, cnt[(size_t)b]); }
+    CHK(dev_upload(&P.vi_dptr, dptr.data(), dptr.size()));
+    CHK(dev_upload(&P.vi_dict, (const double *)nullptr, 0, (size_t)dptr[(size_t)ngrp] + 1));
+    SGPU_LAUNCH(sk::k_vi_compact, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)tmp.p, (const int *)P.vi_dptr, P.vi_dict);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(g.cs));
+    P.vi_uw8 = uniform ? w8_0 : 0;
+    P.vi_bytes = tot + (P.sp_rbase ? 6 : 2) * (int64_t)M + 8 * (int64_t)P.ncols + 8 * (int64_t)M + 8 * (int64_t)dptr[(size_t)ngrp];
+    P.vi_ok = true;
+    if (std::getenv("SAENA_SETUP_TIMING"))
+        fprintf(stderr, "[sgpu] value-indexed row patterns: %d rows, %lld entries, %lld code bytes (%.2f per entry), at most %d distinct values per workgroup of 256 rows, %d in all dictionaries\n",
+                M, (long long)P.nnz, (long long)tot, (double)tot / (double)std::max<int64_t>(1, P.nnz), dmax, dptr[(size_t)ngrp]);
+    return SGPU_OK;
+}
+
 // The row-paired values of k_sellp2 on top of build_sellp's pattern ids: slices of 128 rows, a slice padded to its longest
 // row, position-major with the values of rows 2 l and 2 l + 1 side by side.
 int build_sellp2(CsrPart &P, const std::vector<double> &h_val_all) {
@@ -1467,6 +1544,19 @@ SellKernelFn pick_sellp(int epi, bool halo, bool pair, bool nt, bool wide) {
     if (wide) return nt ? pick_sellp_n<true, true>(epi, halo, pair) : pick_sellp_n<false, true>(epi, halo, pair);
     return nt ? pick_sellp_n<true, false>(epi, halo, pair) : pick_sellp_n<false, false>(epi, halo, pair);
 }
+template <bool HALO, bool NT>
+SellKernelFn pick_vidx_h(int epi) {
+    switch (epi) {
+        case sk::EPI_SPMV:     return sk::k_vidx<sk::EPI_SPMV, HALO, NT>;
+        case sk::EPI_RESIDUAL: return sk::k_vidx<sk::EPI_RESIDUAL, HALO, NT>;
+        case sk::EPI_JACOBI:   return sk::k_vidx<sk::EPI_JACOBI, HALO, NT>;
+        case sk::EPI_CHEBY0:   return sk::k_vidx<sk::EPI_CHEBY0, HALO, NT>;
+        case sk::EPI_CHEBYK:   return sk::k_vidx<sk::EPI_CHEBYK, HALO, NT>;
+        case sk::EPI_RSWEEP:   return sk::k_vidx<sk::EPI_RSWEEP, HALO, NT>;
+        default:               return sk::k_vidx<sk::EPI_SUB, HALO, NT>;
+    }
+}
+SellKernelFn pick_vidx(int epi, bool halo, bool nt) { return halo ? (nt ? pick_vidx_h<true, true>(epi) : pick_vidx_h<true, false>(epi)) : (nt ? pick_vidx_h<false, true>(epi) : pick_vidx_h<false, false>(epi)); }
 template <bool HALO, bool PAIR, bool NT>
 SellKernelFn pick_sellpx_h(int epi) {
     switch (epi) {
@@ -1574,6 +1664,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
     a.c0 = e.c0; a.c1 = e.c1; a.skip = skip;
     a.segtab = nullptr; a.segptr = nullptr; a.ccol = nullptr; a.cc_ob = 12; a.dst = nullptr; a.cmptr = nullptr;
     a.ptab = nullptr; a.pt_w = 0; a.pt_n = 0; a.ncols = P.ncols; a.nt_from = 0; a.uw = 0; a.rbase = nullptr;
+    a.vcode = nullptr; a.vcptr = nullptr; a.vdict = nullptr; a.vdptr = nullptr;
     static const int st_plain_env = std::getenv("SAENA_STORE_PLAIN") ? std::atoi(std::getenv("SAENA_STORE_PLAIN")) : 0;
     a.st_plain = st_plain_env;
     static const int nt_rt = std::getenv("SAENA_STREAM_NT") ? std::atoi(std::getenv("SAENA_STREAM_NT")) : 0;
@@ -1588,6 +1679,16 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
             : epi == sk::EPI_JACOBI ? sk::k_dense_rows<sk::EPI_JACOBI> : epi == sk::EPI_CHEBY0 ? sk::k_dense_rows<sk::EPI_CHEBY0>
             : epi == sk::EPI_CHEBYK ? sk::k_dense_rows<sk::EPI_CHEBYK> : epi == sk::EPI_RSWEEP ? sk::k_dense_rows<sk::EPI_RSWEEP> : sk::k_dense_rows<sk::EPI_SUB>;
         SGPU_LAUNCH(kd, dim3((P.nrows + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, (const double *)P.dense, P.nrows, P.ncols);
+    } else if (P.variant == 17) {                                 // row patterns + 8-bit value codes, a lane per row
+        if (!P.vi_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the value-indexed row-pattern form was not built");
+        a.blk_row = nullptr; a.nblk = P.nslices ? P.nslices : (P.nrows + 63) / 64;
+        a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n; a.rbase = P.sp_rbase;
+        a.vcode = P.vi_code; a.vcptr = P.vi_cptr; a.vdict = P.vi_dict; a.vdptr = P.vi_dptr; a.uw = P.vi_uw8;
+        static const int nt_envv = std::getenv("SAENA_SELLP_NT") ? std::atoi(std::getenv("SAENA_SELLP_NT")) : -1;
+        const bool nt = nt_envv >= 0 ? nt_envv != 0 : P.vi_bytes > (int64_t)256 * 1024 * 1024;
+        a.nt_from = nt ? resident_slices(a.nblk, (double)P.nnz / (double)std::max(1, a.nblk)) : 0;     // (about a byte of codes per entry)
+        const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
+        SGPU_LAUNCH(pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
     } else if (P.variant == 15) {                                 // k_sellp with x in LDS windows
         if (!P.spx_ok || !P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
         a.blk_row = nullptr; a.nblk = P.nslices;
@@ -2447,7 +2548,7 @@ int sgpu_op_set_lanes_per_row(sgpu_op *op, int lanes) {
 }
 
 // the kernel forms, by number: ONE table, whose length is what set_variant, the plan cache's lookup and its store accept
-static const char *const VARIANT_NAMES[] = {"k_csr_stream<16KiB>", "k_csr_stream<32KiB>", "k_csr_vector", "k_csr_cc16<16KiB>", "k_csr_cc16<32KiB>", "k_dense_rows", "k_csr_wave", "k_csr_cm<16KiB>", "k_csr_cm<32KiB>", "k_sell", "k_csr_xlds", "k_sellp", "k_sellx", "k_rowt", "k_sellp2", "k_sellpx", "k_csr_xldsr"};   // (3, 4, 7, 8 are named with their slot/offset split below)
+static const char *const VARIANT_NAMES[] = {"k_csr_stream<16KiB>", "k_csr_stream<32KiB>", "k_csr_vector", "k_csr_cc16<16KiB>", "k_csr_cc16<32KiB>", "k_dense_rows", "k_csr_wave", "k_csr_cm<16KiB>", "k_csr_cm<32KiB>", "k_sell", "k_csr_xlds", "k_sellp", "k_sellx", "k_rowt", "k_sellp2", "k_sellpx", "k_csr_xldsr", "k_vidx"};   // (3, 4, 7, 8 are named with their slot/offset split below)
 static constexpr int MAX_VARIANT = (int)(sizeof VARIANT_NAMES / sizeof VARIANT_NAMES[0]) - 1;
 
 int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_name) {
@@ -2462,7 +2563,7 @@ int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_nam
             const_cast<sgpu_op *>(op)->vname = buf;
             *kernel_name = op->vname.c_str();
         } else {
-            *kernel_name = (v == 11 && op->loc.sp_rbase) ? (op->loc.sp_wide ? "k_sellp<wide,rowbase>" : "k_sellp<rowbase>") : (v == 11 && op->loc.sp_wide) ? "k_sellp<wide>" : (v == 14 && op->loc.sp_wide) ? "k_sellp2<wide>" : (v == 9 && op->loc.sl_sorted) ? "k_sell<sorted>" : VARIANT_NAMES[v];      // the compact table around 1024 threads
+            *kernel_name = (v == 17 && op->loc.sp_rbase) ? "k_vidx<rowbase>" : (v == 11 && op->loc.sp_rbase) ? (op->loc.sp_wide ? "k_sellp<wide,rowbase>" : "k_sellp<rowbase>") : (v == 11 && op->loc.sp_wide) ? "k_sellp<wide>" : (v == 14 && op->loc.sp_wide) ? "k_sellp2<wide>" : (v == 9 && op->loc.sl_sorted) ? "k_sell<sorted>" : VARIANT_NAMES[v];      // the compact table around 1024 threads
         }
     }
     return SGPU_OK;
@@ -2471,6 +2572,14 @@ int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_nam
 int sgpu_op_set_variant(sgpu_op *op, int variant) {
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     if (variant < 0 || variant > MAX_VARIANT) return fail(SGPU_ERR_ARG, "variant must be 0..%d", MAX_VARIANT);
+    if (variant == 17) {
+        CHK(build_sell_values(op->loc));
+        CHK(build_sellp(op->loc));
+        CHK(build_vidx(op->loc));
+        if (!op->loc.vi_ok)
+            return fail(SGPU_ERR_ARG, "the value-indexed row-pattern form needs what the row-pattern form needs (k_sellp) with ONE pattern table, and at most %d "
+                                      "distinct values (as bit patterns) in every group of %d rows", sk::VI_MAX, sk::BLOCK);
+    }
     if (variant == 15) {
         CHK(build_sell_values(op->loc));
         CHK(build_sellp(op->loc));
@@ -2536,7 +2645,7 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
 
 // ---- plan cache: what the autotune chose for an operator of this shape on this device, so that a second process picks the
 // same kernel (same summation order: bit-identical solves across processes) and skips the sweep.  One line per operator in
-// $SAENA_PLAN_CACHE, default $XDG_CACHE_HOME or ~/.cache + /saena_amd/plans-v3.tsv (v3: round 4 added candidate forms -- plans an older library cached must not shadow them); SAENA_PLAN_CACHE=off disables it.
+// $SAENA_PLAN_CACHE, default $XDG_CACHE_HOME or ~/.cache + /saena_amd/plans-v4.tsv (v3: round 4 added candidate forms, v4: the value-indexed form -- plans an older library cached must not shadow them); SAENA_PLAN_CACHE=off disables it.
 extern "C++" {                                              // (helpers with C++ types inside the extern "C" block)
 namespace {
 uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
@@ -2556,7 +2665,7 @@ std::string plan_cache_path() {
     ::mkdir(dir.c_str(), 0755);
     dir += "/saena_amd";
     ::mkdir(dir.c_str(), 0755);
-    return dir + "/plans-v3.tsv";
+    return dir + "/plans-v4.tsv";
 }
 // key: device, sizes, what the kernel does (smoother epilogue or plain product, halo mask), the row-length histogram in
 // powers of two and the column ids at 256 evenly spaced entries
@@ -2619,12 +2728,13 @@ void finish_plan(sgpu_op *op, int bv) {
             op->loc.cm_ok[k] = false; op->loc.cm_tried[k] = 0;
         }
     if (bv != 14 && !keep) op->loc.free_sellp2();
-    if (bv == 14 && !keep) {                                      // k_sellp2 keeps the pattern ids and the table; k_sell's / k_sellp's arrays go
+    if (bv != 17 && !keep) op->loc.free_vidx();
+    if ((bv == 14 || bv == 17) && !keep) {                        // k_sellp2 / k_vidx keep the pattern ids and the table; k_sell's / k_sellp's arrays go
         CsrPart &L = op->loc;
         L.free_sell_columns();
         hipFree(L.sl_val); hipFree(L.sl_ptr); hipFree(L.sl_perm); L.sl_val = nullptr; L.sl_ptr = nullptr; L.sl_perm = nullptr;
         L.sl_vals = false; L.sl_vals_tried = 0; L.sl_sorted = false;                       // (a later set_variant(11) re-orders the values again, from the device's CSR copy)
-    } else if (bv != 9 && bv != 11 && bv != 15 && !keep) op->loc.free_sell();
+    } else if (bv != 9 && bv != 11 && bv != 15 && !keep) op->loc.free_sell();        // (with the pattern ids, the table and k_vidx's codes)
     else if ((bv == 11 || bv == 15) && !keep) op->loc.free_sell_columns();    // k_sellp / k_sellpx keep the values and the slice pointers only
     else if (bv == 9 && !keep) op->loc.free_sellp();
     if (bv != 15 && !keep) op->loc.free_sellpx();
@@ -2639,7 +2749,7 @@ void finish_plan(sgpu_op *op, int bv) {
     if (!keep && !op->h_val_all.empty()) {
         if (op->h_val_all.size() >= ((size_t)1 << 22) && !std::getenv("SAENA_NO_ASYNC_FREE")) {
             auto *junk = new std::vector<double>(std::move(op->h_val_all));
-            std::thread([junk] { delete junk; }).detach();
+            try { std::thread([junk] { delete junk; }).detach(); } catch (...) { delete junk; }       // (no thread to be had: free it here)
         }
         std::vector<double>().swap(op->h_val_all);
     }
@@ -2650,7 +2760,7 @@ void finish_plan(sgpu_op *op, int bv) {
         }
 }
 // does the form add a row's products one after the other in column order (the reference's sum, whatever else is tuned)?
-bool sequential_sum(int v, int lanes) { return v == 9 || v == 11 || v == 13 || v == 14 || v == 15 || (lanes == 1 && (v == 0 || v == 1 || v == 3 || v == 4 || v == 7 || v == 8)); }
+bool sequential_sum(int v, int lanes) { return v == 9 || v == 11 || v == 13 || v == 14 || v == 15 || v == 17 || (lanes == 1 && (v == 0 || v == 1 || v == 3 || v == 4 || v == 7 || v == 8)); }
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 } // namespace
 } // extern "C++"
@@ -2701,6 +2811,14 @@ int sgpu_op_autotune(sgpu_op *op) {
             if (!std::getenv("SAENA_NO_SELLP")) {                                                    // rows that repeat a few patterns: no column stream
                 CHK(build_sellp(op->loc));
                 if (op->loc.sp_ok) variants.push_back(11);
+                // ... and the values as 8-bit codes into a dictionary per workgroup (operators of at most VI_MAX distinct values per
+                // 256 rows: the constant-coefficient stencil levels and their transfers): 1 B per entry instead of 8.  Offered where the
+                // values are more than the eight XCDs' L2 (32 MiB) hold from one launch to the next -- the bytes it saves come from the
+                // Infinity Cache or HBM; below that it was not measured and the plan stays as it was (128^3 fine level: 111 MB)
+                if (op->loc.sp_ok && !op->loc.sp_wide && 8 * op->loc.nnz > ((int64_t)32 << 20) && !std::getenv("SAENA_NO_VALUE_INDEX")) {
+                    CHK(build_vidx(op->loc));
+                    if (op->loc.vi_ok) variants.push_back(17);
+                }
                 // ... and a lane per two rows: half the gathers.  With a table per workgroup (sp_wide: the 68-entry level) it wins on the
                 // operator of 128^3 (110 against 116 us, k_sellpx 114) and ties on that of 256^3 (940 / 945, k_sellpx 890), whose row-paired
                 // copy is 4.5 GB: tried up to 1 GB (profiles/r03_sellp_pergroup_tables.log).  (Round 4: the device makes the copy in
@@ -2787,7 +2905,7 @@ int sgpu_op_autotune(sgpu_op *op) {
     std::vector<std::pair<int, int>> cands;
     for (int v : variants)
         for (int gl : (v == 10 ? lanes_x : v == 16 ? lanes_r : lanes)) {
-            if ((v == 9 || v == 11 || v == 12 || v == 13 || v == 14 || v == 15) && gl != lanes.front()) continue;      // a lane per row (piece) whatever the setting
+            if ((v == 9 || v == 11 || v == 12 || v == 13 || v == 14 || v == 15 || v == 17) && gl != lanes.front()) continue;      // a lane per row (piece) whatever the setting
             if (v == 5 && gl != lanes.front()) continue;                   // one wave per dense row likewise
             cands.push_back({v, gl});
         }
