@@ -1351,9 +1351,11 @@ __global__ __launch_bounds__(XL_BLOCK) void k_csr_xlds(const SpmvArgs a, const X
                     for (int u = 0; u < 4; ++u) {
                         double x0 = xs[c[u].x & 0xffffu], x1 = xs[c[u].x >> 16], x2 = xs[c[u].y & 0xffffu], x3 = xs[c[u].y >> 16];
                         if (wj[u] < 0) x0 = x1 = x2 = x3 = 0.0;
-                        else if (i[u] < lo[u] || i[u] + 4 > hi[u]) {
-                            x0 = stray(i[u], lo[u], hi[u]) ? 0.0 : x0;     x1 = stray(i[u] + 1, lo[u], hi[u]) ? 0.0 : x1;
-                            x2 = stray(i[u] + 2, lo[u], hi[u]) ? 0.0 : x2; x3 = stray(i[u] + 3, lo[u], hi[u]) ? 0.0 : x3;
+                        else if (i[u] < lo[u] || i[u] + 4 > hi[u]) {      // entries of other pieces: BOTH factors zeroed (an inf or NaN value stays out)
+                            if (stray(i[u], lo[u], hi[u]))     { v01[u].x = 0.0; x0 = 0.0; }
+                            if (stray(i[u] + 1, lo[u], hi[u])) { v01[u].y = 0.0; x1 = 0.0; }
+                            if (stray(i[u] + 2, lo[u], hi[u])) { v23[u].x = 0.0; x2 = 0.0; }
+                            if (stray(i[u] + 3, lo[u], hi[u])) { v23[u].y = 0.0; x3 = 0.0; }
                         }
 #pragma unroll
                         for (int j = 0; j < RP; ++j)
@@ -1405,9 +1407,12 @@ __global__ __launch_bounds__(XL_BLOCK) void k_csr_xlds(const SpmvArgs a, const X
                 for (int u = 0; u < 4; ++u) {
                     double x0 = xs[c[u].x & 0xffffu], x1 = xs[c[u].x >> 16], x2 = xs[c[u].y & 0xffffu], x3 = xs[c[u].y >> 16];
                     if (u > 0 && q + G * u >= nq) x0 = x1 = x2 = x3 = 0.0;
-                    else if (i[u] < p0 || i[u] + 4 > p1) {        // first / last quad: the neighbours' entries (other rows, other windows) count as zero
-                        x0 = stray(i[u], p0, p1) ? 0.0 : x0;     x1 = stray(i[u] + 1, p0, p1) ? 0.0 : x1;
-                        x2 = stray(i[u] + 2, p0, p1) ? 0.0 : x2; x3 = stray(i[u] + 3, p0, p1) ? 0.0 : x3;
+                    else if (i[u] < p0 || i[u] + 4 > p1) {        // first / last quad: the neighbours' entries (other rows, other windows) count as
+                        // zero with BOTH factors zeroed, as in k_csr_wave: an inf or NaN value of a neighbour stays out of this row's sum
+                        if (stray(i[u], p0, p1))     { v01[u].x = 0.0; x0 = 0.0; }
+                        if (stray(i[u] + 1, p0, p1)) { v01[u].y = 0.0; x1 = 0.0; }
+                        if (stray(i[u] + 2, p0, p1)) { v23[u].x = 0.0; x2 = 0.0; }
+                        if (stray(i[u] + 3, p0, p1)) { v23[u].y = 0.0; x3 = 0.0; }
                     }
                     sum += v01[u].x * x0; sum += v01[u].y * x1; sum += v23[u].x * x2; sum += v23[u].y * x3;
                 }
