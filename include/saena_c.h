@@ -86,6 +86,31 @@ int   saena_band_matrix(saena_matrix_h *A, index_t M, unsigned int bandwidth);
  * A and B assembled, one rank in this round; C (a fresh handle's contents are replaced) is assembled on return */
 int   saena_matmat(saena_matrix_h *A, saena_matrix_h *B, saena_matrix_h *C);
 
+/* ---- tests: the sparse product of the setup from plain arrays, and which path served it ----
+ * C = A B with A (a_rows x b_rows) and B (b_rows x b_cols) in CSR (64-bit row pointers), through the code the setup
+ * multiplies with.  row_offset: global id of row 0 of A (an entry survives iff |c_ij| > 1e-14 or i + row_offset == j).
+ * B in one piece (b_col1 == NULL), or in two as the distributed setup holds it: entries [0, b_split) at b_col / b_val,
+ * entries [b_split, b_ptr[b_rows]) at b_col1 / b_val1, b_split a row boundary.
+ * PRECONDITION, checked here (an error, nothing runs): the columns of every row of B are distinct and ascending and
+ * below b_cols, the columns of A are rows of B.  Rows of A may repeat a column and come in any order.
+ * mode 0: what the setup does (the device kernel from 200 000 stored entries on where libsaena_amd.so has a context,
+ *         the host kernel when it declines or below);
+ *      1: the host kernel, whatever is installed;
+ *      2: [GPU] the device kernel whatever the size; a missing or declining device kernel is an error, not a host product.
+ * *c_nnz = entries of C; saena_debug_spgemm_result copies C out: c_ptr[a_rows + 1], c_col / c_val[*c_nnz], rows ascending
+ * by column.
+ * saena_debug_spgemm_stats: counters of the LAST product into last[], their sums over every product (the setup's
+ * included) since saena_debug_spgemm_stats_reset into total[]; either may be NULL; returns the number of counters, in
+ * this order (host.SPGEMM_STATS): host kernel rows on the dense accumulator, on the hash accumulator, rehash steps;
+ * device rows on light, medium, medium-try kept, medium-try abandoned, LDS accumulator, HBM accumulator; chunks; column
+ * windows of the LDS accumulator; 1 if the device kernel declined; 1 if the result is the device kernel's. */
+int  saena_debug_spgemm(int mode, index_t a_rows, index_t b_rows, index_t b_cols, const nnz_t *a_ptr, const index_t *a_col,
+                        const value_t *a_val, const nnz_t *b_ptr, const index_t *b_col, const value_t *b_val, nnz_t b_split,
+                        const index_t *b_col1, const value_t *b_val1, index_t row_offset, nnz_t *c_nnz);
+int  saena_debug_spgemm_result(nnz_t *c_ptr, index_t *c_col, value_t *c_val);
+int  saena_debug_spgemm_stats(long *last, long *total);
+void saena_debug_spgemm_stats_reset(void);
+
 /* ---- transfer operators (prolong_matrix / restrict_matrix) ---- */
 typedef struct saena_transfer_h saena_transfer_h;
 /* rows/cols are GLOBAL ids of this rank's fine rows; split_row = fine partition, split_col = coarse partition */

@@ -153,6 +153,9 @@ Csr transpose(const Csr &A) {
 } // namespace
 // C = A B on the GPU when libsaena_amd.so has a device context (sgpu_spgemm.hip installs this; bit-identical result)
 spgemm_hook_fn g_spgemm_hook = nullptr;
+// what the last product did, and every product since spgemm_stats_reset() (amg_setup.h)
+spgemm_stats g_spgemm_last, g_spgemm_total;
+void spgemm_stats_reset() { g_spgemm_last = spgemm_stats(); g_spgemm_total = spgemm_stats(); }
 double g_measured_chain_us = 0.0;
 namespace {
 
@@ -168,15 +171,47 @@ struct CsrRef {
     CsrRef(const Csr &M, const std::vector<index_t> &cols) : nrows(M.nrows), ptr(M.ptr.data()), col(cols.data()), val(M.val.data()) {}
 };
 
-Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0) {
+// who multiplies: what the setup does (the hook from SPGEMM_HOOK_MIN stored entries of A and B on, the host kernel when it
+// declines), or -- saena_debug_spgemm, the tests -- the host kernel with the hook ignored, or the hook whatever the size
+// of the operands, where a hook that is missing or declines is an error instead of a quiet host product
+enum spgemm_mode { SPGEMM_AUTO = 0, SPGEMM_HOST = 1, SPGEMM_DEVICE = 2 };
+constexpr size_t SPGEMM_HOOK_MIN = 200000;
+void stats_begin() { g_spgemm_last = spgemm_stats(); }
+void stats_end() { for (int s = 0; s < SPGEMM_NSTATS; ++s) g_spgemm_total.v[s] += g_spgemm_last.v[s]; }
+bool hook_wanted(spgemm_mode mode, size_t stored) {
+    if (mode == SPGEMM_HOST) return false;
+    if (mode == SPGEMM_DEVICE) {
+        if (!g_spgemm_hook) throw std::runtime_error("spgemm: no device kernel is installed (host-only library, no sgpu_init, or SAENA_HOST_SPGEMM)");
+        return true;
+    }
+    return g_spgemm_hook && stored >= SPGEMM_HOOK_MIN;
+}
+void hook_declined(spgemm_mode mode) {
+    g_spgemm_last.v[SPGEMM_DECLINED] = 1;
+    if (mode == SPGEMM_DEVICE) { stats_end(); throw std::runtime_error("spgemm: the device kernel declined the product"); }
+}
+
+Csr spgemm_host(const CsrRef &A, const Csr &B, index_t row_offset);
+Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0, spgemm_mode mode = SPGEMM_AUTO) {
+    stats_begin();
+    if (A.nrows > 0 && B.nrows > 0 && hook_wanted(mode, (size_t)A.ptr[A.nrows] + B.col.size())) {
+        Csr C;
+        C.nrows = A.nrows; C.ncols = B.ncols;
+        if (g_spgemm_hook(A.nrows, B.nrows, B.ncols, A.ptr, A.col, A.val, B.ptr.data(), B.col.data(), B.val.data(), 0, nullptr, nullptr,
+                          row_offset, C.ptr, C.col, C.val) == 0) {
+            g_spgemm_last.v[SPGEMM_ON_DEVICE] = 1;
+            stats_end();
+            return C;
+        }
+        hook_declined(mode);                                // the GPU declined (memory): the host kernel below
+    }
+    Csr C = spgemm_host(A, B, row_offset);
+    stats_end();
+    return C;
+}
+Csr spgemm_host(const CsrRef &A, const Csr &B, index_t row_offset) {
     Csr C;
     C.nrows = A.nrows; C.ncols = B.ncols;
-    if (g_spgemm_hook && A.nrows > 0 && B.nrows > 0 && ((size_t)A.ptr[A.nrows] + B.col.size()) >= 200000) {
-        if (g_spgemm_hook(A.nrows, B.nrows, B.ncols, A.ptr, A.col, A.val, B.ptr.data(), B.col.data(), B.val.data(), 0, nullptr, nullptr,
-                          row_offset, C.ptr, C.col, C.val) == 0)
-            return C;
-        C.ptr.clear(); C.col.clear(); C.val.clear();       // the GPU declined (memory): the host kernel below
-    }
     // work estimate per row for load balance
     std::vector<nnz_t> work((size_t)A.nrows + 1, 0);
     for (index_t i = 0; i < A.nrows; ++i) {
@@ -189,6 +224,7 @@ Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0) {
     std::vector<std::vector<value_t>> tval((size_t)T);
     std::vector<index_t> tlo((size_t)T, 0), thi((size_t)T, 0);
     std::vector<nnz_t> rowlen((size_t)A.nrows, 0);
+    std::vector<long> n_dense((size_t)T, 0), n_hash((size_t)T, 0), n_rehash((size_t)T, 0);      // rows per accumulator: g_spgemm_last
     parallel_rows(A.nrows, &work, [&](int t, index_t lo, index_t hi) {
         tlo[t] = lo; thi[t] = hi;
         // Two accumulators, same arithmetic (every output entry adds its products in generation order): an
@@ -208,6 +244,7 @@ Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0) {
             const nnz_t products = work[i + 1] - work[i] - 1;
             nnz_t cnt = 0;
             if (products > (nnz_t)B.ncols / 8) {                         // dense accumulator
+                ++n_dense[t];
                 if (acc.empty()) { acc.assign((size_t)B.ncols, 0.0); mark.assign((size_t)B.ncols, 0); }
                 cols.clear();
                 for (nnz_t ka = A.ptr[i]; ka < A.ptr[i + 1]; ++ka) {
@@ -225,6 +262,7 @@ Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0) {
                     mark[j] = 0;
                 }
             } else {                                                      // hash accumulator, grown by rehashing at load 1/2
+                ++n_hash[t];
                 size_t cap = 256;
                 const size_t want = 2 * (size_t)std::min<nnz_t>(products, A.ptr[i + 1] - A.ptr[i] + 64);
                 while (cap < want) cap *= 2;
@@ -255,6 +293,7 @@ Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0) {
                                 }
                                 hkey.swap(okey); hval.swap(oval);
                                 cap *= 2; mask = nmask;
+                                ++n_rehash[t];
                                 h = slot_of(j);
                             }
                             hkey[h] = j; hval[h] = 0.0; out.emplace_back(j, 0.0);
@@ -272,6 +311,11 @@ Csr spgemm(const CsrRef &A, const Csr &B, index_t row_offset = 0) {
             rowlen[i] = cnt;
         }
     });
+    for (int t = 0; t < T; ++t) {
+        g_spgemm_last.v[SPGEMM_HOST_DENSE] += n_dense[(size_t)t];
+        g_spgemm_last.v[SPGEMM_HOST_HASH] += n_hash[(size_t)t];
+        g_spgemm_last.v[SPGEMM_HOST_REHASH] += n_rehash[(size_t)t];
+    }
     C.ptr.resize((size_t)A.nrows + 1);
     C.ptr[0] = 0;
     for (index_t i = 0; i < A.nrows; ++i) C.ptr[i + 1] = C.ptr[i] + rowlen[i];
@@ -936,9 +980,10 @@ Csr stack_rows(const Csr &local, const Csr &halo) {
 // C = A [local; halo] without stacking the two pieces of B on the host when the GPU kernel takes them (it copies each piece to
 // its place in device memory; only the row pointers are stacked here): at 16 M rows per rank a stacked copy of level 1's
 // operator is 6.8 GB to allocate, fill and free for every product
-Csr spgemm_stacked(const CsrRef &A, const Csr &local, const Csr &halo, index_t row_offset) {
+Csr spgemm_stacked(const CsrRef &A, const Csr &local, const Csr &halo, index_t row_offset, spgemm_mode mode = SPGEMM_AUTO) {
     const nnz_t base = local.ptr[(size_t)local.nrows];
-    if (g_spgemm_hook && A.nrows > 0 && local.nrows + halo.nrows > 0 && ((size_t)A.ptr[A.nrows] + (size_t)base + halo.col.size()) >= 200000) {
+    stats_begin();
+    if (A.nrows > 0 && local.nrows + halo.nrows > 0 && hook_wanted(mode, (size_t)A.ptr[A.nrows] + (size_t)base + halo.col.size())) {
         Csr C;
         C.nrows = A.nrows; C.ncols = local.ncols;
         std::vector<nnz_t> ptr((size_t)local.nrows + (size_t)halo.nrows + 1);
@@ -946,10 +991,16 @@ Csr spgemm_stacked(const CsrRef &A, const Csr &local, const Csr &halo, index_t r
         for (index_t i = 0; i < halo.nrows; ++i) ptr[(size_t)local.nrows + 1 + i] = base + halo.ptr[(size_t)i + 1];
         if (g_spgemm_hook(A.nrows, local.nrows + halo.nrows, local.ncols, A.ptr, A.col, A.val, ptr.data(), local.col.data(), local.val.data(), base,
                           halo.col.empty() ? local.col.data() : halo.col.data(), halo.val.empty() ? local.val.data() : halo.val.data(),
-                          row_offset, C.ptr, C.col, C.val) == 0)
+                          row_offset, C.ptr, C.col, C.val) == 0) {
+            g_spgemm_last.v[SPGEMM_ON_DEVICE] = 1;
+            stats_end();
             return C;
+        }
+        hook_declined(mode);
     }
-    return spgemm(A, stack_rows(local, halo), row_offset);
+    Csr C = spgemm_host(A, stack_rows(local, halo), row_offset);
+    stats_end();
+    return C;
 }
 // multi-gigabyte temporaries are handed to a detached thread to be freed (unmapping them took 2.8 s per rank of the 323^3
 // setup, between the phases that need the cores): SAENA_NO_ASYNC_FREE=1 frees in place
@@ -1557,6 +1608,47 @@ int amg_hierarchy::setup_distributed(saena_matrix *Ad, const amg_options &o) {
     Ad->eig_max_of_invdiagXA = A_global->eig_max_of_invdiagXA;
     distribute(c, Ad->split);
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// saena_debug_spgemm: the products of the setup from plain arrays (tests).  The operands are checked here -- ids in range,
+// B's rows distinct and ascending -- because a device kernel trusts them.
+void debug_spgemm(int mode, index_t a_rows, index_t b_rows, index_t b_cols, const nnz_t *a_ptr, const index_t *a_col, const value_t *a_val,
+                  const nnz_t *b_ptr, const index_t *b_col, const value_t *b_val, nnz_t b_split, const index_t *b_col1, const value_t *b_val1,
+                  index_t row_offset, std::vector<nnz_t> &c_ptr, std::vector<index_t> &c_col, std::vector<value_t> &c_val) {
+    if (mode < SPGEMM_AUTO || mode > SPGEMM_DEVICE) throw std::runtime_error("debug_spgemm: mode is 0 (auto), 1 (host) or 2 (device)");
+    if (a_rows < 0 || b_rows < 0 || b_cols < 0 || !a_ptr || !b_ptr || a_ptr[0] != 0 || b_ptr[0] != 0) throw std::runtime_error("debug_spgemm: bad sizes or row pointers");
+    for (index_t i = 0; i < a_rows; ++i) if (a_ptr[i + 1] < a_ptr[i]) throw std::runtime_error("debug_spgemm: A's row pointers descend");
+    for (index_t k = 0; k < b_rows; ++k) if (b_ptr[k + 1] < b_ptr[k]) throw std::runtime_error("debug_spgemm: B's row pointers descend");
+    const nnz_t a_nnz = a_ptr[a_rows], b_nnz = b_ptr[b_rows];
+    for (nnz_t k = 0; k < a_nnz; ++k) if (a_col[k] < 0 || a_col[k] >= b_rows) throw std::runtime_error("debug_spgemm: a column of A is not a row of B");
+    index_t split_row = b_rows;                             // B in two pieces: rows [0, split_row) and the rest
+    if (b_col1) {
+        if (b_split < 0 || b_split > b_nnz) throw std::runtime_error("debug_spgemm: b_split outside B");
+        split_row = (index_t)(std::lower_bound(b_ptr, b_ptr + b_rows + 1, b_split) - b_ptr);
+        if (b_ptr[split_row] != b_split) throw std::runtime_error("debug_spgemm: b_split is not a row boundary of B");
+    }
+    const nnz_t n0 = b_col1 ? b_split : b_nnz;
+    Csr local, halo;
+    local.nrows = split_row; local.ncols = b_cols;
+    local.ptr.assign(b_ptr, b_ptr + split_row + 1);
+    local.col.assign(b_col, b_col + n0); local.val.assign(b_val, b_val + n0);
+    halo.nrows = b_rows - split_row; halo.ncols = b_cols;
+    halo.ptr.assign((size_t)halo.nrows + 1, 0);
+    for (index_t k = 0; k < halo.nrows; ++k) halo.ptr[(size_t)k + 1] = b_ptr[split_row + k + 1] - n0;
+    if (b_col1) { halo.col.assign(b_col1, b_col1 + (b_nnz - n0)); halo.val.assign(b_val1, b_val1 + (b_nnz - n0)); }
+    for (const Csr *piece : {&local, &halo})
+        for (index_t k = 0; k < piece->nrows; ++k)
+            for (nnz_t q = piece->ptr[(size_t)k]; q < piece->ptr[(size_t)k + 1]; ++q) {
+                const index_t j = piece->col[(size_t)q];
+                if (j < 0 || j >= b_cols) throw std::runtime_error("debug_spgemm: a column of B is out of range");
+                if (q > piece->ptr[(size_t)k] && piece->col[(size_t)q - 1] >= j) throw std::runtime_error("debug_spgemm: the columns of a row of B must be distinct and ascending");
+            }
+    CsrRef A;
+    A.nrows = a_rows; A.ptr = a_ptr; A.col = a_col; A.val = a_val;
+    Csr C = b_col1 ? spgemm_stacked(A, local, halo, row_offset, (spgemm_mode)mode) : spgemm(A, local, row_offset, (spgemm_mode)mode);
+    if (C.ptr.empty()) C.ptr.assign((size_t)a_rows + 1, 0);
+    c_ptr = std::move(C.ptr); c_col = std::move(C.col); c_val = std::move(C.val);
 }
 
 } // namespace saena_host

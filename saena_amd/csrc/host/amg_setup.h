@@ -23,6 +23,38 @@ typedef int (*spgemm_hook_fn)(int a_rows, int b_rows, int b_cols, const long *a_
                               const long *b_ptr, const int *b_col, const double *b_val, long b_split, const int *b_col1, const double *b_val1,
                               int row_offset, std::vector<long> &c_ptr, std::vector<int> &c_col, std::vector<double> &c_val);
 extern spgemm_hook_fn g_spgemm_hook;
+// PRECONDITION of the hook, of the host kernel's "bit for bit" partner: the columns of every row of B are DISTINCT and
+// ASCENDING (the device kernels spread a row of B over their lanes without atomics on the sums, and bisect it by column).
+// Every right operand of the setup is an assembled operator, a smoothed prolongator whose rows were sorted and merged, or
+// rows fetched from one of those; see gpu_spgemm in sgpu_spgemm.hip.  A's rows may come in any order, duplicates included.
+
+// Which path served the rows of a product: counted by the host kernel and by the host side of the device driver (no
+// kernel takes part), for the tests that must know which accumulator they exercised.  g_spgemm_last is the last product,
+// g_spgemm_total the sum over the products since spgemm_stats_reset().  The setup multiplies from one thread at a time.
+enum {
+    SPGEMM_HOST_DENSE = 0,    // host kernel: rows on the dense accumulator (products > columns / 8)
+    SPGEMM_HOST_HASH,         //              rows on the hash accumulator
+    SPGEMM_HOST_REHASH,       //              grow-and-rehash steps of the hash accumulator
+    SPGEMM_LIGHT,             // device: rows on k_spgemm_light
+    SPGEMM_MEDIUM,            //         rows on k_spgemm_medium<false>
+    SPGEMM_TRY_KEPT,          //         rows k_spgemm_medium<true> finished in its table
+    SPGEMM_TRY_ABANDONED,     //         rows it gave up (more than 3072 distinct columns, or the table full inside a step)
+    SPGEMM_LDS,               //         abandoned rows served by k_spgemm_lds (dense accumulator in LDS windows)
+    SPGEMM_HBM,               //         abandoned rows served by k_spgemm_heavy (dense accumulator in HBM)
+    SPGEMM_CHUNKS,            //         chunks of rows the driver ran
+    SPGEMM_WINDOWS,           //         column windows of k_spgemm_lds (0: that kernel did not run)
+    SPGEMM_DECLINED,          // the hook was asked and declined
+    SPGEMM_ON_DEVICE,         // the result is the hook's
+    SPGEMM_NSTATS
+};
+struct spgemm_stats { long v[SPGEMM_NSTATS] = {}; };
+extern spgemm_stats g_spgemm_last, g_spgemm_total;
+void spgemm_stats_reset();
+// saena_debug_spgemm (include/saena_c.h): C = A B from plain arrays through the setup's own product code.
+// mode: 0 what the setup does, 1 the host kernel, 2 the hook (throws when there is none or when it declines)
+void debug_spgemm(int mode, index_t a_rows, index_t b_rows, index_t b_cols, const nnz_t *a_ptr, const index_t *a_col, const value_t *a_val,
+                  const nnz_t *b_ptr, const index_t *b_col, const value_t *b_val, nnz_t b_split, const index_t *b_col1, const value_t *b_val1,
+                  index_t row_offset, std::vector<nnz_t> &c_ptr, std::vector<index_t> &c_col, std::vector<value_t> &c_val);
 // The exchange chain of one multi-rank apply in microseconds (pack -> RCCL send/recv -> boundary rows), as the GPU runtime
 // MEASURED it on this job's communicator at sgpu_init (a ping-pong with the neighbouring rank; the maximum over the
 // ranks, so every rank holds the same number); 0: not measured (host-only library, one rank).  The agglomeration model

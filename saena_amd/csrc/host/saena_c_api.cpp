@@ -43,6 +43,10 @@ void fill_desc(const DistLayout &L, const std::vector<value_t> *inv_diag, sgpu_o
     d->inv_diag = inv_diag && !inv_diag->empty() ? inv_diag->data() : nullptr;
     d->halo_fp32 = 0;
 }
+// the product of the last saena_debug_spgemm, until saena_debug_spgemm_result fetches it
+std::vector<nnz_t> dbg_ptr;
+std::vector<index_t> dbg_col;
+std::vector<value_t> dbg_val;
 } // namespace
 
 extern "C" {
@@ -155,6 +159,30 @@ int saena_matmat(saena_matrix_h *A, saena_matrix_h *B, saena_matrix_h *C) {
         C->A.assemble();
     });
 }
+
+// ---- the setup's product from plain arrays, and which path served it (tests) ----
+int saena_debug_spgemm(int mode, index_t a_rows, index_t b_rows, index_t b_cols, const nnz_t *a_ptr, const index_t *a_col, const value_t *a_val,
+                       const nnz_t *b_ptr, const index_t *b_col, const value_t *b_val, nnz_t b_split, const index_t *b_col1, const value_t *b_val1,
+                       index_t row_offset, nnz_t *c_nnz) {
+    return guard([&] {
+        dbg_ptr.clear(); dbg_col.clear(); dbg_val.clear();
+        debug_spgemm(mode, a_rows, b_rows, b_cols, a_ptr, a_col, a_val, b_ptr, b_col, b_val, b_split, b_col1, b_val1, row_offset, dbg_ptr, dbg_col, dbg_val);
+        if (c_nnz) *c_nnz = (nnz_t)dbg_col.size();
+    });
+}
+int saena_debug_spgemm_result(nnz_t *c_ptr, index_t *c_col, value_t *c_val) {
+    return guard([&] {
+        if (dbg_ptr.empty()) throw std::runtime_error("saena_debug_spgemm_result: no product to fetch");
+        std::copy(dbg_ptr.begin(), dbg_ptr.end(), c_ptr);
+        std::copy(dbg_col.begin(), dbg_col.end(), c_col);
+        std::copy(dbg_val.begin(), dbg_val.end(), c_val);
+    });
+}
+int saena_debug_spgemm_stats(long *last, long *total) {
+    for (int s = 0; s < SPGEMM_NSTATS; ++s) { if (last) last[s] = g_spgemm_last.v[s]; if (total) total[s] = g_spgemm_total.v[s]; }
+    return SPGEMM_NSTATS;
+}
+void saena_debug_spgemm_stats_reset(void) { spgemm_stats_reset(); }
 
 int saena_laplacian3D_set_rhs(saena_matrix_h *Ah, index_t mx, index_t my, index_t mz, value_t *rhs_local) {
     return guard([&] {

@@ -4,7 +4,8 @@
 // The setup is host code in the reference and stays host code here; these two products are 70-80 % of it
 // (measured: 256^3, 16 host threads: 55 of 76 s), so they run on the GPU when one is there (saena_host::g_spgemm_hook,
 // installed by sgpu_init; SAENA_HOST_SPGEMM=1 keeps the host kernel).  The result is the host kernel's BIT FOR BIT
-// (tests/test_gpu_spgemm.py), which is what keeps the hierarchy equal to the reference's printed sizes: every output
+// (tests/test_spgemm_conformance.py holds every path below to it, tests/test_gpu_spgemm.py the hierarchy), which is what
+// keeps the hierarchy equal to the reference's printed sizes: every output
 // entry c_ij adds its products a_ik b_kj in the order the host adds them -- k in the order of row i of A -- because a
 // row is owned by one wave / workgroup that walks the entries of A's row one after the other and spreads only the
 // entries of B's row k, whose columns are distinct, over its lanes.  No floating-point atomics whose order could vary.
@@ -21,6 +22,7 @@
 // the diagonal, saena_object_setup_matmat.cpp:2423,2442) get the key INT_MAX; one segmented radix sort per chunk of rows
 // orders every segment by column, and the kept prefix of each segment is copied out.
 #include "../../include/saena_gpu.h"
+#include "host/amg_setup.h"
 #include "host/par.h"
 
 #include <hip/hip_runtime.h>
@@ -32,13 +34,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-
-namespace saena_host {
-typedef int (*spgemm_hook_fn)(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int *a_col, const double *a_val,
-                              const long *b_ptr, const int *b_col, const double *b_val, long b_split, const int *b_col1, const double *b_val1,
-                              int row_offset, std::vector<long> &c_ptr, std::vector<int> &c_col, std::vector<double> &c_val);
-extern spgemm_hook_fn g_spgemm_hook;
-}
 
 namespace {
 
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(256) void k_spgemm_light(Mats m, const int *__restr
             unsigned h = hash_col(j) & (LIGHT_SLOTS - 1);
             while (true) {
                 const int prev = atomicCAS(&K[h], -1, j);
-                if (prev == -1) { V[h] = v; break; }
+                if (prev == -1) { V[h] = 0.0 + v; break; }        // the host: acc = 0.0, then += a b (a first product of -0.0 leaves +0.0)
                 if (prev == j) { V[h] += v; break; }
                 h = (h + 1) & (LIGHT_SLOTS - 1);
             }
@@ -129,7 +124,7 @@ __global__ __launch_bounds__(256) void k_spgemm_medium(Mats m, const int *__rest
             int steps = 0;
             while (true) {
                 const int prev = atomicCAS(&K[h], -1, j);
-                if (prev == -1) { V[h] = v; if (TRY) atomicAdd(&counter[2], 1); break; }
+                if (prev == -1) { V[h] = 0.0 + v; if (TRY) atomicAdd(&counter[2], 1); break; }      // (0.0 + v: as in k_spgemm_light)
                 if (prev == j) { V[h] += v; break; }
                 h = (h + 1) & (MEDIUM_SLOTS - 1);
                 if (TRY && ++steps >= MEDIUM_SLOTS) { counter[3] = 1; break; }      // table full: give the row up
@@ -213,7 +208,8 @@ __global__ __launch_bounds__(256) void k_spgemm_heavy(Mats m, const int *__restr
 // by k_window_starts -- and adds a * b into the slots of its columns; the columns of one row of B are distinct, so no two
 // lanes meet, and a barrier separates ka from ka + 1: every output entry adds its products in the order of A's row, the
 // host's order, bit for bit.  A slot that nothing touched holds a sentinel (a NaN bit pattern no sum produces from finite
-// data) instead of a separate mark: the window is scanned once at the end, touched slots emitted (dropped entries get the
+// data; an INPUT NaN that carries this very payload would be taken for "untouched" -- not supported, not tested)
+// instead of a separate mark: the window is scanned once at the end, touched slots emitted (dropped entries get the
 // key INT_MAX like everywhere) and reset.  A (ka, window) pair without entries costs no barrier.
 constexpr int LDS_COLS = 20224;
 constexpr int LDS_MAXW = 16;
@@ -308,6 +304,22 @@ struct Dev {                                    // RAII for the call's device bu
 extern "C" int sgpu_context_device();      // sgpu_runtime.hip: the device of this process's context
 #define SP_CHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return 1; } } while (0)
 
+// PRECONDITION: the columns of every row of B are DISTINCT and ASCENDING (and below b_cols; the columns of A are rows of B).
+// Distinct, because the lanes of a wave / workgroup take the entries of one row of B side by side and add into the slots of
+// their columns without atomics on the sums; ascending, because k_window_starts bisects a row by column.  Rows of A may
+// repeat a column and come in any order: its entries are taken one after the other.  The callers (host/amg_setup.cpp):
+//   spgemm(Rc, Ac_), matmat     B = csr_of(an assembled saena_matrix): assemble() sorts by (row, column) and merges
+//                               duplicates (adds them or keeps the last), the layout's local entries are row-major with ascending columns;
+//   spgemm(RA, Pc)              B = the smoothed prolongator, every row ordered by stable_sort_by_first and its equal
+//                               columns added into one entry;
+//   spgemm_stacked(R, A, Ahalo), (RA, P, Phalo)   B = the rank's rows of A_l / P_l followed by whole rows fetched from their
+//                               owners (FetchPlan::rows copies a row as its owner holds it): A_0 is the assembled matrix, a
+//                               coarse A_l is a product of this function or of the host kernel (both emit rows ascending
+//                               by column, distinct) after filter_csr, which removes entries and puts a missing diagonal at its place
+//                               in column order; P_l as above.
+// Returns 0, or 1 to decline (out of device memory, a row beyond the scratch): the caller multiplies on the host.
+// SAENA_SPGEMM_CHUNK_ENTRIES=n (tests): chunks of at most n scratch entries instead of 384 Mi, so that a small product runs
+// as several chunks; read per call.
 int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int *a_col, const double *a_val,
                const long *b_ptr, const int *b_col, const double *b_val, long b_split, const int *b_col1, const double *b_val1,
                int row_offset, std::vector<long> &c_ptr, std::vector<int> &c_col, std::vector<double> &c_val) {
@@ -354,7 +366,8 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
     t_up = secs(T0, now());
 
     // chunks of consecutive rows whose scratch segments fit CH entries (2 x 12 B each: unsorted + sorted)
-    const long long CH = 384LL << 20;                                           // < 2^31: in-chunk offsets are ints
+    long long CH = 384LL << 20;                                                 // < 2^31: in-chunk offsets are ints
+    if (const char *e = std::getenv("SAENA_SPGEMM_CHUNK_ENTRIES")) CH = std::max(1LL, std::min(CH, std::atoll(e)));
     const int MAXROWS_CHUNK = 16 << 20;
     long long max_ub_sum = 0;
     int max_rows = 0;
@@ -395,6 +408,8 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
 
     c_ptr.assign(1, 0);
     c_col.clear(); c_val.clear();
+    long *stats = saena_host::g_spgemm_last.v;                                  // rows per path, from the lists below (amg_setup.h)
+    stats[saena_host::SPGEMM_CHUNKS] = (long)chunk_start.size() - 1;
     std::vector<int> h_ubptr, h_outptr;
     std::vector<int> h_kept, light, medium, heavy, h_rows;
     for (size_t c = 0; c + 1 < chunk_start.size(); ++c) {
@@ -407,6 +422,8 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
             if (ub[(size_t)i] == 0) continue;
             (ub[(size_t)i] <= LIGHT_UB ? light : ub[(size_t)i] <= MEDIUM_UB ? medium : heavy).push_back(i);
         }
+        stats[saena_host::SPGEMM_LIGHT] += (long)light.size();
+        stats[saena_host::SPGEMM_MEDIUM] += (long)medium.size();
         t_host += secs(Tc, now()); Tc = now();
         SP_CHK(hipMemcpy(d_ubptr, h_ubptr.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
         SP_CHK(hipMemset(d_touched, 0, (size_t)n * 4));
@@ -430,6 +447,8 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
             SP_CHK(hipMemcpy(h_kept.data(), d_touched, (size_t)n * 4, hipMemcpyDeviceToHost));
             std::vector<int> over;
             for (int i : heavy) if (h_kept[(size_t)(i - r0)] < 0) over.push_back(i);
+            stats[saena_host::SPGEMM_TRY_KEPT] += (long)(heavy.size() - over.size());
+            stats[saena_host::SPGEMM_TRY_ABANDONED] += (long)over.size();
             heavy.swap(over);
             if (!heavy.empty()) SP_CHK(hipMemcpy(d_rows + light.size() + medium.size(), heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice));
         }
@@ -443,6 +462,8 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
             hipLaunchKernelGGL(k_spgemm_lds, dim3((unsigned)std::min<size_t>((size_t)lds_grid, heavy.size())), dim3(LDS_BLOCK), 0, 0, m,
                                (const int *)(d_rows + light.size() + medium.size()), (int)heavy.size(), r0, (const int *)d_ubptr, tcol, tval,
                                d_touched, d_kept, row_offset, (const long long *)d_bw, n_windows, b_cols);
+            stats[saena_host::SPGEMM_LDS] += (long)heavy.size();
+            stats[saena_host::SPGEMM_WINDOWS] = n_windows;
             heavy.clear();
         }
         if (!heavy.empty()) {
@@ -458,6 +479,7 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
             hipLaunchKernelGGL(k_spgemm_heavy, dim3((unsigned)std::min<size_t>((size_t)heavy_grid, heavy.size())), dim3(256), 0, 0, m,
                                (const int *)(d_rows + light.size() + medium.size()), (int)heavy.size(), r0, (const int *)d_ubptr, tcol, tval,
                                d_touched, d_kept, row_offset, acc, mark, (long long)b_cols);
+            stats[saena_host::SPGEMM_HBM] += (long)heavy.size();
         }
         SP_CHK(hipGetLastError());
         if (timing) { SP_CHK(hipDeviceSynchronize()); t_kern += secs(Tc, now()); Tc = now(); }

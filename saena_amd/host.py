@@ -58,6 +58,11 @@ HOST_SYMBOLS = {
     "saena_laplacian3D_set_rhs": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _PD]),
     "saena_band_matrix": (C.c_int, [_VP, C.c_int, C.c_uint]),
     "saena_matmat": (C.c_int, [_VP, _VP, _VP]),
+    "saena_debug_spgemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.c_long, _VP, _VP, C.c_int,
+                                     C.POINTER(C.c_long)]),
+    "saena_debug_spgemm_result": (C.c_int, [_VP, _VP, _VP]),
+    "saena_debug_spgemm_stats": (C.c_int, [_VP, _VP]),
+    "saena_debug_spgemm_stats_reset": (None, []),
     "saena_prolong_new": (_VP, [_VP, C.c_int, C.c_int, _PI, _PI, _PI, _PI, _PD, C.c_long]),
     "saena_restrict_from_prolong": (_VP, [_VP]),
     "saena_transfer_free": (None, [_VP]),
@@ -373,6 +378,50 @@ class Transfer:
 
     def layout(self):
         return desc_arrays(self.desc())
+
+
+# the counters of saena_debug_spgemm_stats, in its order (include/saena_c.h)
+SPGEMM_STATS = ("host_dense", "host_hash", "host_rehash", "light", "medium", "try_kept", "try_abandoned", "lds", "hbm",
+                "chunks", "windows", "declined", "on_device")
+SPGEMM_MODES = {"auto": 0, "host": 1, "device": 2}
+
+
+def spgemm(L, a_ptr, a_col, a_val, b_ptr, b_col, b_val, b_cols, row_offset=0, mode="auto", split_row=None):
+    """C = A B through the products of the AMG setup (saena_debug_spgemm): -> (c_ptr, c_col, c_val).
+    A is (len(a_ptr) - 1) x (len(b_ptr) - 1), B has b_cols columns; the columns of every row of B must be distinct and
+    ascending.  mode: "host" = the host kernel, "device" = the GPU kernel whatever the size (SgpuError when it is missing
+    or declines), "auto" = what the setup does.  split_row: hand B over in two pieces, rows [0, split_row) and the rest,
+    as the distributed setup holds its own and its fetched rows."""
+    ap, ac, av = np.ascontiguousarray(a_ptr, np.int64), _ai(a_col), _ad(a_val)
+    bp, bc, bv = np.ascontiguousarray(b_ptr, np.int64), _ai(b_col), _ad(b_val)
+    if len(ac) != ap[-1] or len(av) != ap[-1] or len(bc) != bp[-1] or len(bv) != bp[-1]:
+        raise ValueError("spgemm: array lengths do not match the row pointers")
+    ptr = lambda a: a.ctypes.data_as(_VP)
+    if split_row is None:
+        pieces = (ptr(bc), ptr(bv), 0, None, None)
+    else:
+        cut = int(bp[split_row])
+        c0, v0, c1, v1 = bc[:cut].copy(), bv[:cut].copy(), bc[cut:].copy(), bv[cut:].copy()      # two allocations, as in the setup
+        pieces = (ptr(c0), ptr(v0), cut, ptr(c1), ptr(v1))
+    n = C.c_long()
+    _check(L, L.saena_debug_spgemm(SPGEMM_MODES[mode], len(ap) - 1, len(bp) - 1, int(b_cols), ptr(ap), ptr(ac), ptr(av), ptr(bp), *pieces,
+                                   int(row_offset), C.byref(n)))
+    c_ptr, c_col, c_val = np.zeros(len(ap), np.int64), np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
+    _check(L, L.saena_debug_spgemm_result(ptr(c_ptr), ptr(c_col), ptr(c_val)))
+    return c_ptr, c_col, c_val
+
+
+def spgemm_stats(L, total=False):
+    """which path served the rows of the last product (total: of every product since spgemm_stats_reset) -> dict"""
+    last, tot = np.zeros(len(SPGEMM_STATS), np.int64), np.zeros(len(SPGEMM_STATS), np.int64)
+    n = L.saena_debug_spgemm_stats(last.ctypes.data_as(_VP), tot.ctypes.data_as(_VP))
+    if n != len(SPGEMM_STATS):
+        raise SgpuError(f"saena_debug_spgemm_stats has {n} counters, the binding names {len(SPGEMM_STATS)}")
+    return dict(zip(SPGEMM_STATS, (int(x) for x in (tot if total else last))))
+
+
+def spgemm_stats_reset(L):
+    L.saena_debug_spgemm_stats_reset()
 
 
 def device_operator(obj, halo_fp32=False):
