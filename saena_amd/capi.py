@@ -400,7 +400,8 @@ class Operator:
 class Amg:
     """sgpu_amg over Operators A[l], P[l], R[l]."""
 
-    def __init__(self, A, P, R, eig_max=None, pre=3, post=3, smoother="jacobi", max_iter=100, tol=1e-8, use_graph=True, coarse_solver="direct"):
+    def __init__(self, A, P, R, eig_max=None, pre=3, post=3, smoother="jacobi", max_iter=100, tol=1e-8, use_graph=True, coarse_solver="direct",
+                 cg_max_iter=150, cg_tol=1e-12):
         self.A, self.P, self.R = list(A), list(P), list(R)
         n = len(A)
         prm = AmgParams()
@@ -410,6 +411,7 @@ class Amg:
         prm.solver_max_iter, prm.solver_tol = max_iter, tol
         prm.use_graph = 1 if use_graph else 0
         prm.coarse_solver = 1 if coarse_solver == "direct" else 0
+        prm.CG_coarsest_max_iter, prm.CG_coarsest_tol = int(cg_max_iter), float(cg_tol)
         HA = (_VP * n)(*[a.h for a in A])
         HP = (_VP * n)(*([p.h for p in P] + [None] * (n - len(P))))
         HR = (_VP * n)(*([r.h for r in R] + [None] * (n - len(R))))

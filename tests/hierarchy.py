@@ -54,6 +54,14 @@ def oracle_hierarchy(As, Ps, Rs, nprocs=1):
     return OA, OP, OR
 
 
+def single_level_oracle(A, cg_max_iter=150, cg_tol=1e-12, max_iter=100, tol=1e-8):
+    """-> (OracleAmg, OracleOp) of the one-level hierarchy ([A], [], []): its V-cycle is the coarsest solve alone"""
+    OA, _, _ = oracle_hierarchy([A], [], [])
+    O = orc.OracleAmg(OA, [], [], max_iter=max_iter, tol=tol)
+    O.p.contents.CG_coarsest_max_iter, O.p.contents.CG_coarsest_tol = cg_max_iter, cg_tol
+    return O, OA[0]
+
+
 def eig_estimates(As):
     """upper bounds of lambda_max(D^-1 A) (Gershgorin) -- an INPUT of Chebyshev, shared by both sides"""
     out = []
