@@ -243,6 +243,12 @@ public:
     int solve(value_t *&u, saena::options *opts);
     int solve_pCG(value_t *&u, saena::options *opts, bool print_info = true);
     int solve_CG(value_t *&u, saena::options *opts);          // CG without the multigrid preconditioner
+    // nrhs = 2, 4 or 8 right-hand sides through one pass over every operator (one rank): rhs_local and u are column-major,
+    // size x nrhs (column j at [j * size]), partitioned like A; u is allocated (size * nrhs) when null.  Every column is solved
+    // as solve_pCG solves it alone, with its own iteration count and history; returns 1 if any column did not converge
+    int set_rhs_block(const value_t *rhs_local, index_t size, int nrhs);
+    int solve_pCG_block(value_t *&u, saena::options *opts);
+    const std::vector<value_t> &residual_history_block(int j) const { return hist_blk_.at((size_t)j); }
     int solve_smoother(value_t *&u, saena::options *opts);    // the smoother alone (preSmooth sweeps per iteration)
     // C = A B (host SpGEMM, one rank in this round); C is erased first and assembled unless assemble == false
     void matmat(saena::matrix *A, saena::matrix *B, saena::matrix *C, bool assemble = true, bool print_timing = false);
@@ -286,6 +292,9 @@ private:
     std::vector<value_t> rhs_;
     std::vector<value_t> hist_;
     int iters_ = 0;
+    std::vector<value_t> rhs_blk_;                 // set_rhs_block: column-major size x nrhs_
+    int nrhs_ = 0;
+    std::vector<std::vector<value_t>> hist_blk_;   // per column of the last solve_pCG_block
     bool dynamic_levels_ = true;
     bool switch_to_dense_ = false;
     float dense_thre_override_ = 0;

@@ -242,6 +242,38 @@ int sgpu_solve_CG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value
 /* solve_coarsest_CG on the last level only (for tests) */
 int sgpu_coarsest_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters);
 
+/* ---- block vectors: K right-hand sides through one pass over the operator --
+ * A block vector of K columns over n rows is ONE device allocation of n*K doubles (sgpu_vec_alloc) with the columns
+ * interleaved, X[i*K + j]; K is 2, 4 or 8, anything else is SGPU_ERR_ARG on every entry point below.  Outside the
+ * library blocks travel column-major (n x K, column j at cols[j*n]); pack / unpack convert, device to device.
+ * One rank and fp64 only: a context with nranks > 1, or an operator with a remote part, gets SGPU_ERR_ARG.
+ * Every column of a block result is what the scalar entry point computes for that column alone: bit for bit the
+ * reference's sequential row sum at one lane per row, within the tile kernels' bounds above that; column j never
+ * reads column j'.  None of this touches the scalar path (no plan, autotune choice, plan-cache entry or scalar graph):
+ * the block kernel reads the plain CSR arrays every operator keeps. */
+int sgpu_block_pack(const value_t *cols_colmajor, value_t *blk, size_t n, int K);
+int sgpu_block_unpack(const value_t *blk, value_t *cols_colmajor, size_t n, int K);
+/* lanes per row of the block kernel: 0 = from the operator's mean row length (the default), or 1, 4, 16, 64.
+ * (sgpu_op_set_lanes_per_row steers the scalar forms and does not reach the block kernel, nor this the scalar forms.) */
+int sgpu_op_set_block_lanes(sgpu_op *op, int lanes);
+int sgpu_op_get_block_lanes(const sgpu_op *op, int *lanes);
+int sgpu_spmv_block(sgpu_op *op, const value_t *X, value_t *Y, int K);
+int sgpu_residual_block(sgpu_op *op, const value_t *U, const value_t *RHS, value_t *RES, int K);
+int sgpu_jacobi_block(sgpu_op *op, int iter, value_t omega, value_t *U, const value_t *RHS, int K);
+int sgpu_chebyshev_block(sgpu_op *op, int iter, value_t eig_max, value_t *U, const value_t *RHS, int K);
+int sgpu_prolong_correct_block(sgpu_op *P, const value_t *E_coarse, value_t *U, int K);
+/* sgpu_vcycle on K columns: the same steps on block vectors (work vectors made at the first call with this K, freed with
+ * the hierarchy; with use_graph captured once per (U, RHS, K)).  A hierarchy whose coarsest level needs the host-driven CG
+ * (more rows than the LDS-resident solvers hold) is refused with SGPU_ERR_ARG. */
+int sgpu_vcycle_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K);
+/* sgpu_solve_pCG's recurrence on K columns in lockstep, every column with its own scalars and threshold.  A column stops
+ * at the iteration at which its ||r||^2 drops below its own threshold and is not written again; iters[j] and
+ * res_hist[j*hist_cap + k] are those of a scalar solve of column j.  A column whose right-hand side is exactly zero
+ * returns u = 0, iters[j] = 0, res_hist[j*hist_cap] = 0.  SGPU_ERR_NOCONV if any column is still above its threshold after
+ * solver_max_iter iterations (all iterates stay valid).  One host synchronisation per iteration. */
+int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K,
+                         int *iters /*[K]*/, value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
+
 /* ---- measurement -----------------------------------------------------------
  * Runs `reps` back-to-back launches of one kernel on the compute stream,
  * bracketed by hipEvents recorded on that same stream; *ms_per_launch is the

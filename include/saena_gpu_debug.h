@@ -72,6 +72,12 @@ int sgpu_debug_launch_count(long *launches);
  * characters and a terminator. */
 int sgpu_debug_device_info(char *buf, int len);
 
+/* measurement scripts (tests/perf_block.py): sgpu_time_kernel for the block kernel -- `reps` back-to-back launches inside the
+ * library between two events of their own; kind 0: Y = A X, 1: one Jacobi sweep X -> Y -- and the same for whole V-cycles,
+ * K = 0: the scalar sgpu_vcycle on (U, RHS), K = 2, 4, 8: sgpu_vcycle_block (one call before the interval captures the graph). */
+int sgpu_debug_time_block(sgpu_op *op, int kind, const value_t *X, const value_t *RHS, value_t *Y, int K, int reps, float *ms_per_launch);
+int sgpu_debug_time_vcycle(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int reps, float *ms_per_cycle);
+
 #ifdef __cplusplus
 }
 #endif

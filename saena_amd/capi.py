@@ -101,6 +101,19 @@ SYMBOLS = {
     "sgpu_debug_device_info": (C.c_int, [C.c_char_p, C.c_int]),
     "sgpu_debug_allow_local_only": (C.c_int, [_VP, C.c_int]),
     "sgpu_debug_init_host_transport": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP, _VP, _VP]),
+    "sgpu_block_pack": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int]),
+    "sgpu_block_unpack": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int]),
+    "sgpu_op_set_block_lanes": (C.c_int, [_VP, C.c_int]),
+    "sgpu_op_get_block_lanes": (C.c_int, [_VP, _PI]),
+    "sgpu_spmv_block": (C.c_int, [_VP, _VP, _VP, C.c_int]),
+    "sgpu_residual_block": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int]),
+    "sgpu_jacobi_block": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, C.c_int]),
+    "sgpu_chebyshev_block": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP, C.c_int]),
+    "sgpu_prolong_correct_block": (C.c_int, [_VP, _VP, _VP, C.c_int]),
+    "sgpu_vcycle_block": (C.c_int, [_VP, _VP, _VP, C.c_int]),
+    "sgpu_solve_pCG_block": (C.c_int, [_VP, _VP, _VP, C.c_int, _PI, _PD, C.c_int]),
+    "sgpu_debug_time_block": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "sgpu_debug_time_vcycle": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_time_kernel": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_algorithmic_bytes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
 }
@@ -255,6 +268,47 @@ class DeviceVector:
             pass
 
 
+class BlockVector:
+    """K columns over n rows in HBM, interleaved (X[i*K + j]); host arrays are (n, K), column j = host[:, j].  The library
+    converts between its layout and the column-major one callers use (sgpu_block_pack / sgpu_block_unpack)."""
+
+    def __init__(self, n, K, host=None):
+        self.n, self.K = int(n), int(K)
+        p = _VP()
+        check(lib().sgpu_vec_alloc(C.byref(p), self.n * self.K))
+        self.ptr = p
+        if host is not None:
+            self.upload(host)
+
+    def upload(self, host):
+        host = np.asarray(host, np.float64)
+        assert host.shape == (self.n, self.K), host.shape
+        cm = DeviceVector(self.n * self.K, np.asfortranarray(host).ravel(order="F"))     # column-major n x K
+        check(lib().sgpu_block_pack(cm.ptr, self.ptr, self.n, self.K))
+        check(lib().sgpu_device_sync())
+        cm.free()
+        return self
+
+    def download(self):
+        cm = DeviceVector(self.n * self.K)
+        check(lib().sgpu_block_unpack(self.ptr, cm.ptr, self.n, self.K))
+        out = cm.download().reshape((self.n, self.K), order="F")
+        cm.free()
+        return out
+
+    def free(self):
+        if self.ptr:
+            lib().sgpu_vec_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            if _initialised:
+                self.free()
+        except Exception:
+            pass
+
+
 def _ai(a):
     return np.ascontiguousarray(a, np.int32)
 
@@ -350,6 +404,36 @@ class Operator:
 
     def prolong_correct(self, e_coarse, u):
         check(lib().sgpu_prolong_correct(self.h, e_coarse.ptr, u.ptr))
+
+    # block vectors (BlockVector): K right-hand sides through one pass over the operator
+    def set_block_lanes(self, lanes):
+        check(lib().sgpu_op_set_block_lanes(self.h, int(lanes)))
+
+    def block_lanes(self):
+        v = C.c_int()
+        check(lib().sgpu_op_get_block_lanes(self.h, C.byref(v)))
+        return v.value
+
+    def spmv_block(self, X, Y):
+        check(lib().sgpu_spmv_block(self.h, X.ptr, Y.ptr, X.K))
+
+    def residual_block(self, U, RHS, RES):
+        check(lib().sgpu_residual_block(self.h, U.ptr, RHS.ptr, RES.ptr, U.K))
+
+    def jacobi_block(self, it, U, RHS, omega=0.0):
+        check(lib().sgpu_jacobi_block(self.h, int(it), float(omega), U.ptr, RHS.ptr, U.K))
+
+    def chebyshev_block(self, it, eig_max, U, RHS):
+        check(lib().sgpu_chebyshev_block(self.h, int(it), float(eig_max), U.ptr, RHS.ptr, U.K))
+
+    def prolong_correct_block(self, E_coarse, U):
+        check(lib().sgpu_prolong_correct_block(self.h, E_coarse.ptr, U.ptr, U.K))
+
+    def time_block(self, kind, X, RHS, Y, reps):
+        """ms per launch of the block kernel, timed inside the library like time_kernel (kind 0: product, 1: Jacobi sweep X -> Y)"""
+        ms = C.c_float()
+        check(lib().sgpu_debug_time_block(self.h, kind, X.ptr, RHS.ptr if RHS is not None else None, Y.ptr, X.K, reps, C.byref(ms)))
+        return ms.value
 
     def debug_gather_probe(self, mode, x, reps=20):
         ms = C.c_float()
@@ -449,6 +533,25 @@ class Amg:
 
     def solve_smoother(self, u, rhs):
         return self._solve(lib().sgpu_solve_smoother, u, rhs, cap=2048)
+
+    def vcycle_block(self, U, RHS):
+        check(lib().sgpu_vcycle_block(self.h, U.ptr, RHS.ptr, U.K))
+
+    def time_vcycle(self, u, rhs, reps):
+        """ms per V-cycle, `reps` of them back to back inside the library; u / rhs: DeviceVectors (scalar) or BlockVectors"""
+        ms = C.c_float()
+        check(lib().sgpu_debug_time_vcycle(self.h, u.ptr, rhs.ptr, getattr(u, "K", 0), reps, C.byref(ms)))
+        return ms.value
+
+    def solve_pCG_block(self, U, RHS, cap=256):
+        """-> (iters[K], [history of column j], converged): sgpu_solve_pCG_block"""
+        K = U.K
+        it = (C.c_int * K)()
+        hist = np.full((K, cap), np.nan)
+        st = lib().sgpu_solve_pCG_block(self.h, U.ptr, RHS.ptr, K, it, hist.ctypes.data_as(_PD), cap)
+        if st not in (0, -6):
+            check(st)
+        return [int(v) for v in it], [h[~np.isnan(h)] for h in hist], st == 0
 
     def set_solve_params(self, max_iter, tol, smoother, pre, post):
         check(lib().sgpu_amg_set_solve_params(self.h, int(max_iter), float(tol), 0 if smoother == "jacobi" else 1, int(pre), int(post)))

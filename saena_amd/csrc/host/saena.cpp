@@ -362,6 +362,43 @@ int amg::run(value_t *&u, saena::options *opts, int which, bool print_info) {
 int amg::solve(value_t *&u, saena::options *opts) { return run(u, opts, 0, true); }
 int amg::solve_pCG(value_t *&u, saena::options *opts, bool print_info) { return run(u, opts, 1, print_info); }
 int amg::solve_CG(value_t *&u, saena::options *opts) { return run(u, opts, 2, true); }
+
+int amg::set_rhs_block(const value_t *rhs_local, index_t size, int nrhs) {
+    if (!A_ || size != A_->get_num_local_rows()) throw std::runtime_error("saena::amg::set_rhs_block: size does not match the local rows");
+    if (nrhs != 2 && nrhs != 4 && nrhs != 8) throw std::runtime_error("saena::amg::set_rhs_block: a block holds 2, 4 or 8 right-hand sides");
+    rhs_blk_.assign(rhs_local, rhs_local + (size_t)size * nrhs);
+    nrhs_ = nrhs;
+    return 0;
+}
+int amg::solve_pCG_block(value_t *&u, saena::options *opts) {
+    if (!damg_) throw std::runtime_error("saena::amg: set_matrix first");
+    const size_t n = (size_t)A_->get_num_local_rows(), K = (size_t)nrhs_;
+    if (!nrhs_ || rhs_blk_.size() != n * K) throw std::runtime_error("saena::amg: set_rhs_block first");
+    if (opts)
+        gchk(sgpu_amg_set_solve_params(damg_, opts->get_max_iter(), opts->get_tol(), opts->get_smoother() == "jacobi" ? 0 : 1,
+                                       opts->get_preSmooth(), opts->get_postSmooth()), "set_solve_params");
+    value_t *cm = nullptr, *du = nullptr, *dr = nullptr;
+    auto release = [&] { sgpu_vec_free(cm); sgpu_vec_free(du); sgpu_vec_free(dr); };
+    int sa = sgpu_vec_alloc(&cm, n * K);
+    if (sa == SGPU_OK) sa = sgpu_vec_alloc(&du, n * K);
+    if (sa == SGPU_OK) sa = sgpu_vec_alloc(&dr, n * K);
+    if (sa != SGPU_OK) { release(); gchk(sa, "alloc"); }
+    const int cap = 4096;
+    std::vector<value_t> hist(K * (size_t)cap, 0.0);
+    std::vector<int> iters(K, 0);
+    int st = sgpu_vec_upload(cm, rhs_blk_.data(), n * K);
+    if (st == SGPU_OK) st = sgpu_block_pack(cm, dr, n, nrhs_);
+    if (st == SGPU_OK) st = sgpu_solve_pCG_block(damg_, du, dr, nrhs_, iters.data(), hist.data(), cap);
+    if (st != SGPU_OK && st != SGPU_ERR_NOCONV) { release(); gchk(st, "solve_pCG_block"); }
+    hist_blk_.assign(K, {});
+    for (size_t j = 0; j < K; ++j) hist_blk_[j].assign(hist.begin() + (long)(j * cap), hist.begin() + (long)(j * cap) + std::min(iters[j] + 1, cap));
+    if (!u) u = static_cast<value_t *>(std::malloc(std::max<size_t>(1, n * K) * sizeof(value_t)));
+    int st2 = sgpu_block_unpack(du, cm, n, nrhs_);
+    if (st2 == SGPU_OK) st2 = sgpu_vec_download(u, cm, n * K);
+    release();
+    gchk(st2, "download");
+    return st == SGPU_OK ? 0 : 1;
+}
 int amg::set_scale(bool sc) {
     if (sc) throw std::runtime_error("saena::amg::set_scale(true): symmetric scaling is not on the GPU path (false in the reference's drivers)");
     return 0;

@@ -321,6 +321,7 @@ sgpu_amg *saena_amg_device_handle(saena_amg_h *) { no_gpu(); return nullptr; }
 sgpu_op *saena_amg_device_op(saena_amg_h *, int, int) { no_gpu(); return nullptr; }
 int saena_amg_solve(saena_amg_h *, const value_t *, value_t *, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_solve_pCG(saena_amg_h *, const value_t *, value_t *, int *, value_t *, int) { return no_gpu(); }
+int saena_amg_solve_pCG_block(saena_amg_h *, const value_t *, value_t *, int, int *, value_t *, int) { return no_gpu(); }
 #else
 static int gchk(int s) { if (s != 0) { h_err = sgpu_last_error(); } return s; }
 static void drop_device(saena_amg_h *S) {
@@ -387,6 +388,28 @@ static int solve_host(saena_amg_h *S, bool pcg, const value_t *rhs_host, value_t
 }
 int saena_amg_solve(saena_amg_h *S, const value_t *rhs, value_t *u, int *it, value_t *hist, int cap) { return solve_host(S, false, rhs, u, it, hist, cap); }
 int saena_amg_solve_pCG(saena_amg_h *S, const value_t *rhs, value_t *u, int *it, value_t *hist, int cap) { return solve_host(S, true, rhs, u, it, hist, cap); }
+
+// K right-hand sides: the column-major host arrays go up as they are and are packed into / unpacked from block vectors on the device
+int saena_amg_solve_pCG_block(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int K, int *iters, value_t *hist, int cap) {
+    if (!S->damg) { h_err = "saena_amg_to_device has not been called"; return -1; }
+    if (K != 2 && K != 4 && K != 8) { h_err = "saena_amg_solve_pCG_block: a block holds 2, 4 or 8 columns"; return -1; }
+    const size_t n = S->H.dist.empty() ? (size_t)S->H.levels[0].A->M : (size_t)S->H.dist[0].A.M;
+    value_t *cm = nullptr, *u = nullptr, *rhs = nullptr;
+    if (gchk(sgpu_vec_alloc(&cm, n * K)) || gchk(sgpu_vec_alloc(&u, n * K)) || gchk(sgpu_vec_alloc(&rhs, n * K))) {
+        sgpu_vec_free(cm); sgpu_vec_free(u); sgpu_vec_free(rhs);
+        return -2;
+    }
+    int s = gchk(sgpu_vec_upload(cm, rhs_host, n * K));
+    if (!s) s = gchk(sgpu_block_pack(cm, rhs, n, K));
+    if (!s) s = gchk(sgpu_solve_pCG_block(S->damg, u, rhs, K, iters, hist, cap));
+    int s2 = 0;
+    if (s == 0 || s == SGPU_ERR_NOCONV) {
+        s2 = gchk(sgpu_block_unpack(u, cm, n, K));
+        if (!s2) s2 = gchk(sgpu_vec_download(u_host, cm, n * K));
+    }
+    sgpu_vec_free(cm); sgpu_vec_free(u); sgpu_vec_free(rhs);
+    return s ? s : s2;
+}
 #endif
 
 } // extern "C"

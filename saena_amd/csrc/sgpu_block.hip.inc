@@ -1,0 +1,468 @@
+// sgpu_block.hip.inc -- block entry points of include/saena_gpu.h (sgpu_*_block): K right-hand sides through one pass over
+// every operator.  Part of sgpu_runtime.hip (it shares that file's context, handles and helpers); kernels: kernels_block.hip.h.
+//
+// Nothing here touches the scalar path: no plan, no autotune choice, no plan-cache entry, no scalar graph.  The block kernel
+// reads the plain CSR arrays every operator keeps for its whole life (CsrPart::row_ptr / col / val and the 16 KiB row-block
+// plan blk_row); its own state is two lane counts and two lazily made buffers per K and operator, and an AmgBlock per (hierarchy, K).
+namespace {
+
+uint64_t g_block_generation = 0;   // bumped by sgpu_op_set_block_lanes: captured BLOCK V-cycles are stale (the scalar ones are not)
+
+int block_check(const sgpu_op *op, int K, const char *what) {
+    if (K != 2 && K != 4 && K != 8) return fail(SGPU_ERR_ARG, "%s: a block holds 2, 4 or 8 columns (K = %d)", what, K);
+    if (g.nranks > 1 || g.multi()) return fail(SGPU_ERR_ARG, "%s: block entry points run on one rank only (this context has %d)", what, g.nranks);
+    if (op && (op->has_remote || op->recvSize))
+        return fail(SGPU_ERR_ARG, "%s: the operator has a remote part (%d halo entries); block entry points take single-rank operators only", what, op->recvSize);
+    return SGPU_OK;
+}
+
+// lanes per row from the mean row length: a row block holds up to CAP = 2048 entries for 256 lanes, 8 entries per lane
+int block_auto_lanes(const sgpu_op *op) {
+    const double mean = op->M > 0 ? (double)op->loc.nnz / (double)op->M : 0.0;
+    for (int G : {1, 4, 16})
+        if ((double)G * 8.0 >= mean) return G;
+    return 64;
+}
+
+using BlockFn = void (*)(const sk::BlockArgs);
+template <int K, int EPI>
+BlockFn block_pick_g(int G) {
+    switch (G) {
+        case 1:  return sk::k_csr_block<K, EPI, 1>;
+        case 4:  return sk::k_csr_block<K, EPI, 4>;
+        case 16: return sk::k_csr_block<K, EPI, 16>;
+        default: return sk::k_csr_block<K, EPI, 64>;
+    }
+}
+template <int K>
+BlockFn block_pick_epi(int epi, int G) {
+    switch (epi) {
+        case sk::EPI_SPMV:     return block_pick_g<K, sk::EPI_SPMV>(G);
+        case sk::EPI_RESIDUAL: return block_pick_g<K, sk::EPI_RESIDUAL>(G);
+        case sk::EPI_JACOBI:   return block_pick_g<K, sk::EPI_JACOBI>(G);
+        case sk::EPI_CHEBY0:   return block_pick_g<K, sk::EPI_CHEBY0>(G);
+        case sk::EPI_CHEBYK:   return block_pick_g<K, sk::EPI_CHEBYK>(G);
+        case sk::EPI_SUB:      return block_pick_g<K, sk::EPI_SUB>(G);
+        default:               return nullptr;
+    }
+}
+
+// Y = epilogue(A X): one launch of k_csr_block over the operator's 16 KiB row-block plan
+int apply_block(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, int K) {
+    if (op->M == 0 || op->loc.nblk == 0) return SGPU_OK;
+    if (!op->block_lanes_auto) op->block_lanes_auto = block_auto_lanes(op);
+    const int G = op->block_lanes ? op->block_lanes : op->block_lanes_auto;
+    const BlockFn fn = K == 2 ? block_pick_epi<2>(epi, G) : K == 4 ? block_pick_epi<4>(epi, G) : block_pick_epi<8>(epi, G);
+    if (!fn) return fail(SGPU_ERR_ARG, "block apply: no kernel for epilogue %d", epi);   // a missing kernel is an error, never a fall-back
+    sk::BlockArgs a;
+    a.row_ptr = op->loc.row_ptr; a.col = op->loc.col; a.val = op->loc.val; a.blk_row = op->loc.blk_row; a.nblk = op->loc.nblk;
+    a.x = x; a.y = y; a.rhs = e.rhs; a.inv_diag = e.inv_diag; a.u = e.u; a.d = e.d; a.c0 = e.c0; a.c1 = e.c1;
+    SGPU_LAUNCH(fn, dim3(op->loc.nblk), dim3(sk::BLOCK), 0, g.cs, a);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+int block_slot(int K) { return K == 2 ? 0 : K == 4 ? 1 : 2; }
+
+// the operator's block ping-pong buffer (the op-level smoother calls; a block V-cycle ping-pongs in its own work vectors) and its
+// Chebyshev direction for K columns: made when first needed, each on its own
+int ensure_blk_buf(double **p, const sgpu_op *op, int K) {
+    if (*p) return SGPU_OK;
+    if (hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, (size_t)op->M * K) * sizeof(double)) != hipSuccess) {
+        *p = nullptr;
+        return fail(SGPU_ERR_NOMEM, "hipMalloc of a block work vector (%d rows x %d columns) failed", op->M, K);
+    }
+    return SGPU_OK;
+}
+int ensure_blk_tmp(sgpu_op *op, int K) { return ensure_blk_buf(&op->tmp_blk[block_slot(K)], op, K); }
+int ensure_blk_d(sgpu_op *op, int K) { return ensure_blk_buf(&op->dvec_blk[block_slot(K)], op, K); }
+
+// jacobi_pp / cheby_pp on block vectors (no zero-iterate shortcut: a sweep from a zero-filled block gives the same numbers)
+int jacobi_block_pp(sgpu_op *op, int iter, double omega, double *u, double *alt, const double *rhs, double **out, int K) {
+    if (!op->inv_diag && op->M > 0) return fail(SGPU_ERR_ARG, "jacobi: operator has no inv_diag");
+    double *cur = u, *nxt = alt;
+    for (int j = 0; j < iter; ++j) {
+        EpiArgs e; e.rhs = rhs; e.inv_diag = op->inv_diag; e.u = cur; e.c0 = omega;
+        CHK(apply_block(op, sk::EPI_JACOBI, cur, nxt, e, K));
+        std::swap(cur, nxt);
+    }
+    *out = cur;
+    return SGPU_OK;
+}
+int cheby_block_pp(sgpu_op *op, int iter, double eig_max, double *u, double *alt, const double *rhs, double **out, int K) {
+    if (!op->inv_diag && op->M > 0) return fail(SGPU_ERR_ARG, "chebyshev: operator has no inv_diag");
+    const double alpha = 0.13 * eig_max, beta = eig_max;                          // cheby_pp's scalars
+    const double delta = (beta - alpha) / 2.0, theta = (beta + alpha) / 2.0;
+    const double s1 = theta / delta, twos1 = 2.0 * s1;
+    double rhok = 1.0 / s1;
+    double *cur = u, *nxt = alt;
+    for (int i = 0; i < iter; ++i) {
+        EpiArgs e; e.rhs = rhs; e.inv_diag = op->inv_diag; e.u = cur; e.d = op->dvec_blk[block_slot(K)];
+        if (i == 0) { e.c0 = 1.0 / theta; CHK(apply_block(op, sk::EPI_CHEBY0, cur, nxt, e, K)); }
+        else {
+            const double rhokp1 = 1.0 / (twos1 - rhok);
+            const double two_rhokp1 = 2.0 * rhokp1;
+            e.c1 = rhokp1 * rhok; e.c0 = two_rhokp1 / delta;
+            rhok = rhokp1;
+            CHK(apply_block(op, sk::EPI_CHEBYK, cur, nxt, e, K));
+        }
+        std::swap(cur, nxt);
+    }
+    *out = cur;
+    return SGPU_OK;
+}
+
+int block_pack(const double *cols, double *blk, size_t n, int K) {
+    if (!n) return SGPU_OK;
+    SGPU_LAUNCH(sk::k_block_pack, dim3(grid_for(2 * n)), dim3(sk::BLOCK), 0, g.cs, cols, blk, n, K);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+int block_unpack(const double *blk, double *cols, size_t n, int K) {
+    if (!n) return SGPU_OK;
+    SGPU_LAUNCH(sk::k_block_unpack, dim3(grid_for(2 * n)), dim3(sk::BLOCK), 0, g.cs, blk, cols, n, K);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+// ---- per-(hierarchy, K) state ----
+int amg_block(sgpu_amg *h, int K, AmgBlock **out) {
+    const int slot = block_slot(K);
+    if (!h->blk[slot]) {
+        std::unique_ptr<AmgBlock> B(new AmgBlock());
+        B->K = K;
+        const int L = h->nlevels;
+        B->res.assign(L, nullptr); B->rhs.assign(L, nullptr); B->u.assign(L, nullptr); B->alt.assign(L, nullptr);
+        auto alloc = [](double **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, n) * sizeof(double)); };
+        for (int l = 0; l < L; ++l) {
+            const size_t n = (size_t)h->A[l]->M * K;
+            if (l < L - 1) HIPCHK(alloc(&B->res[l], n));
+            if (l >= 1) { HIPCHK(alloc(&B->rhs[l], n)); HIPCHK(alloc(&B->u[l], n)); HIPCHK(alloc(&B->alt[l], n)); }
+            CHK(ensure_blk_d(h->A[l], K));                     // (Chebyshev direction) no allocation may happen inside a graph capture
+        }
+        const size_t n0 = (size_t)h->A[0]->M * K;
+        HIPCHK(alloc(&B->alt0, n0)); HIPCHK(alloc(&B->r, n0)); HIPCHK(alloc(&B->rho, n0)); HIPCHK(alloc(&B->hh, n0)); HIPCHK(alloc(&B->p, n0));
+        HIPCHK(alloc(&B->cm, 2 * (size_t)h->A[L - 1]->M * K));
+        HIPCHK(alloc(&B->S, 8 * (size_t)K));
+        HIPCHK(alloc(&B->partials, (size_t)g.n_partials * K));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&B->hS), K * sizeof(double), hipHostMallocDefault));
+        h->blk[slot] = std::move(B);
+    }
+    AmgBlock *B = h->blk[slot].get();
+    *out = B;
+    return SGPU_OK;
+}
+
+int amg_block_check(sgpu_amg *h, int K, const char *what) {
+    CHK(block_check(nullptr, K, what));
+    if (h->coarse_host_driven) return fail(SGPU_ERR_ARG, "%s: the coarsest level has %d rows and needs the host-driven CG; block solves take hierarchies whose coarsest level fits the LDS-resident solvers (<= %d rows)", what, h->A[h->nlevels - 1]->M, sk::CG_MAXN);
+    for (int l = 0; l < h->nlevels; ++l) {
+        CHK(block_check(h->A[l], K, what));
+        if (l < h->nlevels - 1) { CHK(block_check(h->P[l], K, what)); CHK(block_check(h->R[l], K, what)); }
+    }
+    return SGPU_OK;
+}
+
+int coarse_solve_block(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, bool u_zero) {
+    sgpu_op *A = h->A[h->nlevels - 1];
+    const int n = A->M, K = B.K;
+    if (n == 0) return SGPU_OK;
+    if (h->Ainv) {
+        const int C = std::min(K, pow2floor(std::max(1, sk::DS_CAP / n)));
+        auto fn = C >= 8 ? sk::k_dense_solve_block<8> : C == 4 ? sk::k_dense_solve_block<4> : C == 2 ? sk::k_dense_solve_block<2> : sk::k_dense_solve_block<1>;
+        SGPU_LAUNCH(fn, dim3(1), dim3(sk::CG_BLOCK), 0, g.cs, (const double *)h->Ainv, rhs, u, n, K);
+        HIPCHK(hipGetLastError());
+        return SGPU_OK;
+    }
+    // LDS-resident CG: the existing one-workgroup solver, column by column (<= 1024 rows: not a hot path)
+    double *crhs = B.cm, *cu = B.cm + (size_t)n * K;
+    CHK(block_unpack(rhs, crhs, (size_t)n, K));
+    if (u_zero) CHK(sgpu_vec_fill(cu, 0.0, (size_t)n * K)); else CHK(block_unpack(u, cu, (size_t)n, K));
+    for (int j = 0; j < K; ++j) CHK(coarse_cg_single(h, A, cu + (size_t)j * n, crhs + (size_t)j * n, nullptr));
+    return block_pack(cu, u, (size_t)n, K);
+}
+
+int smooth_block_pp(sgpu_amg *h, int l, int iter, double *u, double *alt, const double *rhs, double **out, int K) {
+    if (h->prm.smoother == 0) {
+        const double om = h->prm.jacobi_omega != 0.0 ? h->prm.jacobi_omega : JACOBI_OMEGA_REF;
+        return jacobi_block_pp(h->A[l], iter, om, u, alt, rhs, out, K);
+    }
+    return cheby_block_pp(h->A[l], iter, h->eig[l], u, alt, rhs, out, K);
+}
+
+// vcycle_level on block vectors, step for step (without its two launch-saving shortcuts, whose results are the plain sweep's)
+int vcycle_block_level(sgpu_amg *h, AmgBlock &B, int l, double *u, double *alt, const double *rhs, double **out, bool u_zero) {
+    const int K = B.K;
+    const size_t n = (size_t)h->A[l]->M * K;
+    if (l == h->nlevels - 1) {
+        CHK(coarse_solve_block(h, B, u, rhs, u_zero));
+        *out = u;
+        return SGPU_OK;
+    }
+    double *cur = u, *oth = alt, *t = nullptr;
+    if (u_zero) CHK(sgpu_vec_fill(cur, 0.0, n));
+    if (h->prm.preSmooth) {
+        CHK(smooth_block_pp(h, l, h->prm.preSmooth, cur, oth, rhs, &t, K));
+        if (t != cur) std::swap(cur, oth);
+    }
+    { EpiArgs e; e.rhs = rhs; CHK(apply_block(h->A[l], sk::EPI_RESIDUAL, cur, B.res[l], e, K)); }
+    CHK(apply_block(h->R[l], sk::EPI_SPMV, B.res[l], B.rhs[l + 1], EpiArgs(), K));
+    double *uc = nullptr;
+    CHK(vcycle_block_level(h, B, l + 1, B.u[l + 1], B.alt[l + 1], B.rhs[l + 1], &uc, true));
+    CHK(apply_block(h->P[l], sk::EPI_SUB, uc, cur, EpiArgs(), K));
+    if (h->prm.postSmooth) {
+        CHK(smooth_block_pp(h, l, h->prm.postSmooth, cur, oth, rhs, &t, K));
+        if (t != cur) std::swap(cur, oth);
+    }
+    *out = cur;
+    return SGPU_OK;
+}
+
+int vcycle_block_eager(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, bool u_zero) {
+    double *out = nullptr;
+    CHK(vcycle_block_level(h, B, 0, u, B.alt0, rhs, &out, u_zero));
+    if (out != u) HIPCHK(hipMemcpyAsync(u, out, (size_t)h->A[0]->M * B.K * sizeof(double), hipMemcpyDeviceToDevice, g.cs));
+    return SGPU_OK;
+}
+
+// vcycle0 for blocks: captured once per (u, rhs, K) and replayed
+int vcycle_block0(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, bool u_zero = false) {
+    if (!h->prm.use_graph) return vcycle_block_eager(h, B, u, rhs, u_zero);
+    if (!B.graphs.empty() && (B.graph_gen != g_plan_generation || B.block_gen != g_block_generation)) {
+        HIPCHK(hipStreamSynchronize(g.cs));
+        B.drop_graphs();
+    }
+    B.graph_gen = g_plan_generation; B.block_gen = g_block_generation;
+    for (auto &c : B.graphs)
+        if (c.u == u && c.rhs == rhs && c.u_zero == u_zero) { ++g_launches; HIPCHK(hipGraphLaunch(c.exec, g.cs)); return SGPU_OK; }
+    AmgBlock::Captured c{u, rhs, u_zero, nullptr, nullptr};
+    HIPCHK(hipStreamBeginCapture(g.cs, hipStreamCaptureModeThreadLocal));
+    const int st = vcycle_block_eager(h, B, u, rhs, u_zero);
+    const hipError_t e = hipStreamEndCapture(g.cs, &c.graph);
+    if (st != SGPU_OK) { if (c.graph) hipGraphDestroy(c.graph); return st; }
+    if (e != hipSuccess) return fail(SGPU_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    HIPCHK(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
+    if (B.graphs.size() >= 8) {
+        hipGraphExecDestroy(B.graphs.front().exec); hipGraphDestroy(B.graphs.front().graph);
+        B.graphs.erase(B.graphs.begin());
+    }
+    B.graphs.push_back(c);
+    ++g_launches; HIPCHK(hipGraphLaunch(c.exec, g.cs));
+    return SGPU_OK;
+}
+
+// out[j] = x_j . y_j on the columns of `active` (the others keep what they hold)
+int dot_block(AmgBlock &B, const double *x, const double *y, size_t n, double *out, unsigned active) {
+    const int nb = dot_nblocks(n), K = B.K;
+    if (K == 2) SGPU_LAUNCH(sk::k_dot_block_partial<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
+    else if (K == 4) SGPU_LAUNCH(sk::k_dot_block_partial<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
+    else SGPU_LAUNCH(sk::k_dot_block_partial<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
+    SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)B.partials, nb, K, out, active);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- measurement (tests/perf_block.py): sgpu_time_kernel's loop for the block kernel and for whole V-cycles, scalar or block:
+// `reps` back-to-back enqueues inside the library between two events of their own ----
+static hipEvent_t g_bt0 = nullptr, g_bt1 = nullptr;
+static int block_timer_events() {
+    if (!g_bt0) { HIPCHK(hipEventCreate(&g_bt0)); HIPCHK(hipEventCreate(&g_bt1)); }
+    return SGPU_OK;
+}
+int sgpu_debug_time_block(sgpu_op *op, int kind, const value_t *X, const value_t *RHS, value_t *Y, int K, int reps, float *ms) {
+    CHK(need_ctx());
+    if (!op || !X || !Y || !ms || reps < 1 || (kind != 0 && kind != 1)) return fail(SGPU_ERR_ARG, "bad argument");
+    if (kind == 1 && (!RHS || !op->inv_diag)) return fail(SGPU_ERR_ARG, "a Jacobi sweep needs rhs and inv_diag");
+    CHK(block_check(op, K, "time_block"));
+    CHK(block_timer_events());
+    HIPCHK(hipEventRecord(g_bt0, g.cs));
+    for (int i = 0; i < reps; ++i) {
+        EpiArgs e;
+        if (kind == 1) { e.rhs = RHS; e.inv_diag = op->inv_diag; e.u = X; e.c0 = JACOBI_OMEGA_REF; }
+        CHK(apply_block(op, kind == 1 ? sk::EPI_JACOBI : sk::EPI_SPMV, X, Y, e, K));
+    }
+    HIPCHK(hipEventRecord(g_bt1, g.cs));
+    HIPCHK(hipEventSynchronize(g_bt1));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
+    *ms = t / reps;
+    return SGPU_OK;
+}
+int sgpu_debug_time_vcycle(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int reps, float *ms) {
+    CHK(need_ctx());
+    if (!h || !U || !RHS || !ms || reps < 1) return fail(SGPU_ERR_ARG, "bad argument");
+    AmgBlock *B = nullptr;
+    if (K != 0) { CHK(amg_block_check(h, K, "time_vcycle")); CHK(amg_block(h, K, &B)); }
+    CHK(block_timer_events());
+    CHK(K ? vcycle_block0(h, *B, U, RHS) : vcycle0(h, U, RHS));          // (captures the graph outside the interval)
+    HIPCHK(hipEventRecord(g_bt0, g.cs));
+    for (int i = 0; i < reps; ++i) CHK(K ? vcycle_block0(h, *B, U, RHS) : vcycle0(h, U, RHS));
+    HIPCHK(hipEventRecord(g_bt1, g.cs));
+    HIPCHK(hipEventSynchronize(g_bt1));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
+    *ms = t / reps;
+    return SGPU_OK;
+}
+
+int sgpu_block_pack(const value_t *cols_colmajor, value_t *blk, size_t n, int K) {
+    CHK(need_ctx());
+    if (!cols_colmajor || !blk) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(nullptr, K, "block_pack"));
+    return block_pack(cols_colmajor, blk, n, K);
+}
+
+int sgpu_block_unpack(const value_t *blk, value_t *cols_colmajor, size_t n, int K) {
+    CHK(need_ctx());
+    if (!cols_colmajor || !blk) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(nullptr, K, "block_unpack"));
+    return block_unpack(blk, cols_colmajor, n, K);
+}
+
+int sgpu_op_set_block_lanes(sgpu_op *op, int lanes) {
+    if (!op) return fail(SGPU_ERR_ARG, "null op");
+    if (lanes != 0 && lanes != 1 && lanes != 4 && lanes != 16 && lanes != 64) return fail(SGPU_ERR_ARG, "block lanes per row must be 0 (auto), 1, 4, 16 or 64 (got %d)", lanes);
+    op->block_lanes = lanes;
+    ++g_block_generation;
+    return SGPU_OK;
+}
+
+int sgpu_op_get_block_lanes(const sgpu_op *op, int *lanes) {
+    if (!op || !lanes) return fail(SGPU_ERR_ARG, "null argument");
+    *lanes = op->block_lanes ? op->block_lanes : (op->block_lanes_auto ? op->block_lanes_auto : block_auto_lanes(op));
+    return SGPU_OK;
+}
+
+int sgpu_spmv_block(sgpu_op *op, const value_t *X, value_t *Y, int K) {
+    CHK(need_ctx());
+    if (!op || !X || !Y) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(op, K, "spmv_block"));
+    return apply_block(op, sk::EPI_SPMV, X, Y, EpiArgs(), K);
+}
+
+int sgpu_residual_block(sgpu_op *op, const value_t *U, const value_t *RHS, value_t *RES, int K) {
+    CHK(need_ctx());
+    if (!op || !U || !RHS || !RES) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(op, K, "residual_block"));
+    EpiArgs e; e.rhs = RHS;
+    return apply_block(op, sk::EPI_RESIDUAL, U, RES, e, K);
+}
+
+int sgpu_jacobi_block(sgpu_op *op, int iter, value_t omega, value_t *U, const value_t *RHS, int K) {
+    CHK(need_ctx());
+    if (!op || !U || !RHS || iter < 0) return fail(SGPU_ERR_ARG, "bad argument");
+    CHK(block_check(op, K, "jacobi_block"));
+    if (omega == 0.0) omega = JACOBI_OMEGA_REF;
+    CHK(ensure_blk_tmp(op, K));
+    double *res = nullptr;
+    CHK(jacobi_block_pp(op, iter, omega, U, op->tmp_blk[block_slot(K)], RHS, &res, K));
+    if (res != U) HIPCHK(hipMemcpyAsync(U, res, (size_t)op->M * K * sizeof(double), hipMemcpyDeviceToDevice, g.cs));
+    return SGPU_OK;
+}
+
+int sgpu_chebyshev_block(sgpu_op *op, int iter, value_t eig_max, value_t *U, const value_t *RHS, int K) {
+    CHK(need_ctx());
+    if (!op || !U || !RHS || iter < 0) return fail(SGPU_ERR_ARG, "bad argument");
+    CHK(block_check(op, K, "chebyshev_block"));
+    if (!(eig_max > 0.0)) return fail(SGPU_ERR_ARG, "chebyshev needs eig_max > 0");
+    CHK(ensure_blk_tmp(op, K)); CHK(ensure_blk_d(op, K));
+    double *res = nullptr;
+    CHK(cheby_block_pp(op, iter, eig_max, U, op->tmp_blk[block_slot(K)], RHS, &res, K));
+    if (res != U) HIPCHK(hipMemcpyAsync(U, res, (size_t)op->M * K * sizeof(double), hipMemcpyDeviceToDevice, g.cs));
+    return SGPU_OK;
+}
+
+int sgpu_prolong_correct_block(sgpu_op *P, const value_t *E_coarse, value_t *U, int K) {
+    CHK(need_ctx());
+    if (!P || !E_coarse || !U) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(P, K, "prolong_correct_block"));
+    return apply_block(P, sk::EPI_SUB, E_coarse, U, EpiArgs(), K);
+}
+
+int sgpu_vcycle_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K) {
+    CHK(need_ctx());
+    if (!h || !U || !RHS) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(amg_block_check(h, K, "vcycle_block"));
+    AmgBlock *B = nullptr;
+    CHK(amg_block(h, K, &B));
+    return vcycle_block0(h, *B, U, RHS);
+}
+
+// sgpu_solve_pCG's recurrence for K columns in lockstep.  Per column: its own rho, alpha, beta (device scalars, rows of S) and
+// threshold; a column is frozen from the iteration at which its ||r||^2 drops below its threshold -- bit j of `active` leaves
+// the mask every update kernel takes, and the column's u, r, p and scalars are not written again.  One host synchronisation
+// per iteration: the K current dots.
+int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int *iters, value_t *hist, int cap) {
+    CHK(need_ctx());
+    if (!h || !U || !RHS) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(amg_block_check(h, K, "solve_pCG_block"));
+    AmgBlock *Bp = nullptr;
+    CHK(amg_block(h, K, &Bp));
+    AmgBlock &B = *Bp;
+    sgpu_op *A = h->A[0];
+    const size_t sz = (size_t)A->M, szK = sz * K;
+    double *r = B.r, *rho = B.rho, *hh = B.hh, *p = B.p;
+    double *Sa = B.S + 4 * K, *Sb = B.S + 7 * K, *Sph = B.S + 5 * K, *Srr = B.S + 6 * K;    // the slots of sgpu_solve_pCG, a row of K each
+    const unsigned all = (1u << K) - 1u;
+    auto fetch = [&](const double *row) -> int {
+        HIPCHK(hipMemcpyAsync(B.hS, row, K * sizeof(double), hipMemcpyDeviceToHost, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
+        return SGPU_OK;
+    };
+    CHK(sgpu_vec_fill(U, 0.0, szK));
+    { EpiArgs e; e.rhs = RHS; CHK(apply_block(A, sk::EPI_RESIDUAL, U, r, e, K)); }
+    CHK(dot_block(B, r, r, sz, Srr, all));
+    CHK(fetch(Srr));
+    double thr[8], cur[8];
+    int it[8];
+    unsigned active = 0, failed = 0;
+    for (int j = 0; j < K; ++j) {
+        const double init = B.hS[j];
+        if (hist && cap > 0) hist[(size_t)j * cap] = std::sqrt(init);
+        thr[j] = init * h->prm.solver_tol * h->prm.solver_tol;
+        cur[j] = init;
+        it[j] = 0;
+        if (init != 0.0) active |= 1u << j;       // a zero right-hand side: u = 0 is the solution, frozen at iteration 0 (the scalar solve divides 0 by 0 there)
+    }
+    if (active && h->prm.solver_max_iter > 0) {
+        CHK(vcycle_block0(h, B, rho, r, true));
+        CHK(sgpu_vec_copy(p, rho, szK));
+        CHK(dot_block(B, r, rho, sz, Sa, active));
+        const int nb = dot_nblocks(sz);
+        for (int i = 0; i < h->prm.solver_max_iter && active; ++i) {
+            CHK(apply_block(A, sk::EPI_SPMV, p, hh, EpiArgs(), K));
+            CHK(dot_block(B, p, hh, sz, Sph, active));
+            if (K == 2) SGPU_LAUNCH(sk::k_pcg_update_block<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const double *)Sa, (const double *)Sph, (const double *)p, (const double *)hh, U, r, sz, active, B.partials);
+            else if (K == 4) SGPU_LAUNCH(sk::k_pcg_update_block<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const double *)Sa, (const double *)Sph, (const double *)p, (const double *)hh, U, r, sz, active, B.partials);
+            else SGPU_LAUNCH(sk::k_pcg_update_block<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const double *)Sa, (const double *)Sph, (const double *)p, (const double *)hh, U, r, sz, active, B.partials);
+            SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)B.partials, nb, K, Srr, active);
+            HIPCHK(hipGetLastError());
+            CHK(fetch(Srr));
+            for (int j = 0; j < K; ++j) {
+                if (!((active >> j) & 1u)) continue;
+                cur[j] = B.hS[j];
+                it[j] = i + 1;
+                if (hist && i + 1 < cap) hist[(size_t)j * cap + i + 1] = std::sqrt(cur[j]);
+                if (cur[j] < thr[j]) active &= ~(1u << j);
+            }
+            if (!active || i + 1 == h->prm.solver_max_iter) break;
+            CHK(vcycle_block0(h, B, rho, r, true));
+            CHK(dot_block(B, r, rho, sz, Sb, active));
+            const int gd = grid_for(2 * sz);
+            if (K == 2) SGPU_LAUNCH(sk::k_pcg_direction_block<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)Sb, (const double *)Sa, (const double *)rho, p, sz, active);
+            else if (K == 4) SGPU_LAUNCH(sk::k_pcg_direction_block<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)Sb, (const double *)Sa, (const double *)rho, p, sz, active);
+            else SGPU_LAUNCH(sk::k_pcg_direction_block<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)Sb, (const double *)Sa, (const double *)rho, p, sz, active);
+            HIPCHK(hipGetLastError());
+            std::swap(Sa, Sb);
+        }
+    }
+    failed = active;                               // still above their thresholds at solver_max_iter
+    if (iters) for (int j = 0; j < K; ++j) iters[j] = it[j];
+    return failed ? SGPU_ERR_NOCONV : SGPU_OK;
+}
+
+} // extern "C"

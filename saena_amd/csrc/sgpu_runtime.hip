@@ -8,6 +8,7 @@
 #include "../../include/saena_gpu.h"
 #include "../../include/saena_gpu_debug.h"
 #include "kernels.hip.h"
+#include "kernels_block.hip.h"
 #include "host/comm.h"
 #include "host/par.h"
 #include "host/amg_setup.h"
@@ -1371,6 +1372,11 @@ struct sgpu_op {
     double *tmp = nullptr;        // smoother ping-pong buffer [M]
     double *ones = nullptr;       // [M] of 1.0 (sgpu_residual_negative: rhs - A u as 1 * 1 * (rhs - A u)), made at its first call
     double *dvec = nullptr;       // chebyshev d [M]
+    // block entry points (sgpu_*_block): lanes per row of k_csr_block (0: from the mean row length at the first block apply),
+    // and the block ping-pong buffer / Chebyshev d of [M * K] per K = 2, 4, 8, made at the first block smoother call with that K
+    // (never re-allocated: captured block V-cycles hold the pointers)
+    int     block_lanes = 0, block_lanes_auto = 0;
+    double *tmp_blk[3] = {nullptr, nullptr, nullptr}, *dvec_blk[3] = {nullptr, nullptr, nullptr};
     // halo plan
     int     vIndexSize = 0, recvSize = 0;
     int    *vIndex = nullptr;
@@ -1393,6 +1399,7 @@ struct sgpu_op {
     ~sgpu_op() {                  // also runs when sgpu_op_create bails out half-way: nothing leaks
         loc.free_all(); rem.free_all();
         hipFree(dense_rem);
+        for (int k = 0; k < 3; ++k) { hipFree(tmp_blk[k]); hipFree(dvec_blk[k]); }
         hipFree(skip); hipFree(inv_diag); hipFree(tmp); hipFree(ones); hipFree(dvec); hipFree(vIndex); hipFree(send_buf); hipFree(recv_buf); hipFree(send_f); hipFree(recv_f);
         if (ev_x) hipEventDestroy(ev_x);
         if (ev_halo) hipEventDestroy(ev_halo);
@@ -3204,6 +3211,32 @@ int sgpu_chebyshev_host(sgpu_op *op, int iter, value_t eig_max, value_t *u_host,
 
 // ===========================================================================
 // multigrid
+// block V-cycle / pCG state of a hierarchy for ONE K (sgpu_block.hip.inc): made at the first block call with that K
+struct AmgBlock {
+    int K = 0;
+    std::vector<double *> res, rhs, u, alt;   // block work vectors per level, as sgpu_amg's scalar ones
+    double *alt0 = nullptr, *r = nullptr, *rho = nullptr, *hh = nullptr, *p = nullptr;
+    double *cm = nullptr;                     // coarsest CG: the K columns unpacked (rhs, then u), 2 * n * K
+    double *S = nullptr, *partials = nullptr; // device scalars [8][K]; dot partial sums [n_partials][K]
+    double *hS = nullptr;                     // pinned mirror of one row of S
+    struct Captured { double *u; const double *rhs; bool u_zero; hipGraph_t graph; hipGraphExec_t exec; };
+    std::vector<Captured> graphs;
+    uint64_t graph_gen = 0, block_gen = 0;
+    void drop_graphs() {
+        for (auto &c : graphs) { hipGraphExecDestroy(c.exec); hipGraphDestroy(c.graph); }
+        graphs.clear();
+    }
+    ~AmgBlock() {
+        drop_graphs();
+        for (auto q : res) hipFree(q);
+        for (auto q : rhs) hipFree(q);
+        for (auto q : u) hipFree(q);
+        for (auto q : alt) hipFree(q);
+        hipFree(alt0); hipFree(r); hipFree(rho); hipFree(hh); hipFree(p); hipFree(cm); hipFree(S); hipFree(partials);
+        if (hS) hipHostFree(hS);
+    }
+};
+
 struct sgpu_amg {
     int nlevels = 0;
     std::vector<sgpu_op *> A, P, R;
@@ -3238,7 +3271,9 @@ struct sgpu_amg {
     double *tail_out = nullptr;        // which of u[tail_level] / alt[tail_level] holds the sub-V-cycle's result
     uint64_t graph_gen = 0;            // g_plan_generation the graphs were captured under
     bool coarse_host_driven = false;   // coarsest level too large for the LDS-resident solvers: host-driven CG, no graph capture
+    std::unique_ptr<AmgBlock> blk[3];  // K = 2, 4, 8
     void drop_graphs() {
+        for (auto &b : blk) if (b) b->drop_graphs();
         for (auto &c : graphs) { hipGraphExecDestroy(c.exec); hipGraphDestroy(c.graph); }
         graphs.clear();
         if (tail_exec) { hipGraphExecDestroy(tail_exec); tail_exec = nullptr; }
@@ -3826,6 +3861,8 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 }
 
 } // extern "C"
+
+#include "sgpu_block.hip.inc"
 
 // ===========================================================================
 // Setup-time collectives of the host layer over the same RCCL communicator

@@ -97,6 +97,7 @@ HOST_SYMBOLS.update({
     "saena_amg_device_op": (_VP, [_VP, C.c_int, C.c_int]),
     "saena_amg_solve": (C.c_int, [_VP, _PD, _PD, _PI, _PD, C.c_int]),
     "saena_amg_solve_pCG": (C.c_int, [_VP, _PD, _PD, _PI, _PD, C.c_int]),
+    "saena_amg_solve_pCG_block": (C.c_int, [_VP, _PD, _PD, C.c_int, _PI, _PD, C.c_int]),
 })
 
 _libs = {}
@@ -522,6 +523,18 @@ class AmgSolver:
 
     def solve_pCG(self, rhs):
         return self._solve(self.L.saena_amg_solve_pCG, rhs)
+
+    def solve_pCG_block(self, rhs, cap=256):
+        """rhs: (n, K) with K = 2, 4 or 8 -> (u (n, K), iters[K], [history of column j], converged): saena_amg_solve_pCG_block"""
+        rhs = np.asfortranarray(rhs, np.float64)                 # column-major n x K
+        n, K = rhs.shape
+        u = np.zeros((n, K), order="F")
+        it = (C.c_int * K)()
+        hist = np.full((K, cap), np.nan)
+        st = self.L.saena_amg_solve_pCG_block(self.h, rhs.ctypes.data_as(_PD), u.ctypes.data_as(_PD), K, it, hist.ctypes.data_as(_PD), cap)
+        if st not in (0, -6):
+            _check(self.L, st)
+        return u, [int(v) for v in it], [h[~np.isnan(h)] for h in hist], st == 0
 
     def free(self):
         if self.h:
