@@ -78,6 +78,20 @@ int sgpu_debug_device_info(char *buf, int len);
 int sgpu_debug_time_block(sgpu_op *op, int kind, const value_t *X, const value_t *RHS, value_t *Y, int K, int reps, float *ms_per_launch);
 int sgpu_debug_time_vcycle(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int reps, float *ms_per_cycle);
 
+/* tests (tests/test_gpu_block_solver_layer.py): the block dot and the two block pCG updates as sgpu_solve_pCG_block launches them
+ * (its K switch and its grids), on the caller's block vectors X[i * K + j] of n rows.  The hierarchy is taken for its per-K state
+ * alone (the partial sums of the dots): n is the caller's and need not be the hierarchy's size.  Every pointer is a device
+ * pointer; num / den / out_dev / rr_dev hold K doubles.  Bit j of `active` = column j takes part: the others are not written,
+ * and neither are their out_dev[j] / rr_dev[j].
+ *   dot:        out_dev[j] = X_j . Y_j
+ *   pcg_update: alpha_j = num[j] / den[j]; U_j -= alpha_j P_j; R_j -= alpha_j H_j; rr_dev[j] = R_j . R_j
+ *   direction:  beta_j = num[j] / den[j]; P_j = Z_j + beta_j P_j */
+int sgpu_debug_block_dot(sgpu_amg *h, const value_t *X, const value_t *Y, size_t n, int K, unsigned active, value_t *out_dev);
+int sgpu_debug_block_pcg_update(sgpu_amg *h, const value_t *num, const value_t *den, const value_t *P, const value_t *H,
+                                value_t *U, value_t *R, size_t n, int K, unsigned active, value_t *rr_dev);
+int sgpu_debug_block_pcg_direction(sgpu_amg *h, const value_t *num, const value_t *den, const value_t *Z, value_t *P,
+                                   size_t n, int K, unsigned active);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,9 @@ SYMBOLS = {
     "sgpu_solve_pCG_block": (C.c_int, [_VP, _VP, _VP, C.c_int, _PI, _PD, C.c_int]),
     "sgpu_debug_time_block": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_time_vcycle": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "sgpu_debug_block_dot": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, C.c_uint, _VP]),
+    "sgpu_debug_block_pcg_update": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_uint, _VP]),
+    "sgpu_debug_block_pcg_direction": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_uint]),
     "sgpu_time_kernel": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_algorithmic_bytes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
 }
@@ -552,6 +555,16 @@ class Amg:
         if st not in (0, -6):
             check(st)
         return [int(v) for v in it], [h[~np.isnan(h)] for h in hist], st == 0
+
+    # the block dot and the block pCG updates on the caller's device vectors (sgpu_debug_block_*): n rows of K interleaved columns
+    def debug_block_dot(self, X, Y, n, K, active, out):
+        check(lib().sgpu_debug_block_dot(self.h, X.ptr, Y.ptr, int(n), int(K), int(active), out.ptr))
+
+    def debug_block_pcg_update(self, num, den, P, H, U, R, n, K, active, rr):
+        check(lib().sgpu_debug_block_pcg_update(self.h, num.ptr, den.ptr, P.ptr, H.ptr, U.ptr, R.ptr, int(n), int(K), int(active), rr.ptr))
+
+    def debug_block_pcg_direction(self, num, den, Z, P, n, K, active):
+        check(lib().sgpu_debug_block_pcg_direction(self.h, num.ptr, den.ptr, Z.ptr, P.ptr, int(n), int(K), int(active)))
 
     def set_solve_params(self, max_iter, tol, smoother, pre, post):
         check(lib().sgpu_amg_set_solve_params(self.h, int(max_iter), float(tol), 0 if smoother == "jacobi" else 1, int(pre), int(post)))

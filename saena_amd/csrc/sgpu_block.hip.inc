@@ -262,6 +262,38 @@ int dot_block(AmgBlock &B, const double *x, const double *y, size_t n, double *o
     return SGPU_OK;
 }
 
+// alpha_j = num[j] / den[j]; u -= alpha p, r -= alpha h and out[j] = r_j . r_j on the columns of `active`: the fused update on
+// the dot's grid, then the dot's second kernel
+int pcg_update_block(AmgBlock &B, const double *num, const double *den, const double *p, const double *hh, double *u, double *r, size_t n,
+                     unsigned active, double *out) {
+    const int nb = dot_nblocks(n), K = B.K;
+    if (K == 2) SGPU_LAUNCH(sk::k_pcg_update_block<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
+    else if (K == 4) SGPU_LAUNCH(sk::k_pcg_update_block<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
+    else SGPU_LAUNCH(sk::k_pcg_update_block<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
+    SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)B.partials, nb, K, out, active);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+// beta_j = num[j] / den[j]; p = z + beta p on the columns of `active`
+int pcg_direction_block(AmgBlock &B, const double *num, const double *den, const double *z, double *p, size_t n, unsigned active) {
+    const int gd = grid_for(2 * n), K = B.K;
+    if (K == 2) SGPU_LAUNCH(sk::k_pcg_direction_block<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
+    else if (K == 4) SGPU_LAUNCH(sk::k_pcg_direction_block<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
+    else SGPU_LAUNCH(sk::k_pcg_direction_block<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+// what the three sgpu_debug_block_* wrappers check: the hierarchy (for its AmgBlock), K and the column mask
+int debug_block_args(sgpu_amg *h, int K, unsigned active, const char *what, AmgBlock **B) {
+    CHK(need_ctx());
+    if (!h) return fail(SGPU_ERR_ARG, "%s: null hierarchy", what);
+    CHK(amg_block_check(h, K, what));
+    if (active >> K) return fail(SGPU_ERR_ARG, "%s: the column mask 0x%x names columns past K = %d", what, active, K);
+    return amg_block(h, K, B);
+}
+
 } // namespace
 
 extern "C" {
@@ -307,6 +339,30 @@ int sgpu_debug_time_vcycle(sgpu_amg *h, value_t *U, const value_t *RHS, int K, i
     HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
     *ms = t / reps;
     return SGPU_OK;
+}
+
+// ---- tests (include/saena_gpu_debug.h): the launch code of the block dot and of the two pCG updates on the caller's vectors ----
+int sgpu_debug_block_dot(sgpu_amg *h, const value_t *X, const value_t *Y, size_t n, int K, unsigned active, value_t *out_dev) {
+    AmgBlock *B = nullptr;
+    CHK(debug_block_args(h, K, active, "debug_block_dot", &B));
+    if (!X || !Y || !out_dev) return fail(SGPU_ERR_ARG, "null argument");
+    return dot_block(*B, X, Y, n, out_dev, active);
+}
+
+int sgpu_debug_block_pcg_update(sgpu_amg *h, const value_t *num, const value_t *den, const value_t *P, const value_t *H,
+                                value_t *U, value_t *R, size_t n, int K, unsigned active, value_t *rr_dev) {
+    AmgBlock *B = nullptr;
+    CHK(debug_block_args(h, K, active, "debug_block_pcg_update", &B));
+    if (!num || !den || !P || !H || !U || !R || !rr_dev) return fail(SGPU_ERR_ARG, "null argument");
+    return pcg_update_block(*B, num, den, P, H, U, R, n, active, rr_dev);
+}
+
+int sgpu_debug_block_pcg_direction(sgpu_amg *h, const value_t *num, const value_t *den, const value_t *Z, value_t *P,
+                                   size_t n, int K, unsigned active) {
+    AmgBlock *B = nullptr;
+    CHK(debug_block_args(h, K, active, "debug_block_pcg_direction", &B));
+    if (!num || !den || !Z || !P) return fail(SGPU_ERR_ARG, "null argument");
+    return pcg_direction_block(*B, num, den, Z, P, n, active);
 }
 
 int sgpu_block_pack(const value_t *cols_colmajor, value_t *blk, size_t n, int K) {
@@ -432,15 +488,10 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
         CHK(vcycle_block0(h, B, rho, r, true));
         CHK(sgpu_vec_copy(p, rho, szK));
         CHK(dot_block(B, r, rho, sz, Sa, active));
-        const int nb = dot_nblocks(sz);
         for (int i = 0; i < h->prm.solver_max_iter && active; ++i) {
             CHK(apply_block(A, sk::EPI_SPMV, p, hh, EpiArgs(), K));
             CHK(dot_block(B, p, hh, sz, Sph, active));
-            if (K == 2) SGPU_LAUNCH(sk::k_pcg_update_block<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const double *)Sa, (const double *)Sph, (const double *)p, (const double *)hh, U, r, sz, active, B.partials);
-            else if (K == 4) SGPU_LAUNCH(sk::k_pcg_update_block<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const double *)Sa, (const double *)Sph, (const double *)p, (const double *)hh, U, r, sz, active, B.partials);
-            else SGPU_LAUNCH(sk::k_pcg_update_block<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const double *)Sa, (const double *)Sph, (const double *)p, (const double *)hh, U, r, sz, active, B.partials);
-            SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)B.partials, nb, K, Srr, active);
-            HIPCHK(hipGetLastError());
+            CHK(pcg_update_block(B, Sa, Sph, p, hh, U, r, sz, active, Srr));
             CHK(fetch(Srr));
             for (int j = 0; j < K; ++j) {
                 if (!((active >> j) & 1u)) continue;
@@ -452,11 +503,7 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
             if (!active || i + 1 == h->prm.solver_max_iter) break;
             CHK(vcycle_block0(h, B, rho, r, true));
             CHK(dot_block(B, r, rho, sz, Sb, active));
-            const int gd = grid_for(2 * sz);
-            if (K == 2) SGPU_LAUNCH(sk::k_pcg_direction_block<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)Sb, (const double *)Sa, (const double *)rho, p, sz, active);
-            else if (K == 4) SGPU_LAUNCH(sk::k_pcg_direction_block<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)Sb, (const double *)Sa, (const double *)rho, p, sz, active);
-            else SGPU_LAUNCH(sk::k_pcg_direction_block<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)Sb, (const double *)Sa, (const double *)rho, p, sz, active);
-            HIPCHK(hipGetLastError());
+            CHK(pcg_direction_block(B, Sb, Sa, rho, p, sz, active));
             std::swap(Sa, Sb);
         }
     }

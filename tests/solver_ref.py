@@ -97,7 +97,19 @@ EARLY_OUT_CASES = (("tri", 257), ("tri", 1025))                      # rhs = 0 a
 FALLBACK_CASES = (("tri", 1025), ("band17", 1025), ("arrow", 1025))  # more rows than the LDS solvers hold
 KRYLOV_SIZES = (262401, 524545)                                      # solve_CG on tri(n): past 256 * 1024 rows (the dot's grid, which the fused
 #                                                                      update runs on) and past 256 * 2048 (the direction update's grid)
-ALL_CASES = sorted(set(DIRECT_CASES) | set(CAPPED_CASES) | set(EARLY_OUT_CASES) | set(FALLBACK_CASES))
+# the block path (tests/test_gpu_block_solver_layer.py).  k_dense_solve_block<C> holds C = min(K, pow2floor(4096 / n)) columns of
+# the right-hand side in LDS per pass: 512 rows at K = 8 fill it with C = 8, 513 to 1024 rows at K = 8 take two passes of C = 4,
+# 1024 rows at K = 4 fill it with C = 4
+BLOCK_DIRECT_CASES = ([("tri", n) for n in (1, 9, 64, 65, 511, 512, 513, 729, 1023, 1024)]
+                      + [(f, n) for f in ("band17", "arrow", "shifted") for n in (257, 1024)] + [("dense_spd", 200)])
+BLOCK_CG_CASES = [c for c in CG_CASES if c[1] in FAMILY_SIZES] + [("tri", 1023)]
+BLOCK_NEW_CASES = sorted(set(BLOCK_DIRECT_CASES) - set(DIRECT_CASES))  # tri 511, 512, 513, 729: in no scalar list
+TWO_LEVEL = ((262401, 257), (524545, 513))                           # tri_two_level: 1022 and 1023 coarse rows; the fine level is past
+#                                                                      the grid of the block dot / update, the second past the direction's too
+# every size at which a block vector kernel takes another path: wave and block edges, the second grid-stride trip of the dot and
+# the fused update (n > 256 * 1024) and of direction / pack / unpack (n > 256 * 2048)
+BLOCK_VEC_SIZES = (0, 1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 513, 100003, 262144, 262145, 262401, 524288, 524289, 1048577)
+ALL_CASES = sorted(set(DIRECT_CASES) | set(CAPPED_CASES) | set(EARLY_OUT_CASES) | set(FALLBACK_CASES) | set(BLOCK_DIRECT_CASES))
 
 _cache = {}
 
@@ -121,6 +133,47 @@ def case(family, n):
     return _cache[key]
 
 
+_COL_SCALE = (1.0, 0.0, -2.5, 0.75, 4.0, 1.5, -1.0, 3.0)
+
+
+def coarse_columns(family, n, K):
+    """-> (RHS (n, K), X (n, K)): column j is case(family, n)["rhs"] times _COL_SCALE[j] plus 0.1 j, column 1 all zero; X its
+    solve_hp solutions.  A column does not depend on K.  Computed once and shared: treat as read-only"""
+    c = case(family, n)
+    for j in range(K):
+        if (family, n, j) not in _cache:
+            b = _COL_SCALE[j] * c["rhs"] + (0.1 * j if j != 1 else 0.0)
+            x = solve_hp(c["dense"], b)[0] if j != 1 else np.zeros(n)
+            b.setflags(write=False); x.setflags(write=False)
+            _cache[(family, n, j)] = (b, x)
+    cols = [_cache[(family, n, j)] for j in range(K)]
+    return np.stack([b for b, _ in cols], axis=1), np.stack([x for _, x in cols], axis=1)
+
+
+def tri_two_level(n, agg):
+    """-> ([A, Ac], [P], [R]): A = tri(n), P piecewise constant (ones) over aggregates of `agg` consecutive rows, R = P^T,
+    Ac = R A P with sorted indices (tridiagonal, ceil(n / agg) rows)"""
+    A = tri(n)
+    nc = -(-n // agg)
+    P = sp.csr_matrix((np.ones(n), (np.arange(n), np.arange(n) // agg)), shape=(n, nc))
+    R = P.T.tocsr()
+    Ac = (R @ A @ P).tocsr()
+    Ac.sort_indices()
+    R.sort_indices()
+    return [A, Ac], [P], [R]
+
+
+def block_columns(n, K):
+    """-> K distinct right-hand sides of n rows (a list).  Smooth ones (1 and 7) that the coarse level takes most of, rough ones
+    that the smoother takes, a single spike, a seeded random one: they reach a tolerance at different iterations"""
+    i = np.arange(n, dtype=np.float64)
+    spike = np.zeros(n)
+    spike[n // 2] = 1.0
+    cols = [rhs_for(n), np.sin(0.001 * i), np.random.default_rng(7 + n).standard_normal(n), spike,
+            1.0 + 0.5 * np.sin(0.2 * i), (1.0 - 2.0 * (np.arange(n) % 2)) * (1.0 + 0.1 * np.cos(0.01 * i)), i / n - 0.5, np.cos(0.0003 * i)]
+    return cols[:K]
+
+
 # ---------------------------------------------------------------------------
 # references
 def residual_hp(A, x, b):
@@ -129,9 +182,12 @@ def residual_hp(A, x, b):
     b = np.asarray(b, np.longdouble)
     if sp.issparse(A):
         A = A.tocsr()
-        rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
-        Ax = np.zeros(A.shape[0], np.longdouble)
-        np.add.at(Ax, rows, A.data.astype(np.longdouble) * x[A.indices])
+        prod = A.data.astype(np.longdouble) * x[A.indices]
+        if A.shape[0] and np.diff(A.indptr).min() > 0:          # no empty row: a row's products added in stored order, quickly
+            Ax = np.add.reduceat(prod, A.indptr[:-1])
+        else:
+            Ax = np.zeros(A.shape[0], np.longdouble)
+            np.add.at(Ax, np.repeat(np.arange(A.shape[0]), np.diff(A.indptr)), prod)
     else:
         Ax = np.asarray(A, np.longdouble) @ x
     r = b - Ax
@@ -178,10 +234,11 @@ def dot_bound(x, y):
     return k * U * s / (1 - k * U)
 
 
-def dot_inputs(n, kind):
+def dot_inputs(n, kind, seed=0):
     """-> (x, y) float64.  normal: mixed signs; positive: no cancellation at all; cancelling: the second half-block undoes
-    the first (y[h:2h] = -y[:h], x[h:2h] = x[:h]), so the exact result is small against sum|x y|"""
-    rng = np.random.default_rng(1000 + n)
+    the first (y[h:2h] = -y[:h], x[h:2h] = x[:h]), so the exact result is small against sum|x y|.  seed: another pair of the
+    same kind (the columns of a block)"""
+    rng = np.random.default_rng(1000 + n + 7919 * 1000 * seed)
     x, y = rng.standard_normal(n), rng.standard_normal(n)
     if kind == "positive":
         x, y = np.abs(x) + 0.5, np.abs(y) + 0.5
@@ -234,6 +291,18 @@ def dot_blocked(x, y):
     for k in range(trips2):
         s2 = s2 + p[k]
     return float(_block_sums(s2)[0])
+
+
+def pcg_update(num, den, p, h, u, r):
+    """k_pcg_update_block on one column, a rounding per operation: alpha = num / den; -> (u - alpha p, r - alpha h)"""
+    alpha = np.float64(num) / np.float64(den)
+    return u - alpha * p, r - alpha * h
+
+
+def pcg_direction(num, den, z, p):
+    """k_pcg_direction_block on one column: beta = num / den; -> 1 z + beta p"""
+    beta = np.float64(num) / np.float64(den)
+    return 1.0 * z + beta * p
 
 
 def coarsest_cg(A, rhs, u0=None, tol=CG_TOL, max_iter=CG_MAX_ITER):
@@ -297,6 +366,14 @@ def gauss_jordan_inverse(D, pivot=True):
             np.multiply.outer(f, m[c], out=t)
             m -= t
     return inv, swaps
+
+
+def inverse(family, n):
+    """gauss_jordan_inverse of case(family, n), computed once (seconds at 1024 rows) and shared: treat as read-only"""
+    if ("inv", family, n) not in _cache:
+        _cache[("inv", family, n)] = gauss_jordan_inverse(case(family, n)["dense"])
+        _cache[("inv", family, n)][0].setflags(write=False)
+    return _cache[("inv", family, n)]
 
 
 def direct_bound(n, cond):
