@@ -259,8 +259,14 @@ public:
     // The reference declares both (saena.hpp:230-231) and compiles their bodies OUT (`#if 0`, saena_object_solve.cpp:3808 / 4077: GMRES and
     // pGMRES return 0 without touching u).  Mirrored as that: the solve parameters are re-read like every solve* does, u is left as it
     // was (allocated and zeroed when null), a line says so, 0 is returned.
+    // The live method for operators that are not symmetric positive definite is solve_pFGMRES below.
     int solve_GMRES(value_t *&u, saena::options *opts);
     int solve_pGMRES(value_t *&u, saena::options *opts);
+    // Restarted flexible GMRES, right-preconditioned by one V-cycle per inner iteration (precondition = false: plain restarted GMRES),
+    // for operators solve_pCG is not defined for (sgpu_solve_FGMRES; one rank).  restart: 1..64 inner iterations per cycle;
+    // opts->get_max_iter() caps the inner iterations.  residual_history() holds ||r_0|| and the residual estimate after every inner
+    // iteration, last_iterations() their number; returns 1 if the recomputed residual did not reach the tolerance
+    int solve_pFGMRES(value_t *&u, saena::options *opts, int restart = 30, bool precondition = true);
     comm get_orig_comm();
 
     int  switch_to_dense(bool val);                 // dense row-major storage for the coarse levels past the density threshold
@@ -300,7 +306,8 @@ private:
     float dense_thre_override_ = 0;
     int max_level_override_ = -1;
     void drop_device();
-    int run(value_t *&u, saena::options *opts, int which, bool print_info);   // which: 0 solve, 1 solve_pCG, 2 solve_CG, 3 solve_smoother
+    // which: 0 solve, 1 solve_pCG, 2 solve_CG, 3 solve_smoother, 4 solve_pFGMRES (the only one that reads restart / precondition)
+    int run(value_t *&u, saena::options *opts, int which, bool print_info, int restart = 0, bool precondition = true);
     int gmres_compiled_out(const char *name, value_t *&u, saena::options *opts);
 };
 

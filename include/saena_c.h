@@ -164,6 +164,9 @@ int   saena_amg_solve_pCG(saena_amg_h *S, const value_t *rhs_host, value_t *u_ho
 /* [GPU] solve_pCG for K = 2, 4 or 8 right-hand sides through one pass over every operator (sgpu_solve_pCG_block; one rank):
  * rhs_host / u_host are column-major n x K (column j at [j*n]), iters[K], res_hist[K][hist_cap] */
 int   saena_amg_solve_pCG_block(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int K, int *iters, value_t *res_hist, int hist_cap);
+/* [GPU] restarted flexible GMRES for operators that are not symmetric positive definite (sgpu_solve_FGMRES; one rank): restart in
+ * 1..64, precond 1 = one V-cycle per iteration, 0 = none; iters counts inner iterations, res_hist[k] is the residual estimate */
+int   saena_amg_solve_pFGMRES(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int restart, int precond, int *iters, value_t *res_hist, int hist_cap);
 
 #ifdef __cplusplus
 }

@@ -274,6 +274,22 @@ int sgpu_vcycle_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K);
 int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K,
                          int *iters /*[K]*/, value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
 
+/* ---- restarted flexible GMRES ------------------------------------------------
+ * For operators that are not symmetric positive definite, where sgpu_solve_pCG is not defined.  Right-preconditioned and flexible
+ * (the preconditioned vectors are stored), so a V-cycle that is not a fixed linear map -- the CG coarsest solver, a Chebyshev
+ * smoother -- is a valid preconditioner.  restart: 1..64 inner iterations per cycle; precond 1: one V-cycle from a zero iterate,
+ * exactly what sgpu_solve_pCG applies; precond 0: none (plain restarted GMRES).  u starts from zero.  res_hist[0] = ||r_0||,
+ * res_hist[k] = the Givens estimate of ||r_k|| after inner iteration k; the threshold is ||r_0||^2 tol^2 as in sgpu_solve_pCG.  At
+ * the end of every cycle rhs - A u is recomputed; only that recomputed norm (*true_res, may be NULL) declares convergence, and
+ * another cycle starts when the estimate was optimistic.  *iters counts inner iterations (at most solver_max_iter).  A zero
+ * right-hand side returns u = 0, 0 iterations, SGPU_OK.  SGPU_ERR_NOCONV: not converged within solver_max_iter, or a breakdown
+ * (u holds the last completed cycle).  One rank; a hierarchy that needs the host-driven coarsest CG or an operator with a remote
+ * part is refused with SGPU_ERR_ARG.  The work space (2 restart + 3 vectors) is allocated at the first call with a given restart
+ * length and freed with the hierarchy; sgpu_solve_pCG's vectors and the cache of captured V-cycles are not touched.  One host
+ * synchronisation per inner iteration. */
+int sgpu_solve_FGMRES(sgpu_amg *h, value_t *u, const value_t *rhs, int restart, int precond,
+                      int *iters, value_t *res_hist, int hist_cap, value_t *true_res);
+
 /* ---- measurement -----------------------------------------------------------
  * Runs `reps` back-to-back launches of one kernel on the compute stream,
  * bracketed by hipEvents recorded on that same stream; *ms_per_launch is the

@@ -92,6 +92,15 @@ int sgpu_debug_block_pcg_update(sgpu_amg *h, const value_t *num, const value_t *
 int sgpu_debug_block_pcg_direction(sgpu_amg *h, const value_t *num, const value_t *den, const value_t *Z, value_t *P,
                                    size_t n, int K, unsigned active);
 
+/* tests (tests/test_gpu_gmres.py): the two Gram-Schmidt launch helpers of sgpu_solve_FGMRES on the caller's arrays.  V: device,
+ * column-major, column c at V + c * ld, ld even and >= n, 16-byte aligned; w: device, n rows, 16-byte aligned; ncols <= 65.
+ *   dots:   out_host[c] = V[:,c] . w
+ *   update: w -= sum_c h_host[c] V[:,c], ascending c, product rounded then subtracted; *norm2_out_host (may be NULL) = the new w . w
+ * time_gs (tests/perf_gmres.py): ms per run of `reps` back-to-back runs, kind 0: dots, 1: update with the norm (zero coefficients). */
+int sgpu_debug_gs_dots(const value_t *V, size_t ld, int ncols, const value_t *w, size_t n, value_t *out_host);
+int sgpu_debug_gs_update(const value_t *V, size_t ld, int ncols, const value_t *h_host, value_t *w, size_t n, value_t *norm2_out_host);
+int sgpu_debug_time_gs(int kind, const value_t *V, size_t ld, int ncols, value_t *w, size_t n, int reps, float *ms_per_run);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,10 @@ SYMBOLS = {
     "sgpu_debug_block_dot": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, C.c_uint, _VP]),
     "sgpu_debug_block_pcg_update": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_uint, _VP]),
     "sgpu_debug_block_pcg_direction": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_uint]),
+    "sgpu_solve_FGMRES": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _PI, _PD, C.c_int, _PD]),
+    "sgpu_debug_gs_dots": (C.c_int, [_VP, C.c_size_t, C.c_int, _VP, C.c_size_t, _PD]),
+    "sgpu_debug_gs_update": (C.c_int, [_VP, C.c_size_t, C.c_int, _PD, _VP, C.c_size_t, _PD]),
+    "sgpu_debug_time_gs": (C.c_int, [C.c_int, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_time_kernel": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_algorithmic_bytes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
 }
@@ -537,6 +541,16 @@ class Amg:
     def solve_smoother(self, u, rhs):
         return self._solve(lib().sgpu_solve_smoother, u, rhs, cap=2048)
 
+    def solve_fgmres(self, u, rhs, restart=30, precond=True, cap=4096):
+        """-> (iters, history, converged, true_res): sgpu_solve_FGMRES; history[0] = ||r_0||, history[k] the Givens estimate after inner
+        iteration k, true_res the last recomputed ||rhs - A u||"""
+        it, tr = C.c_int(), C.c_double()
+        hist = np.full(cap, np.nan)
+        st = lib().sgpu_solve_FGMRES(self.h, u.ptr, rhs.ptr, int(restart), 1 if precond else 0, C.byref(it), hist.ctypes.data_as(_PD), cap, C.byref(tr))
+        if st not in (0, -6):
+            check(st)
+        return it.value, hist[~np.isnan(hist)], st == 0, tr.value
+
     def vcycle_block(self, U, RHS):
         check(lib().sgpu_vcycle_block(self.h, U.ptr, RHS.ptr, U.K))
 
@@ -617,6 +631,28 @@ def chain_us():
     v = C.c_double()
     check(lib().sgpu_debug_chain_us(C.byref(v)))
     return v.value
+
+
+def gs_dots(V, ld, ncols, w, n):
+    """-> h[ncols] = V[:,c] . w through the FGMRES launch helper (sgpu_debug_gs_dots); V, w: DeviceVectors (or anything with .ptr)"""
+    out = np.empty(int(ncols))
+    check(lib().sgpu_debug_gs_dots(V.ptr, int(ld), int(ncols), w.ptr, int(n), out.ctypes.data_as(_PD)))
+    return out
+
+
+def gs_update(V, ld, ncols, h, w, n, norm=False):
+    """w -= sum_c h[c] V[:,c] on the device (sgpu_debug_gs_update); -> the fused ||w||^2 when norm, else None"""
+    h = _ad(h)
+    assert h.size == ncols
+    nrm = C.c_double()
+    check(lib().sgpu_debug_gs_update(V.ptr, int(ld), int(ncols), h.ctypes.data_as(_PD), w.ptr, int(n), C.byref(nrm) if norm else None))
+    return nrm.value if norm else None
+
+
+def time_gs(kind, V, ld, ncols, w, n, reps):
+    ms = C.c_float()
+    check(lib().sgpu_debug_time_gs(int(kind), V.ptr, int(ld), int(ncols), w.ptr, int(n), int(reps), C.byref(ms)))
+    return ms.value
 
 
 def launch_count():

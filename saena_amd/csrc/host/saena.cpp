@@ -332,7 +332,7 @@ int amg::set_rhs(const value_t *rhs_local, index_t size) {
     return 0;
 }
 
-int amg::run(value_t *&u, saena::options *opts, int which, bool print_info) {
+int amg::run(value_t *&u, saena::options *opts, int which, bool print_info, int restart, bool precondition) {
     if (!damg_) throw std::runtime_error("saena::amg: set_matrix first");
     const size_t n = (size_t)A_->get_num_local_rows();
     if (rhs_.size() != n) throw std::runtime_error("saena::amg: set_rhs first");
@@ -346,6 +346,7 @@ int amg::run(value_t *&u, saena::options *opts, int which, bool print_info) {
     int st = which == 1 ? sgpu_solve_pCG(damg_, du, dr, &iters_, hist_.data(), (int)hist_.size())
            : which == 2 ? sgpu_solve_CG(damg_, du, dr, &iters_, hist_.data(), (int)hist_.size())
            : which == 3 ? sgpu_solve_smoother(damg_, du, dr, &iters_, hist_.data(), (int)hist_.size())
+           : which == 4 ? sgpu_solve_FGMRES(damg_, du, dr, restart, precondition ? 1 : 0, &iters_, hist_.data(), (int)hist_.size(), nullptr)
                         : sgpu_solve(damg_, du, dr, &iters_, hist_.data(), (int)hist_.size());
     if (st != SGPU_OK && st != SGPU_ERR_NOCONV) { sgpu_vec_free(du); sgpu_vec_free(dr); gchk(st, "solve"); }
     hist_.resize((size_t)std::min<int>(iters_ + 1, 4096));
@@ -362,6 +363,7 @@ int amg::run(value_t *&u, saena::options *opts, int which, bool print_info) {
 int amg::solve(value_t *&u, saena::options *opts) { return run(u, opts, 0, true); }
 int amg::solve_pCG(value_t *&u, saena::options *opts, bool print_info) { return run(u, opts, 1, print_info); }
 int amg::solve_CG(value_t *&u, saena::options *opts) { return run(u, opts, 2, true); }
+int amg::solve_pFGMRES(value_t *&u, saena::options *opts, int restart, bool precondition) { return run(u, opts, 4, true, restart, precondition); }
 
 int amg::set_rhs_block(const value_t *rhs_local, index_t size, int nrhs) {
     if (!A_ || size != A_->get_num_local_rows()) throw std::runtime_error("saena::amg::set_rhs_block: size does not match the local rows");
@@ -456,7 +458,7 @@ int amg::solve_petsc(value_t *&, saena::options *) {
     return 1;
 }
 // solve_GMRES / solve_pGMRES (saena.cpp:818-835 -> saena_object::GMRES / pGMRES, whose bodies sit inside `#if 0`, saena_object_solve.cpp:3808 /
-// 4077): set_solve_params, then nothing
+// 4077): set_solve_params, then nothing.  The live method for nonsymmetric operators is solve_pFGMRES.
 int amg::gmres_compiled_out(const char *name, value_t *&u, saena::options *opts) {
     if (!damg_) throw std::runtime_error("saena::amg: set_matrix first");
     if (opts)

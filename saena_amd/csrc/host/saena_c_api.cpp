@@ -322,6 +322,7 @@ sgpu_op *saena_amg_device_op(saena_amg_h *, int, int) { no_gpu(); return nullptr
 int saena_amg_solve(saena_amg_h *, const value_t *, value_t *, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_solve_pCG(saena_amg_h *, const value_t *, value_t *, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_solve_pCG_block(saena_amg_h *, const value_t *, value_t *, int, int *, value_t *, int) { return no_gpu(); }
+int saena_amg_solve_pFGMRES(saena_amg_h *, const value_t *, value_t *, int, int, int *, value_t *, int) { return no_gpu(); }
 #else
 static int gchk(int s) { if (s != 0) { h_err = sgpu_last_error(); } return s; }
 static void drop_device(saena_amg_h *S) {
@@ -408,6 +409,19 @@ int saena_amg_solve_pCG_block(saena_amg_h *S, const value_t *rhs_host, value_t *
         if (!s2) s2 = gchk(sgpu_vec_download(u_host, cm, n * K));
     }
     sgpu_vec_free(cm); sgpu_vec_free(u); sgpu_vec_free(rhs);
+    return s ? s : s2;
+}
+
+int saena_amg_solve_pFGMRES(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int restart, int precond, int *iters, value_t *hist, int cap) {
+    if (!S->damg) { h_err = "saena_amg_to_device has not been called"; return -1; }
+    const size_t n = S->H.dist.empty() ? (size_t)S->H.levels[0].A->M : (size_t)S->H.dist[0].A.M;
+    value_t *u = nullptr, *rhs = nullptr;
+    if (gchk(sgpu_vec_alloc(&u, n)) || gchk(sgpu_vec_alloc(&rhs, n))) { sgpu_vec_free(u); sgpu_vec_free(rhs); return -2; }
+    int s = gchk(sgpu_vec_upload(rhs, rhs_host, n));
+    if (!s) s = gchk(sgpu_solve_FGMRES(S->damg, u, rhs, restart, precond, iters, hist, cap, nullptr));
+    int s2 = 0;
+    if (s == 0 || s == SGPU_ERR_NOCONV) s2 = gchk(sgpu_vec_download(u_host, u, n));
+    sgpu_vec_free(u); sgpu_vec_free(rhs);
     return s ? s : s2;
 }
 #endif

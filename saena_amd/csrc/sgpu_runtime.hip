@@ -9,6 +9,7 @@
 #include "../../include/saena_gpu_debug.h"
 #include "kernels.hip.h"
 #include "kernels_block.hip.h"
+#include "kernels_gmres.hip.h"
 #include "host/comm.h"
 #include "host/par.h"
 #include "host/amg_setup.h"
@@ -3237,6 +3238,28 @@ struct AmgBlock {
     }
 };
 
+// restarted FGMRES state of a hierarchy (sgpu_gmres.hip.inc): made at the first sgpu_solve_FGMRES with a given restart length
+struct AmgGmres {
+    int restart = 0;
+    size_t ld = 0;                                   // leading dimension of V and Z: the rows rounded up to an even number
+    double *V = nullptr, *Z = nullptr;               // Krylov basis (restart + 1 columns), preconditioned vectors (restart columns)
+    double *pin = nullptr, *pout = nullptr;          // the fixed pair the V-cycle preconditions through
+    double *coef = nullptr, *partials = nullptr;     // device coefficients (two Gram-Schmidt sets and ||w||^2); the dots' partial sums
+    double *hcoef = nullptr;                         // pinned mirror of coef
+    hipGraph_t graph = nullptr;                      // the V-cycle on (pout, pin) from a zero iterate, captured once
+    hipGraphExec_t exec = nullptr;
+    uint64_t graph_gen = 0;
+    void drop_graph() {
+        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
+        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
+    }
+    ~AmgGmres() {
+        drop_graph();
+        hipFree(V); hipFree(Z); hipFree(pin); hipFree(pout); hipFree(coef); hipFree(partials);
+        if (hcoef) hipHostFree(hcoef);
+    }
+};
+
 struct sgpu_amg {
     int nlevels = 0;
     std::vector<sgpu_op *> A, P, R;
@@ -3272,8 +3295,10 @@ struct sgpu_amg {
     uint64_t graph_gen = 0;            // g_plan_generation the graphs were captured under
     bool coarse_host_driven = false;   // coarsest level too large for the LDS-resident solvers: host-driven CG, no graph capture
     std::unique_ptr<AmgBlock> blk[3];  // K = 2, 4, 8
+    std::unique_ptr<AmgGmres> gm;      // sgpu_solve_FGMRES
     void drop_graphs() {
         for (auto &b : blk) if (b) b->drop_graphs();
+        if (gm) gm->drop_graph();
         for (auto &c : graphs) { hipGraphExecDestroy(c.exec); hipGraphDestroy(c.graph); }
         graphs.clear();
         if (tail_exec) { hipGraphExecDestroy(tail_exec); tail_exec = nullptr; }
@@ -3863,6 +3888,7 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 } // extern "C"
 
 #include "sgpu_block.hip.inc"
+#include "sgpu_gmres.hip.inc"
 
 // ===========================================================================
 // Setup-time collectives of the host layer over the same RCCL communicator

@@ -98,6 +98,7 @@ HOST_SYMBOLS.update({
     "saena_amg_solve": (C.c_int, [_VP, _PD, _PD, _PI, _PD, C.c_int]),
     "saena_amg_solve_pCG": (C.c_int, [_VP, _PD, _PD, _PI, _PD, C.c_int]),
     "saena_amg_solve_pCG_block": (C.c_int, [_VP, _PD, _PD, C.c_int, _PI, _PD, C.c_int]),
+    "saena_amg_solve_pFGMRES": (C.c_int, [_VP, _PD, _PD, C.c_int, C.c_int, _PI, _PD, C.c_int]),
 })
 
 _libs = {}
@@ -523,6 +524,10 @@ class AmgSolver:
 
     def solve_pCG(self, rhs):
         return self._solve(self.L.saena_amg_solve_pCG, rhs)
+
+    def solve_pFGMRES(self, rhs, restart=30, precond=True, cap=4096):
+        """restarted flexible GMRES (saena_amg_solve_pFGMRES) -> (u, inner iterations, residual estimates, converged)"""
+        return self._solve(lambda h, r, u, it, hist, c: self.L.saena_amg_solve_pFGMRES(h, r, u, int(restart), 1 if precond else 0, it, hist, c), rhs, cap=cap)
 
     def solve_pCG_block(self, rhs, cap=256):
         """rhs: (n, K) with K = 2, 4 or 8 -> (u (n, K), iters[K], [history of column j], converged): saena_amg_solve_pCG_block"""
