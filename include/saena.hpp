@@ -267,6 +267,15 @@ public:
     // opts->get_max_iter() caps the inner iterations.  residual_history() holds ||r_0|| and the residual estimate after every inner
     // iteration, last_iterations() their number; returns 1 if the recomputed residual did not reach the tolerance
     int solve_pFGMRES(value_t *&u, saena::options *opts, int restart = 30, bool precondition = true);
+    // The nev smallest eigenpairs of the matrix (symmetric positive definite) by LOBPCG on a block of K = 2, 4 or 8 vectors, one
+    // block V-cycle per iteration as preconditioner (precondition = false: none); sgpu_eigs_LOBPCG, one rank.  x0: column-major
+    // size x K start vectors partitioned like A, or nullptr for the default start; opts->get_max_iter() caps the iterations,
+    // opts->get_tol() is the tolerance of ||A x - lambda x|| relative to lambda.  lambda receives K values, ascending; x (allocated
+    // size * K when null) the eigenvectors, column-major; columns nev .. K-1 are guard vectors that need not have converged.
+    // eig_residuals() holds ||A x_j - lambda_j x_j||, last_iterations() the iterations; returns 1 if a wanted pair did not converge.
+    // Expect slow convergence when nev cuts a cluster of equal eigenvalues in two: let nev end at a gap of the spectrum.
+    int eigs(value_t *&x, std::vector<value_t> &lambda, saena::options *opts, int K, int nev, const value_t *x0 = nullptr, bool precondition = true);
+    const std::vector<value_t> &eig_residuals() const { return eig_res_; }
     comm get_orig_comm();
 
     int  switch_to_dense(bool val);                 // dense row-major storage for the coarse levels past the density threshold
@@ -301,6 +310,7 @@ private:
     std::vector<value_t> rhs_blk_;                 // set_rhs_block: column-major size x nrhs_
     int nrhs_ = 0;
     std::vector<std::vector<value_t>> hist_blk_;   // per column of the last solve_pCG_block
+    std::vector<value_t> eig_res_;                 // of the last eigs
     bool dynamic_levels_ = true;
     bool switch_to_dense_ = false;
     float dense_thre_override_ = 0;

@@ -167,6 +167,21 @@ int   saena_amg_solve_pCG_block(saena_amg_h *S, const value_t *rhs_host, value_t
 /* [GPU] restarted flexible GMRES for operators that are not symmetric positive definite (sgpu_solve_FGMRES; one rank): restart in
  * 1..64, precond 1 = one V-cycle per iteration, 0 = none; iters counts inner iterations, res_hist[k] is the residual estimate */
 int   saena_amg_solve_pFGMRES(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int restart, int precond, int *iters, value_t *res_hist, int hist_cap);
+/* [GPU] the nev smallest eigenpairs of the assembled (symmetric positive definite) matrix by LOBPCG on K = 2, 4 or 8 vectors
+ * (sgpu_eigs_LOBPCG; one rank), precond 1 = one block V-cycle per iteration, 0 = none.  x0_host: column-major n x K start vectors,
+ * or NULL for the default start (a fixed LCG sequence over the row index in (-1, 1), one stream per column).  lambda[K] ascending,
+ * x_host column-major n x K (the eigenvectors; columns nev .. K-1 are guard vectors), res[K] = ||A x_j - lambda_j x_j|| (may be NULL).
+ * nev should end at a gap of the spectrum, not inside a cluster of equal eigenvalues.  SGPU_ERR_NOCONV: the outputs are still written */
+int   saena_amg_eigs(saena_amg_h *S, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
+                     value_t *lambda, value_t *x_host, value_t *res, int *iters);
+
+/* ---- tests: the dense generalised symmetric eigenproblem of the Rayleigh-Ritz step (host/dense_eig.cpp) ----
+ * A v = w B v for symmetric A and symmetric positive definite B of order 1 <= n <= 24, row-major: w[n] ascending, V[i * n + k] =
+ * component i of vector k, V^T B V = I.  Cholesky of B with a relative pivot test, then cyclic Jacobi on L^-1 A L^-T.
+ * -1: B is not numerically positive definite (reported, not factored), -2: the Jacobi iteration failed, -3: n out of range,
+ * -4: null argument.  saena_debug_sym_geig_sweeps: the Jacobi sweeps the last successful call on this thread took. */
+int   saena_debug_sym_geig(int n, const double *A, const double *B, double *w, double *V);
+int   saena_debug_sym_geig_sweeps(void);
 
 #ifdef __cplusplus
 }

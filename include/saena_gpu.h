@@ -290,6 +290,30 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K,
 int sgpu_solve_FGMRES(sgpu_amg *h, value_t *u, const value_t *rhs, int restart, int precond,
                       int *iters, value_t *res_hist, int hist_cap, value_t *true_res);
 
+/* ---- LOBPCG: the smallest eigenpairs of the level-0 operator ------------------
+ * Standard problem A x = lambda x for the symmetric positive definite level-0 operator of a hierarchy, by LOBPCG on a block of K
+ * vectors (K = 2, 4 or 8), preconditioned by one block V-cycle from a zero iterate -- exactly what sgpu_solve_pCG_block applies
+ * (precond 1), or by nothing (precond 0: W = R).  X is a block vector X[i*K + j] (16-byte aligned): on entry the start vectors, which
+ * must be linearly independent; on return the eigenvectors, orthonormal, columns in ascending order of lambda.  The caller asks for the
+ * nev smallest pairs, 1 <= nev <= K; columns nev .. K-1 are guard vectors: iterated and returned, not required to converge.  nev
+ * should end at a gap of the spectrum, not inside a cluster of equal eigenvalues: the convergence of column j is governed by the gap
+ * to the first eigenvalue outside the block, and a cluster cut in two converges slowly.
+ * Column j is converged when ||A x_j - lambda_j x_j|| < tol lambda_j; converged columns stay in the Rayleigh-Ritz basis and stop
+ * contributing search directions (soft locking).  The solve ends when columns 0 .. nev-1 are converged; then A X is recomputed and only
+ * the recomputed norms declare convergence -- when they contradict the carried ones and iterations remain, the iteration goes on.
+ * lambda[K], res[K] (may be NULL; the last recomputed ||r_j||) and res_hist[j*hist_cap + k] (may be NULL; ||r_j|| at the start of
+ * iteration k) are host arrays; *iters = completed iterations.
+ * SGPU_ERR_ARG: K outside {2, 4, 8}, nev outside 1..K, fewer than 3 K rows, more than one rank, an operator with a remote part, a
+ * hierarchy that needs the host-driven coarsest CG, linearly dependent start vectors.  SGPU_ERR_NOCONV: not converged after max_iter
+ * iterations (X, lambda, res are those of the last iteration); a breakdown (the preconditioned residuals of the active columns are
+ * linearly dependent; X and lambda of the last completed iteration stay valid); a Ritz value <= 0 (the operator is not SPD).
+ * The work space (six block vectors) is allocated at the first call with a given K and freed with the hierarchy; the V-cycle runs
+ * through one fixed pair of them in a captured graph of its own, outside the block cache of eight.  Three host synchronisations per
+ * iteration, each of at most 12 K^2 + K doubles. */
+int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, value_t tol, int precond,
+                     value_t *lambda /*[K] host*/, value_t *res /*[K] host: recomputed ||r_j||*/, int *iters,
+                     value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
+
 /* ---- measurement -----------------------------------------------------------
  * Runs `reps` back-to-back launches of one kernel on the compute stream,
  * bracketed by hipEvents recorded on that same stream; *ms_per_launch is the

@@ -101,6 +101,25 @@ int sgpu_debug_gs_dots(const value_t *V, size_t ld, int ncols, const value_t *w,
 int sgpu_debug_gs_update(const value_t *V, size_t ld, int ncols, const value_t *h_host, value_t *w, size_t n, value_t *norm2_out_host);
 int sgpu_debug_time_gs(int kind, const value_t *V, size_t ld, int ncols, value_t *w, size_t n, int reps, float *ms_per_run);
 
+/* tests (tests/test_gpu_eig_kernels.py): the launch helpers of sgpu_eigs_LOBPCG on the caller's block vectors X[i * K + j] of n rows
+ * (16-byte aligned device pointers; the hierarchy is taken for its per-K partial sums alone: n is the caller's).
+ *   block_gram:   out_dev[a * K + b] = X_a . Y_b, K^2 doubles, every entry with the bits of sgpu_dot on the two columns
+ *   block_mix:    Out[i, b] = sum_{s < ns} sum_a S_s[i, a] C_s[a, b] (+ Add[i, b] when Add is not NULL), ns = 1, 2 or 3; C_s: device,
+ *                 K x K row-major; sources beyond ns are ignored; Out may alias any source and Add
+ *   eig_residual: R = AX - X diag(lambda_dev), rr_dev[j] = ||r_j||^2 (K doubles)
+ *   eig_stop:     the next sgpu_eigs_LOBPCG with this K returns SGPU_ERR_NOCONV right after the orthonormalisation step of iteration
+ *                 index `iteration` (0-based), before the Rayleigh-Ritz update: eig_vector then shows W, AW, P, AP as that step left them
+ *   eig_vector:   after a solve, a copy of one of the solver's own block vectors (which: 0 AX, 1 R, 2 W, 3 AW, 4 P, 5 AP) into dst
+ * time_eig (tests/perf_eig.py): ms per run of `reps` back-to-back runs, kind 0: block_gram of (X, Y), 1: block_mix of ns sources
+ * (X, Y, X; zero coefficients) into Out, 2: eig_residual of (AX = X, X = Y) into Out. */
+int sgpu_debug_block_gram(sgpu_amg *h, const value_t *X, const value_t *Y, size_t n, int K, value_t *out_dev);
+int sgpu_debug_block_mix(int K, int ns, const value_t *S0, const value_t *C0, const value_t *S1, const value_t *C1, const value_t *S2,
+                         const value_t *C2, const value_t *Add, value_t *Out, size_t n);
+int sgpu_debug_eig_residual(sgpu_amg *h, const value_t *AX, const value_t *X, const value_t *lambda_dev, value_t *R, size_t n, int K, value_t *rr_dev);
+int sgpu_debug_eig_stop(sgpu_amg *h, int K, int iteration);
+int sgpu_debug_eig_vector(sgpu_amg *h, int K, int which, value_t *dst);
+int sgpu_debug_time_eig(sgpu_amg *h, int kind, int ns, const value_t *X, const value_t *Y, value_t *Out, size_t n, int K, int reps, float *ms_per_run);
+
 #ifdef __cplusplus
 }
 #endif

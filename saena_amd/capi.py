@@ -121,6 +121,13 @@ SYMBOLS = {
     "sgpu_debug_gs_dots": (C.c_int, [_VP, C.c_size_t, C.c_int, _VP, C.c_size_t, _PD]),
     "sgpu_debug_gs_update": (C.c_int, [_VP, C.c_size_t, C.c_int, _PD, _VP, C.c_size_t, _PD]),
     "sgpu_debug_time_gs": (C.c_int, [C.c_int, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
+    "sgpu_eigs_LOBPCG": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PI, _PD, C.c_int]),
+    "sgpu_debug_block_gram": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
+    "sgpu_debug_block_mix": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
+    "sgpu_debug_eig_residual": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
+    "sgpu_debug_eig_stop": (C.c_int, [_VP, C.c_int, C.c_int]),
+    "sgpu_debug_eig_vector": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "sgpu_debug_time_eig": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_time_kernel": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_algorithmic_bytes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
 }
@@ -580,6 +587,36 @@ class Amg:
     def debug_block_pcg_direction(self, num, den, Z, P, n, K, active):
         check(lib().sgpu_debug_block_pcg_direction(self.h, num.ptr, den.ptr, Z.ptr, P.ptr, int(n), int(K), int(active)))
 
+    def lobpcg(self, X, nev, max_iter=100, tol=1e-8, precond=True, cap=512):
+        """sgpu_eigs_LOBPCG on the block vector X (anything with .ptr and .K; start vectors in, eigenvectors out)
+        -> (lambda[K], res[K], iterations, [history of column j], converged)"""
+        K = X.K
+        lam, res, it = np.full(K, np.nan), np.full(K, np.nan), C.c_int()
+        hist = np.full((K, cap), np.nan)
+        st = lib().sgpu_eigs_LOBPCG(self.h, X.ptr, K, int(nev), int(max_iter), float(tol), 1 if precond else 0, lam.ctypes.data_as(_PD),
+                                    res.ctypes.data_as(_PD), C.byref(it), hist.ctypes.data_as(_PD), cap)
+        if st not in (0, -6):
+            check(st)
+        return lam, res, it.value, [h[~np.isnan(h)] for h in hist], st == 0
+
+    # the LOBPCG launch helpers on the caller's device vectors (sgpu_debug_block_gram / _block_mix / _eig_residual)
+    def debug_block_gram(self, X, Y, n, K, out):
+        check(lib().sgpu_debug_block_gram(self.h, X.ptr, Y.ptr, int(n), int(K), out.ptr))
+
+    def debug_eig_residual(self, AX, X, lam, R, n, K, rr):
+        check(lib().sgpu_debug_eig_residual(self.h, AX.ptr, X.ptr, lam.ptr, R.ptr, int(n), int(K), rr.ptr))
+
+    def debug_eig_stop(self, K, iteration):
+        check(lib().sgpu_debug_eig_stop(self.h, int(K), int(iteration)))
+
+    def debug_eig_vector(self, K, which, dst):
+        check(lib().sgpu_debug_eig_vector(self.h, int(K), int(which), dst.ptr))
+
+    def time_eig(self, kind, ns, X, Y, Out, n, K, reps):
+        ms = C.c_float()
+        check(lib().sgpu_debug_time_eig(self.h, int(kind), int(ns), X.ptr, Y.ptr, Out.ptr, int(n), int(K), int(reps), C.byref(ms)))
+        return ms.value
+
     def set_solve_params(self, max_iter, tol, smoother, pre, post):
         check(lib().sgpu_amg_set_solve_params(self.h, int(max_iter), float(tol), 0 if smoother == "jacobi" else 1, int(pre), int(post)))
 
@@ -653,6 +690,16 @@ def time_gs(kind, V, ld, ncols, w, n, reps):
     ms = C.c_float()
     check(lib().sgpu_debug_time_gs(int(kind), V.ptr, int(ld), int(ncols), w.ptr, int(n), int(reps), C.byref(ms)))
     return ms.value
+
+
+def block_mix(K, sources, coefs, out, n, add=None):
+    """out = sum_s sources[s] coefs[s] (+ add) on block vectors of n rows (sgpu_debug_block_mix); 1 to 3 sources, coefs: device, K x K"""
+    ns = len(sources)
+    assert ns == len(coefs) and 1 <= ns <= 3
+    p = []
+    for s in range(3):
+        p += [sources[s].ptr, coefs[s].ptr] if s < ns else [None, None]
+    check(lib().sgpu_debug_block_mix(int(K), ns, *p, add.ptr if add is not None else None, out.ptr, int(n)))
 
 
 def launch_count():

@@ -1,0 +1,49 @@
+// eigs_device.h -- what saena_amg_eigs (saena_c_api.cpp) and saena::amg::eigs (saena.cpp) share: the default start vectors and the
+// trip of column-major host arrays through sgpu_eigs_LOBPCG.
+#pragma once
+#include "../../../include/saena_gpu.h"
+
+#include <cstddef>
+#include <vector>
+
+namespace saena_host {
+
+// out: column-major n x K; column j is find_eig's LCG sequence over the row index, in (-1, 1), from a seed of its own
+inline void default_eig_start(size_t n, int K, value_t *out) {
+    for (int j = 0; j < K; ++j) {
+        unsigned long long lcg = 88172645463325252ULL + 0x9E3779B97F4A7C15ULL * (unsigned long long)j;
+        for (size_t i = 0; i < n; ++i) {
+            lcg = lcg * 6364136223846793005ULL + 1442695040888963407ULL;
+            out[(size_t)j * n + i] = ((lcg >> 11) * (1.0 / 9007199254740992.0)) * 2.0 - 1.0;
+        }
+    }
+}
+
+#ifdef SAENA_WITH_GPU
+// x0_host (column-major n x K, or null for the default start) up, packed into a block vector, sgpu_eigs_LOBPCG, and the eigenvectors
+// back into x_host the same way.  -> the sgpu status (SGPU_ERR_NOCONV: the outputs are written all the same; sgpu_last_error has the text)
+inline int eigs_host_arrays(sgpu_amg *h, size_t n, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
+                            value_t *lambda, value_t *x_host, value_t *res, int *iters) {
+    std::vector<value_t> start;
+    if (!x0_host) {
+        start.resize(n * (size_t)K);
+        default_eig_start(n, K, start.data());
+        x0_host = start.data();
+    }
+    value_t *cm = nullptr, *x = nullptr;
+    int s = sgpu_vec_alloc(&cm, n * K);
+    if (s == SGPU_OK) s = sgpu_vec_alloc(&x, n * K);
+    if (s == SGPU_OK) s = sgpu_vec_upload(cm, x0_host, n * K);
+    if (s == SGPU_OK) s = sgpu_block_pack(cm, x, n, K);
+    if (s == SGPU_OK) s = sgpu_eigs_LOBPCG(h, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0);
+    if (s == SGPU_OK || s == SGPU_ERR_NOCONV) {
+        int s2 = sgpu_block_unpack(x, cm, n, K);
+        if (s2 == SGPU_OK) s2 = sgpu_vec_download(x_host, cm, n * K);
+        if (s2 != SGPU_OK) s = s2;
+    }
+    sgpu_vec_free(cm); sgpu_vec_free(x);
+    return s;
+}
+#endif
+
+} // namespace saena_host

@@ -7,6 +7,7 @@
 #include "comm.h"
 #include "amg_setup.h"
 #include "saena_matrix.h"
+#include "eigs_device.h"
 
 #include <algorithm>
 #include <chrono>
@@ -399,6 +400,24 @@ int amg::solve_pCG_block(value_t *&u, saena::options *opts) {
     if (st2 == SGPU_OK) st2 = sgpu_vec_download(u, cm, n * K);
     release();
     gchk(st2, "download");
+    return st == SGPU_OK ? 0 : 1;
+}
+int amg::eigs(value_t *&x, std::vector<value_t> &lambda, saena::options *opts, int K, int nev, const value_t *x0, bool precondition) {
+    if (!damg_) throw std::runtime_error("saena::amg: set_matrix first");
+    if (K != 2 && K != 4 && K != 8) throw std::runtime_error("saena::amg::eigs: a block holds 2, 4 or 8 vectors");
+    const size_t n = (size_t)A_->get_num_local_rows(), nK = n * (size_t)K;
+    int max_iter = 100;
+    double tol = 1e-8;
+    if (opts) {
+        gchk(sgpu_amg_set_solve_params(damg_, opts->get_max_iter(), opts->get_tol(), opts->get_smoother() == "jacobi" ? 0 : 1,
+                                       opts->get_preSmooth(), opts->get_postSmooth()), "set_solve_params");
+        max_iter = opts->get_max_iter(); tol = opts->get_tol();
+    }
+    lambda.assign((size_t)K, 0.0);
+    eig_res_.assign((size_t)K, 0.0);
+    if (!x) x = static_cast<value_t *>(std::malloc(std::max<size_t>(1, nK) * sizeof(value_t)));
+    const int st = saena_host::eigs_host_arrays(damg_, n, x0, K, nev, max_iter, tol, precondition ? 1 : 0, lambda.data(), x, eig_res_.data(), &iters_);
+    if (st != SGPU_OK && st != SGPU_ERR_NOCONV) gchk(st, "eigs");
     return st == SGPU_OK ? 0 : 1;
 }
 int amg::set_scale(bool sc) {

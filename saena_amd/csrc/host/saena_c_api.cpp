@@ -3,11 +3,13 @@
 #include "saena_matrix.h"
 #include "amg_setup.h"
 #include "shm_comm.h"
+#include "eigs_device.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <memory>
 #include <string>
+#include <vector>
 
 using namespace saena_host;
 
@@ -323,6 +325,7 @@ int saena_amg_solve(saena_amg_h *, const value_t *, value_t *, int *, value_t *,
 int saena_amg_solve_pCG(saena_amg_h *, const value_t *, value_t *, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_solve_pCG_block(saena_amg_h *, const value_t *, value_t *, int, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_solve_pFGMRES(saena_amg_h *, const value_t *, value_t *, int, int, int *, value_t *, int) { return no_gpu(); }
+int saena_amg_eigs(saena_amg_h *, const value_t *, int, int, int, value_t, int, value_t *, value_t *, value_t *, int *) { return no_gpu(); }
 #else
 static int gchk(int s) { if (s != 0) { h_err = sgpu_last_error(); } return s; }
 static void drop_device(saena_amg_h *S) {
@@ -423,6 +426,16 @@ int saena_amg_solve_pFGMRES(saena_amg_h *S, const value_t *rhs_host, value_t *u_
     if (s == 0 || s == SGPU_ERR_NOCONV) s2 = gchk(sgpu_vec_download(u_host, u, n));
     sgpu_vec_free(u); sgpu_vec_free(rhs);
     return s ? s : s2;
+}
+
+// sgpu_eigs_LOBPCG on column-major host arrays (host/eigs_device.h, shared with saena::amg::eigs)
+int saena_amg_eigs(saena_amg_h *S, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda,
+                   value_t *x_host, value_t *res, int *iters) {
+    if (!S->damg) { h_err = "saena_amg_to_device has not been called"; return -1; }
+    if (K != 2 && K != 4 && K != 8) { h_err = "saena_amg_eigs: a block holds 2, 4 or 8 columns"; return -1; }
+    if (!lambda || !x_host) { h_err = "saena_amg_eigs: null argument"; return -1; }
+    const size_t n = S->H.dist.empty() ? (size_t)S->H.levels[0].A->M : (size_t)S->H.dist[0].A.M;
+    return gchk(eigs_host_arrays(S->damg, n, x0_host, K, nev, max_iter, tol, precond, lambda, x_host, res, iters));
 }
 #endif
 

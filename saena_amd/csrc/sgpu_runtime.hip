@@ -10,6 +10,8 @@
 #include "kernels.hip.h"
 #include "kernels_block.hip.h"
 #include "kernels_gmres.hip.h"
+#include "kernels_eig.hip.h"
+#include "host/dense_eig.h"
 #include "host/comm.h"
 #include "host/par.h"
 #include "host/amg_setup.h"
@@ -3260,6 +3262,30 @@ struct AmgGmres {
     }
 };
 
+// LOBPCG state of a hierarchy for ONE K (sgpu_eig.hip.inc): made at the first sgpu_eigs_LOBPCG with that K
+struct AmgEig {
+    int K = 0;
+    double *AX = nullptr, *R = nullptr, *W = nullptr, *AW = nullptr, *P = nullptr, *AP = nullptr;   // block vectors (X is the caller's)
+    double *gpart = nullptr, *rpart = nullptr;       // partial sums: 12 Gram blocks [n_partials][K*K] each; the residual norms [n_partials][K]
+    double *coef = nullptr;                          // device: 3 K*K mix coefficients | K lambda | K ||r_j||^2 | 12 Gram blocks of K*K
+    double *hmix = nullptr, *hlam = nullptr, *hdown = nullptr;   // pinned: what goes up (coefficients, lambda), what comes down (norms, Gram blocks)
+    hipGraph_t graph = nullptr;                      // the block V-cycle on (W, R) from a zero iterate, captured once
+    hipGraphExec_t exec = nullptr;
+    uint64_t graph_gen = 0, block_gen = 0;
+    int debug_stop = -1;                             // sgpu_debug_eig_stop: the iteration a test wants to look into
+    void drop_graph() {
+        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
+        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
+    }
+    ~AmgEig() {
+        drop_graph();
+        hipFree(AX); hipFree(R); hipFree(W); hipFree(AW); hipFree(P); hipFree(AP); hipFree(gpart); hipFree(rpart); hipFree(coef);
+        if (hmix) hipHostFree(hmix);
+        if (hlam) hipHostFree(hlam);
+        if (hdown) hipHostFree(hdown);
+    }
+};
+
 struct sgpu_amg {
     int nlevels = 0;
     std::vector<sgpu_op *> A, P, R;
@@ -3296,9 +3322,11 @@ struct sgpu_amg {
     bool coarse_host_driven = false;   // coarsest level too large for the LDS-resident solvers: host-driven CG, no graph capture
     std::unique_ptr<AmgBlock> blk[3];  // K = 2, 4, 8
     std::unique_ptr<AmgGmres> gm;      // sgpu_solve_FGMRES
+    std::unique_ptr<AmgEig> eigs[3];   // sgpu_eigs_LOBPCG, K = 2, 4, 8
     void drop_graphs() {
         for (auto &b : blk) if (b) b->drop_graphs();
         if (gm) gm->drop_graph();
+        for (auto &e : eigs) if (e) e->drop_graph();
         for (auto &c : graphs) { hipGraphExecDestroy(c.exec); hipGraphDestroy(c.graph); }
         graphs.clear();
         if (tail_exec) { hipGraphExecDestroy(tail_exec); tail_exec = nullptr; }
@@ -3889,6 +3917,7 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 
 #include "sgpu_block.hip.inc"
 #include "sgpu_gmres.hip.inc"
+#include "sgpu_eig.hip.inc"
 
 // ===========================================================================
 // Setup-time collectives of the host layer over the same RCCL communicator

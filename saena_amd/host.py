@@ -99,6 +99,9 @@ HOST_SYMBOLS.update({
     "saena_amg_solve_pCG": (C.c_int, [_VP, _PD, _PD, _PI, _PD, C.c_int]),
     "saena_amg_solve_pCG_block": (C.c_int, [_VP, _PD, _PD, C.c_int, _PI, _PD, C.c_int]),
     "saena_amg_solve_pFGMRES": (C.c_int, [_VP, _PD, _PD, C.c_int, C.c_int, _PI, _PD, C.c_int]),
+    "saena_amg_eigs": (C.c_int, [_VP, _PD, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PD, _PI]),
+    "saena_debug_sym_geig": (C.c_int, [C.c_int, _PD, _PD, _PD, _PD]),
+    "saena_debug_sym_geig_sweeps": (C.c_int, []),
 })
 
 _libs = {}
@@ -118,6 +121,16 @@ def load(which="host"):
             fn.restype, fn.argtypes = res, args
         _libs[which] = L
     return _libs[which]
+
+
+def sym_geig(A, B, which="host"):
+    """A v = w B v through saena_debug_sym_geig -> (status, w, V (columns = vectors), Jacobi sweeps)"""
+    L = load(which)
+    A, B = _ad(A), _ad(B)
+    n = A.shape[0]
+    w, V = np.full(n, np.nan), np.full((n, n), np.nan)
+    st = L.saena_debug_sym_geig(n, A.ctypes.data_as(_PD), B.ctypes.data_as(_PD), w.ctypes.data_as(_PD), V.ctypes.data_as(_PD))
+    return st, w, V, L.saena_debug_sym_geig_sweeps()
 
 
 def _ai(a):
@@ -540,6 +553,23 @@ class AmgSolver:
         if st not in (0, -6):
             _check(self.L, st)
         return u, [int(v) for v in it], [h[~np.isnan(h)] for h in hist], st == 0
+
+    def eigs(self, K, nev, x0=None, max_iter=100, tol=1e-8, precond=True):
+        """the nev smallest eigenpairs by LOBPCG on K = 2, 4 or 8 vectors (saena_amg_eigs); x0: (n, K) start vectors or None for the
+        default start -> (lambda[K], X (n, K), res[K], iterations, converged)"""
+        n = self.A.num_local_rows
+        p0 = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, np.float64)
+            assert x0.shape == (n, K), x0.shape
+            p0 = x0.ctypes.data_as(_PD)
+        X = np.zeros((n, K), order="F")
+        lam, res, it = np.full(K, np.nan), np.full(K, np.nan), C.c_int()
+        st = self.L.saena_amg_eigs(self.h, p0, int(K), int(nev), int(max_iter), float(tol), 1 if precond else 0, lam.ctypes.data_as(_PD),
+                                   X.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it))
+        if st not in (0, -6):
+            _check(self.L, st)
+        return lam, X, res, it.value, st == 0
 
     def free(self):
         if self.h:
