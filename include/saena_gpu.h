@@ -148,11 +148,21 @@ int sgpu_op_set_lanes_per_row(sgpu_op *op, int lanes);
  * dictionary per workgroup of 256 rows -- 1 B per entry instead of 8, the same products and row sums (operators that qualify for
  * 11 with ONE pattern table and hold at most 256 distinct values, as bit patterns, in every group of 256 rows: constant-
  * coefficient stencils and their level-0 transfers; "k_vidx<rowbase>" on the rowbase table; SAENA_NO_VALUE_INDEX=1 keeps it
- * out of the autotune).
- * 12 and 13 are built from a host copy of the values that the library keeps only until the plan-time autotune
+ * out of the autotune).  Variant 17 has a second LAUNCH MODE, sgpu_op_set_x_windows below: the same stored operator, x gathered
+ * from LDS windows; sgpu_op_set_variant(17) alone selects direct gathers and both modes report 17, "k_vidx".
+ * Only 12 and 13 still depend on the host copy of the values, which the library keeps only until the plan-time autotune
  * (SGPU_ERR_ARG afterwards); every form returns SGPU_ERR_ARG where it does not apply */
 int sgpu_op_set_variant(sgpu_op *op, int variant);
 int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_name);
+/* x-window launch mode of variant 17 (k_vidxw): a workgroup of rows_per_workgroup in {256, 512, 1024} consecutive rows loads the
+ * few windows of x its rows reach ONCE into LDS and gathers from there (the 7-point level: three windows instead of seven loads
+ * per row); 0 turns it off (direct gathers).  Results are bit-identical in both modes.  SGPU_ERR_ARG, with a message that names
+ * the "x windows", where the mode does not apply -- the operator is not on variant 17, rowbase or per-workgroup pattern tables,
+ * more than 16 windows, LDS positions beyond 16 bits, more than 64 KiB of LDS -- and the operator stays as it was.  The autotune
+ * times the mode next to direct gathers wherever it offers 17 (SAENA_NO_X_WINDOWS=1 leaves it out) and the plan cache remembers it.
+ * sgpu_op_get_x_windows: the rows per workgroup in use, 0 = direct gathers (or another variant). */
+int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup);
+int sgpu_op_get_x_windows(const sgpu_op *op, int *rows_per_workgroup);
 /* time the (variant, lanes) candidates that apply to this operator and keep the fastest (plan-time autotune; no
  * collective).  Call it right after sgpu_op_create: operators of up to 768 entries per row hold a host copy of their
  * values (8 B per entry) for the re-ordered forms from the create until this call -- or until sgpu_op_destroy. */

@@ -69,6 +69,8 @@ SYMBOLS = {
     "sgpu_op_set_variant": (C.c_int, [_VP, C.c_int]),
     "sgpu_op_autotune": (C.c_int, [_VP]),
     "sgpu_op_get_variant": (C.c_int, [_VP, _PI, C.POINTER(C.c_char_p)]),
+    "sgpu_op_set_x_windows": (C.c_int, [_VP, C.c_int]),
+    "sgpu_op_get_x_windows": (C.c_int, [_VP, _PI]),
     "sgpu_spmv": (C.c_int, [_VP, _VP, _VP]),
     "sgpu_residual": (C.c_int, [_VP, _VP, _VP, _VP]),
     "sgpu_residual_negative": (C.c_int, [_VP, _VP, _VP, _VP]),
@@ -397,6 +399,16 @@ class Operator:
 
     def set_variant(self, variant):
         check(lib().sgpu_op_set_variant(self.h, int(variant)))
+
+    def set_x_windows(self, rows_per_workgroup):
+        """x-window launch mode of variant 17: 256 / 512 / 1024 rows per workgroup, 0 = direct gathers; raises where it is refused"""
+        check(lib().sgpu_op_set_x_windows(self.h, int(rows_per_workgroup)))
+
+    def x_windows(self):
+        """rows per workgroup of the x-window mode in use, 0 = direct gathers"""
+        v = C.c_int()
+        check(lib().sgpu_op_get_x_windows(self.h, C.byref(v)))
+        return v.value
 
     def spmv(self, v, w):
         check(lib().sgpu_spmv(self.h, v.ptr, w.ptr))

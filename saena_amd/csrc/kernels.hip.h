@@ -861,6 +861,135 @@ __global__ __launch_bounds__(BLOCK) void k_vidx(const SpmvArgs a, int nrows) {
     if (r < nrows) epilogue<EPI, HALO, NT>(a, r, sum);
 }
 
+// K1v with x windows (a launch mode of variant 17, not a form of its own: the stored operator -- codes, dictionaries, pattern ids --
+// is k_vidx's).  k_vidx requests x seven times per row of the 7-point level although every element is stored once; a workgroup of
+// R consecutive rows reads x only inside a few windows [r0 + omin_c, r0 + R + omax_c) (k_sellpx's clusters, the gap rule at R), which
+// it loads ONCE with coalesced loads and gathers from LDS: 8 (3 R + 2 n) / R bytes of x per row instead of 56.
+// Every global load of a workgroup is issued before its ONE barrier: codes, pattern id, the epilogue's operands (Jacobi / residual,
+// as k_sellp2<PRE>), then windows, dictionaries and table -- k_vidx's chain of three dependent round trips becomes one.
+// blockDim.x = R in {256, 512, 1024}, a lane per row; dynamic LDS: [windows of x][R / 256 dictionaries of VI_MAX][table].
+// a.segtab: nwin, S (doubles of x in LDS), then per window (LDS base, omin - base), at least four (unused: base INT32_MAX); a.ptab: the table as 16-bit words -- the patterns'
+// lengths (padded to a multiple of 8), then per pattern pt_w (a multiple of 8) LDS positions for the workgroup's first row, the
+// tail repeating the last one; a.vcode / a.vcptr / a.uw / a.vdict / a.vdptr / a.dst: k_vidx's.
+// Same products, same sequential row sum: bit-identical to k_vidx and k_sellp.
+constexpr int VW_MAX_LDS = 64 * 1024;          // windows + dictionaries + table: at least two workgroups per CU
+typedef unsigned sk_u4v __attribute__((ext_vector_type(4)));
+template <int EPI, bool HALO, bool NT>
+__global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, int nrows) {
+    extern __shared__ __attribute__((aligned(16))) double vw_lds[];
+    if constexpr (HALO) fork_signal(a);
+    // (the kernel is bound by instruction issue on the cache-resident level, not by bytes: no division, no branch per position or
+    //  per staged element -- clamped addresses and selects instead)
+    const int R = (int)blockDim.x, sh = __builtin_ctz((unsigned)R) - 6, D = R >> 8;     // rows, log2(slices) and dictionaries per workgroup
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int b = xcd_remap(blockIdx.x, (a.nblk + (1 << sh) - 1) >> sh);
+    const int r0 = b * R;
+    const int s = __builtin_amdgcn_readfirstlane((b << sh) + (tid >> 6));
+    const bool live = s < a.nblk;                                  // (the last workgroup's spare waves still stage and meet the barrier)
+    const int r = r0 + tid;
+    const bool row = r < nrows;                                    // (only inside live slices)
+    const int rc = row ? r : 0;                                    // a valid row for the loads of a lane without one
+    // ---- 1. every global load of the lane
+    int cp = 0, w8 = 0;
+    if (live) {
+        if (a.uw) { w8 = a.uw; cp = s * w8 * 64; }
+        else { cp = a.vcptr[s]; w8 = (a.vcptr[s + 1] - cp) >> 6; }
+    }
+    const bool ntv = NT && s >= a.nt_from;
+    const sk_u2v *c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp) + lane;
+    auto ld_codes = [&](int j) { sk_u2v v; if (ntv) v = __builtin_nontemporal_load(c8 + (j >> 3) * 64); else v = c8[(j >> 3) * 64]; return v; };
+    sk_u2v cc = {0u, 0u};
+    if (w8 > 0) cc = ld_codes(0);
+    int pid;
+    if constexpr (NT) pid = __builtin_nontemporal_load(a.dst + rc); else pid = a.dst[rc];
+    constexpr bool PREF = !HALO && (EPI == EPI_JACOBI || EPI == EPI_RESIDUAL);
+    double pre_b = 0.0, pre_dg = 0.0, pre_u = 0.0;
+    if constexpr (PREF) {
+        pre_b = ld_once<NT>(a.rhs + rc);
+        if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(a.inv_diag + rc); pre_u = a.u[rc]; }
+    }
+    const sk_i4v w0 = *reinterpret_cast<const sk_i4v *>(a.segtab), w1 = *reinterpret_cast<const sk_i4v *>(a.segtab + 4);
+    const int b3 = a.segtab[8], e3 = a.segtab[9];
+    const int nwin = w0.x, S = w0.y;                               // (w0.z = 0: the first window's base)
+    const int ngd = (a.nblk + 3) >> 2;                             // dictionaries of the operator
+    const int d0 = a.vdptr[b * D], dn = a.vdptr[b * D + D < ngd ? b * D + D : ngd] - d0;      // this workgroup's, contiguous: dn <= D * VI_MAX = R
+    const int dw0 = live ? a.vdptr[s >> 2] - d0 : 0;               // where this wave's own begins
+    double *xw = vw_lds, *dict = vw_lds + ((S + 2) & ~1);          // (xw[S]: a spare slot for the staging lanes past the windows)
+    unsigned short *tab = reinterpret_cast<unsigned short *>(dict + D * VI_MAX);
+    const int lp = (a.pt_n + 7) & ~7, tn = lp + a.pt_n * a.pt_w;   // 16-bit words of the table, a multiple of 8
+    // ---- 2. windows (zero where they leave the vector), dictionaries, table -> LDS
+    const int xlast = a.ncols - 1;
+    auto stage4 = [&](int i0) {                                    // four elements per lane: all loads, then all LDS writes
+        int    ii[4], dd[4];
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            ii[u] = i0 + u * R + tid;
+            dd[u] = w0.w;                                          // the last window that begins at or before the element (unused ones: base INT32_MAX)
+            dd[u] = ii[u] >= w1.x ? w1.y : dd[u];
+            dd[u] = ii[u] >= w1.z ? w1.w : dd[u];
+            dd[u] = ii[u] >= b3 ? e3 : dd[u];
+        }
+        for (int c = 4; c < nwin; ++c) {
+            const int bc = a.segtab[2 + 2 * c], dc = a.segtab[3 + 2 * c];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (ii[u] >= bc) dd[u] = dc;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int col = r0 + ii[u] + dd[u], colc = col < 0 ? 0 : col > xlast ? xlast : col;
+            v[u] = a.x[colc];
+            if (col != colc) v[u] = 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) xw[ii[u] < S ? ii[u] : S] = v[u];
+    };
+    stage4(0);
+    for (int i0 = 4 * R; i0 < S; i0 += 4 * R) stage4(i0);
+    if (tid < dn) dict[tid] = a.vdict[d0 + tid];
+    {
+        const sk_u4v *gt = reinterpret_cast<const sk_u4v *>(a.ptab);
+        sk_u4v *lt = reinterpret_cast<sk_u4v *>(tab);
+        for (int i = tid; i < (tn >> 3); i += R) lt[i] = gt[i];
+    }
+    __syncthreads();
+    if (!live) return;
+    // ---- 3. the row: dictionary value x window entry, in the table's order
+    if (!row) pid = 0;
+    const int len = row ? (int)tab[pid] : 0;
+    const unsigned short *pos = tab + lp + pid * a.pt_w;
+    const double *xr = xw + tid, *dw = dict + dw0;
+    double sum = 0.0;
+    for (int j = 0; j < w8; j += 8) {                              // (w8 <= pt_w: no row is longer than the longest pattern)
+        const sk_u4v pp = *reinterpret_cast<const sk_u4v *>(pos + j);
+        sk_u2v cn = cc;
+        if (j + 8 < w8) cn = ld_codes(j + 8);
+        double xx[8], dv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const unsigned w = u < 2 ? pp.x : u < 4 ? pp.y : u < 6 ? pp.z : pp.w;
+            xx[u] = xr[(u & 1) ? (w >> 16) : (w & 0xffffu)];
+            dv[u] = dw[((u < 4 ? cc.x : cc.y) >> (8 * (u & 3))) & 0xffu];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {                              // a position past the row's length adds -0.0, which changes no sum (signed zeros
+            const double p = dv[u] * xx[u];                        // and NaNs included): the row sum stays k_vidx's, bit for bit, without a branch
+            sum += j + u < len ? p : -0.0;
+        }
+        cc = cn;
+    }
+    if (row) {
+        if constexpr (PREF) {                                      // epilogue<>'s arithmetic on the operands fetched at the top
+            if constexpr (EPI == EPI_RESIDUAL) st_y<NT>(a, a.y + r, sum - pre_b);
+            else {
+                double t = sum - pre_b;
+                t *= pre_dg * a.c0;
+                st_y<NT>(a, a.y + r, pre_u - t);
+            }
+        } else epilogue<EPI, HALO, NT>(a, r, sum);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // K1x: k_sellp with THE INPUT VECTOR IN LDS.  On the first smoothed-aggregation level (68 entries per row) k_sellp<WIDE> is bound
 // by the load path, not by bytes: for every 8 B of the value stream it gathers 8 B of x, and the two together pass the CU's

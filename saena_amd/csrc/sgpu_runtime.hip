@@ -187,7 +187,22 @@ struct CsrPart {
     int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
     bool            vi_ok = false;
     char            vi_tried = 0;
+    // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
+    // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS positions; vw_rows: the R in
+    // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays, kept and freed with them
+    struct XWin { unsigned short *tab = nullptr; int *win = nullptr; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
+    XWin            vw[3];
+    int             vw_rows = 0;
+    void free_xwin(int keep_rows = 0) {
+        for (int k = 0; k < 3; ++k) {
+            if ((256 << k) == keep_rows) continue;
+            hipFree(vw[k].tab); hipFree(vw[k].win);
+            vw[k] = XWin();
+        }
+        if (vw_rows != keep_rows) vw_rows = 0;
+    }
     void free_vidx() {
+        free_xwin();
         hipFree(vi_code); hipFree(vi_cptr); hipFree(vi_dptr); hipFree(vi_dict);
         vi_code = nullptr; vi_cptr = vi_dptr = nullptr; vi_dict = nullptr; vi_ok = false; vi_tried = 0;
     }
@@ -1174,6 +1189,75 @@ int build_vidx(CsrPart &P) {
     return SGPU_OK;
 }
 
+// The x-window launch mode of k_vidx for workgroups of R = 256 << k rows: build_sellp's ONE pattern table (read back from the
+// device -- the host copy goes when the plan settles), its offsets clustered as build_sellpx does with the gap rule at R, the
+// windows [r0 + omin_c, r0 + R + omax_c) laid out one after the other, and the table rewritten ONCE for the whole operator as
+// 16-bit LDS positions for a workgroup's first row.  Refused (ok stays false, *why says it): rowbase and per-workgroup tables,
+// more than SPX_MAXWIN windows, positions beyond 16 bits, more LDS than VW_MAX_LDS (two workgroups per CU).
+int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
+    CsrPart::XWin &X = P.vw[k];
+    const int R = 256 << k;
+    auto no = [&](const char *m) { if (why) *why = m; return SGPU_OK; };
+    if (X.ok) return SGPU_OK;
+    if (!P.vi_ok || !P.sp_ok || !P.sp_tab) return no("the value-indexed form was not built");
+    if (P.sp_rbase) return no("the patterns are relative to the rows' first columns (rowbase)");
+    if (P.sp_wide) return no("the patterns sit in per-workgroup tables");
+    if (X.tried) return no("refused before");
+    X.tried = 1;
+    const int npat = P.sp_n, W = P.sp_w, M = P.nrows;
+    if (npat <= 0 || W <= 0) return no("no patterns");
+    std::vector<int> tab((size_t)npat * (W + 1));
+    HIPCHK(hipMemcpyAsync(tab.data(), P.sp_tab, tab.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
+    HIPCHK(hipStreamSynchronize(g.cs));
+    std::vector<int> offs;
+    for (int i = 0; i < npat; ++i) {
+        const int *c = &tab[(size_t)i * (W + 1)];
+        if (c[0] < 0 || c[0] > W) return no("a pattern longer than the table's width");
+        offs.insert(offs.end(), c + 1, c + 1 + c[0]);
+    }
+    std::sort(offs.begin(), offs.end());
+    offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
+    if (offs.empty()) return no("no entries");
+    std::vector<int> omin, omax, base;
+    for (size_t i = 0; i < offs.size(); ++i) {
+        if (i == 0 || (int64_t)offs[i] - offs[i - 1] > R) { omin.push_back(offs[i]); omax.push_back(offs[i]); }
+        else omax.back() = offs[i];
+    }
+    const int nwin = (int)omin.size();
+    if (nwin > sk::SPX_MAXWIN) return no("more windows than SPX_MAXWIN");
+    int64_t S = 0;
+    for (int c = 0; c < nwin; ++c) { base.push_back((int)S); S += (int64_t)R + ((int64_t)omax[(size_t)c] - omin[(size_t)c]); if (S > 65536) return no("LDS positions beyond 16 bits"); }
+    if ((int64_t)M + R + S + std::max<int64_t>(std::abs((int64_t)offs.front()), std::abs((int64_t)offs.back())) > (int64_t)INT32_MAX - 8) return no("column arithmetic beyond 32 bits");
+    const int wp = (W + 7) & ~7, lp = (npat + 7) & ~7;
+    if (P.vi_uw8 > wp) return no("slices wider than the table");
+    const int64_t words = (int64_t)lp + (int64_t)npat * wp;
+    const int64_t lds = ((S + 2) & ~(int64_t)1) * 8 + (int64_t)(R / sk::BLOCK) * sk::VI_MAX * 8 + words * 2;
+    if (lds > (int64_t)sk::VW_MAX_LDS) return no("windows, dictionaries and table exceed the LDS cap");
+    std::vector<unsigned short> t16((size_t)words, 0);
+    for (int i = 0; i < npat; ++i) {
+        const int *c = &tab[(size_t)i * (W + 1)];
+        t16[(size_t)i] = (unsigned short)c[0];
+        unsigned short last = 0;                                  // (an empty row reads position 0 and adds nothing)
+        for (int j = 0; j < wp; ++j) {
+            if (j < c[0]) {
+                const int w = (int)(std::upper_bound(omin.begin(), omin.end(), c[1 + j]) - omin.begin()) - 1;      // the window that holds the offset
+                last = (unsigned short)(base[(size_t)w] + (c[1 + j] - omin[(size_t)w]));
+            }
+            t16[(size_t)lp + (size_t)i * wp + j] = last;        // (the tail repeats the last position: read, never added)
+        }
+    }
+    std::vector<int> win(2 + 2 * (size_t)std::max(nwin, 4), INT32_MAX);          // (the kernel reads the first four windows unconditionally: unused ones never match)
+    win[0] = nwin; win[1] = (int)S;
+    for (int c = 0; c < nwin; ++c) { win[2 + 2 * (size_t)c] = base[(size_t)c]; win[3 + 2 * (size_t)c] = omin[(size_t)c] - base[(size_t)c]; }
+    CHK(dev_upload(&X.tab, t16.data(), t16.size(), 8));
+    CHK(dev_upload(&X.win, win.data(), win.size()));
+    X.wp = wp; X.lds = (int)lds; X.ok = true;
+    if (std::getenv("SAENA_SETUP_TIMING"))
+        fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row)\n",
+                R, nwin, (long long)S, R / sk::BLOCK, (long long)words, (double)lds / 1024.0, 8.0 * (double)S / R);
+    return SGPU_OK;
+}
+
 // The row-paired values of k_sellp2 on top of build_sellp's pattern ids: slices of 128 rows, a slice padded to its longest
 // row, position-major with the values of rows 2 l and 2 l + 1 side by side.
 int build_sellp2(CsrPart &P, const std::vector<double> &h_val_all) {
@@ -1567,6 +1651,19 @@ SellKernelFn pick_vidx_h(int epi) {
     }
 }
 SellKernelFn pick_vidx(int epi, bool halo, bool nt) { return halo ? (nt ? pick_vidx_h<true, true>(epi) : pick_vidx_h<true, false>(epi)) : (nt ? pick_vidx_h<false, true>(epi) : pick_vidx_h<false, false>(epi)); }
+template <bool HALO, bool NT>
+SellKernelFn pick_vidxw_h(int epi) {
+    switch (epi) {
+        case sk::EPI_SPMV:     return sk::k_vidxw<sk::EPI_SPMV, HALO, NT>;
+        case sk::EPI_RESIDUAL: return sk::k_vidxw<sk::EPI_RESIDUAL, HALO, NT>;
+        case sk::EPI_JACOBI:   return sk::k_vidxw<sk::EPI_JACOBI, HALO, NT>;
+        case sk::EPI_CHEBY0:   return sk::k_vidxw<sk::EPI_CHEBY0, HALO, NT>;
+        case sk::EPI_CHEBYK:   return sk::k_vidxw<sk::EPI_CHEBYK, HALO, NT>;
+        case sk::EPI_RSWEEP:   return sk::k_vidxw<sk::EPI_RSWEEP, HALO, NT>;
+        default:               return sk::k_vidxw<sk::EPI_SUB, HALO, NT>;
+    }
+}
+SellKernelFn pick_vidxw(int epi, bool halo, bool nt) { return halo ? (nt ? pick_vidxw_h<true, true>(epi) : pick_vidxw_h<true, false>(epi)) : (nt ? pick_vidxw_h<false, true>(epi) : pick_vidxw_h<false, false>(epi)); }
 template <bool HALO, bool PAIR, bool NT>
 SellKernelFn pick_sellpx_h(int epi) {
     switch (epi) {
@@ -1698,6 +1795,13 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         const bool nt = nt_envv >= 0 ? nt_envv != 0 : P.vi_bytes > (int64_t)256 * 1024 * 1024;
         a.nt_from = nt ? resident_slices(a.nblk, (double)P.nnz / (double)std::max(1, a.nblk)) : 0;     // (about a byte of codes per entry)
         const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
+        if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS positions
+            const int k = P.vw_rows == 256 ? 0 : P.vw_rows == 512 ? 1 : 2, spb = P.vw_rows / 64;
+            const CsrPart::XWin &X = P.vw[k];
+            if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
+            a.ptab = reinterpret_cast<const int *>(X.tab); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
+            SGPU_LAUNCH(pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, P.nrows);
+        } else
         SGPU_LAUNCH(pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
     } else if (P.variant == 15) {                                 // k_sellp with x in LDS windows
         if (!P.spx_ok || !P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
@@ -2560,6 +2664,9 @@ int sgpu_op_set_lanes_per_row(sgpu_op *op, int lanes) {
 // the kernel forms, by number: ONE table, whose length is what set_variant, the plan cache's lookup and its store accept
 static const char *const VARIANT_NAMES[] = {"k_csr_stream<16KiB>", "k_csr_stream<32KiB>", "k_csr_vector", "k_csr_cc16<16KiB>", "k_csr_cc16<32KiB>", "k_dense_rows", "k_csr_wave", "k_csr_cm<16KiB>", "k_csr_cm<32KiB>", "k_sell", "k_csr_xlds", "k_sellp", "k_sellx", "k_rowt", "k_sellp2", "k_sellpx", "k_csr_xldsr", "k_vidx"};   // (3, 4, 7, 8 are named with their slot/offset split below)
 static constexpr int MAX_VARIANT = (int)(sizeof VARIANT_NAMES / sizeof VARIANT_NAMES[0]) - 1;
+// the workgroup sizes (256 << k rows) at which the autotune times the x-window mode of variant 17: 256 rows win on the cache-resident
+// 128^3 fine level, 512 on the HBM-resident 256^3 one; 1024 won on neither and stays a setting of sgpu_op_set_x_windows
+static const int XWIN_CANDIDATES[] = {0, 1};
 
 int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_name) {
     if (!op) return fail(SGPU_ERR_ARG, "null op");
@@ -2649,13 +2756,47 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
         if (!op->loc.cc_ok[variant - 3]) return fail(SGPU_ERR_ARG, "a row block of this operator touches more than 256 column segments of 256 columns");
     }
     op->loc.variant = variant;
+    op->loc.vw_rows = 0;                                 // variant 17 alone gathers directly; sgpu_op_set_x_windows turns the windows on
     ++g_plan_generation;
+    if (variant == 17)
+        if (const char *e = std::getenv("SAENA_X_WINDOWS")) {     // development: pin the mode where only the variant can be pinned (counter passes); refused -> direct
+            const int rows = std::atoi(e);
+            if (rows == 256 || rows == 512 || rows == 1024) {
+                CHK(build_xwin(op->loc, rows == 256 ? 0 : rows == 512 ? 1 : 2));
+                if (op->loc.vw[rows == 256 ? 0 : rows == 512 ? 1 : 2].ok) op->loc.vw_rows = rows;
+            }
+        }
+    return SGPU_OK;
+}
+
+int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
+    CHK(need_ctx());
+    if (!op) return fail(SGPU_ERR_ARG, "null op");
+    const int R = rows_per_workgroup;
+    if (R == 0) { op->loc.vw_rows = 0; ++g_plan_generation; return SGPU_OK; }
+    if (R != 256 && R != 512 && R != 1024) return fail(SGPU_ERR_ARG, "x windows: rows per workgroup must be 0 (off), 256, 512 or 1024");
+    if (op->loc.variant != 17) return fail(SGPU_ERR_ARG, "x windows are a launch mode of the value-indexed form: set variant 17 first");
+    const int k = R == 256 ? 0 : R == 512 ? 1 : 2;
+    std::string why;
+    CHK(build_xwin(op->loc, k, &why));
+    if (!op->loc.vw[k].ok)
+        return fail(SGPU_ERR_ARG, "x windows refused for workgroups of %d rows (%s): the mode needs ONE pattern table relative to the row index, at most %d windows, "
+                                  "16-bit LDS positions and %d KiB of LDS for windows, dictionaries and table; the operator keeps its direct gathers",
+                    R, why.c_str(), sk::SPX_MAXWIN, sk::VW_MAX_LDS / 1024);
+    op->loc.vw_rows = R;
+    ++g_plan_generation;
+    return SGPU_OK;
+}
+
+int sgpu_op_get_x_windows(const sgpu_op *op, int *rows_per_workgroup) {
+    if (!op || !rows_per_workgroup) return fail(SGPU_ERR_ARG, "null argument");
+    *rows_per_workgroup = op->loc.variant == 17 ? op->loc.vw_rows : 0;
     return SGPU_OK;
 }
 
 // ---- plan cache: what the autotune chose for an operator of this shape on this device, so that a second process picks the
 // same kernel (same summation order: bit-identical solves across processes) and skips the sweep.  One line per operator in
-// $SAENA_PLAN_CACHE, default $XDG_CACHE_HOME or ~/.cache + /saena_amd/plans-v4.tsv (v3: round 4 added candidate forms, v4: the value-indexed form -- plans an older library cached must not shadow them); SAENA_PLAN_CACHE=off disables it.
+// $SAENA_PLAN_CACHE, default $XDG_CACHE_HOME or ~/.cache + /saena_amd/plans-v5.tsv (v3: round 4 added candidate forms, v4: the value-indexed form, v5: its x-window mode, a field of its own -- plans an older library cached must not shadow them); SAENA_PLAN_CACHE=off disables it.
 extern "C++" {                                              // (helpers with C++ types inside the extern "C" block)
 namespace {
 uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
@@ -2675,7 +2816,7 @@ std::string plan_cache_path() {
     ::mkdir(dir.c_str(), 0755);
     dir += "/saena_amd";
     ::mkdir(dir.c_str(), 0755);
-    return dir + "/plans-v4.tsv";
+    return dir + "/plans-v5.tsv";
 }
 // key: device, sizes, what the kernel does (smoother epilogue or plain product, halo mask), the row-length histogram in
 // powers of two and the column ids at 256 evenly spaced entries
@@ -2701,7 +2842,7 @@ uint64_t plan_key(const sgpu_op *op) {
     for (int i = 0; i < 256 && nn; ++i) { const int c = P.h_col[(size_t)((double)i / 256.0 * (double)nn)]; h = fnv1a(h, &c, sizeof c); }
     return h;
 }
-bool plan_cache_lookup(uint64_t key, int *v, int *lanes) {
+bool plan_cache_lookup(uint64_t key, int *v, int *lanes, int *xw) {
     const std::string path = plan_cache_path();
     if (path.empty()) return false;
     FILE *f = fopen(path.c_str(), "r");
@@ -2709,18 +2850,19 @@ bool plan_cache_lookup(uint64_t key, int *v, int *lanes) {
     char line[256];
     bool hit = false;
     while (fgets(line, sizeof line, f)) {               // the last line of a key wins
-        unsigned long long k; int vv, ll;
-        if (sscanf(line, "%llx %d %d", &k, &vv, &ll) == 3 && k == key && vv >= 0 && vv <= MAX_VARIANT && ll >= 1 && ll <= 64) { *v = vv; *lanes = ll; hit = true; }
+        unsigned long long k; int vv, ll, xx;
+        if (sscanf(line, "%llx %d %d %d", &k, &vv, &ll, &xx) == 4 && k == key && vv >= 0 && vv <= MAX_VARIANT && ll >= 1 && ll <= 64 &&
+            (xx == 0 || (vv == 17 && (xx == 256 || xx == 512 || xx == 1024)))) { *v = vv; *lanes = ll; *xw = xx; hit = true; }
     }
     fclose(f);
     return hit;
 }
-void plan_cache_store(uint64_t key, const sgpu_op *op, int v, int lanes, float ms, int rv = -1, int rlanes = 0, float rms = 0) {
+void plan_cache_store(uint64_t key, const sgpu_op *op, int v, int lanes, int xw, float ms, int rv = -1, int rlanes = 0, float rms = 0) {
     const std::string path = plan_cache_path();
     if (path.empty()) return;
     char line[256];
-    int n = snprintf(line, sizeof line, "%016llx\t%d\t%d\t%.4f\t# %d rows %lld nnz", (unsigned long long)key, v, lanes, ms, op->M, (long long)op->loc.nnz);
-    if (rv >= 0) n += snprintf(line + n, sizeof line - (size_t)n, "; %s %.4f ms; runner-up %s with %d lanes %.4f ms", VARIANT_NAMES[v], ms, VARIANT_NAMES[rv], rlanes, rms);   // (the lookup reads the first three fields)
+    int n = snprintf(line, sizeof line, "%016llx\t%d\t%d\t%d\t%.4f\t# %d rows %lld nnz", (unsigned long long)key, v, lanes, xw, ms, op->M, (long long)op->loc.nnz);
+    if (rv >= 0) n += snprintf(line + n, sizeof line - (size_t)n, "; %s %.4f ms; runner-up %s with %d lanes %.4f ms", VARIANT_NAMES[v], ms, VARIANT_NAMES[rv], rlanes, rms);   // (the lookup reads the first four fields: variant, lanes, x-window rows)
     n += snprintf(line + n, sizeof line - (size_t)n, "\n");
     const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0644);    // one write() of one short line: appends of concurrent ranks do not interleave
     if (fd < 0) return;
@@ -2738,7 +2880,8 @@ void finish_plan(sgpu_op *op, int bv) {
             op->loc.cm_ok[k] = false; op->loc.cm_tried[k] = 0;
         }
     if (bv != 14 && !keep) op->loc.free_sellp2();
-    if (bv != 17 && !keep) op->loc.free_vidx();
+    if (bv != 17 && !keep) op->loc.free_vidx();                   // (the x-window tables go with the codes ...)
+    else if (!keep) op->loc.free_xwin(op->loc.vw_rows);           // (... or stay with them: the workgroup size in use only)
     if ((bv == 14 || bv == 17) && !keep) {                        // k_sellp2 / k_vidx keep the pattern ids and the table; k_sell's / k_sellp's arrays go
         CsrPart &L = op->loc;
         L.free_sell_columns();
@@ -2791,12 +2934,12 @@ int sgpu_op_autotune(sgpu_op *op) {
     const double t_begin = now_s();
     const uint64_t key = plan_key(op);
     {
-        int cv = 0, cl = 1;
-        if (plan_cache_lookup(key, &cv, &cl) && sgpu_op_set_variant(op, cv) == SGPU_OK) {
+        int cv = 0, cl = 1, cx = 0;
+        if (plan_cache_lookup(key, &cv, &cl, &cx) && sgpu_op_set_variant(op, cv) == SGPU_OK && (cx == 0 || sgpu_op_set_x_windows(op, cx) == SGPU_OK)) {
             op->loc.lanes = cl;
             ++g_plan_generation;
             finish_plan(op, cv);
-            if (verbose) fprintf(stderr, "[sgpu] plan of %d rows x %lld nnz from the cache: variant %d, %d lanes (%.3f s)\n", op->M, (long long)op->loc.nnz, cv, cl, now_s() - t_begin);
+            if (verbose) fprintf(stderr, "[sgpu] plan of %d rows x %lld nnz from the cache: variant %d, %d lanes, x windows %d (%.3f s)\n", op->M, (long long)op->loc.nnz, cv, cl, op->loc.vw_rows, now_s() - t_begin);
             return SGPU_OK;
         }
     }
@@ -2813,7 +2956,7 @@ int sgpu_op_autotune(sgpu_op *op) {
     //   rows of up to ~128 entries with even lengths -- sliced ELLPACK (with or without a column stream) or 16-bit columns on
     //   16 KiB tiles; a few hundred entries -- column order inside 32 KiB tiles, 16-bit columns on either tile; a thousand and
     //   more -- x in LDS, the wave-streamed kernel, 16-bit or 32-bit columns on tiles
-    std::vector<int> variants;
+    std::vector<int> variants, xwin_rows;
     bool sell_like = false;
     if (!std::getenv("SAENA_NO_SELL") && (all || avg_row <= 160.0)) {                                 // even rows: a lane per row
         CHK(build_sell_values(op->loc));                                                             // (on the device, from the CSR values: round 4)
@@ -2828,6 +2971,9 @@ int sgpu_op_autotune(sgpu_op *op) {
                 if (op->loc.sp_ok && !op->loc.sp_wide && 8 * op->loc.nnz > ((int64_t)32 << 20) && !std::getenv("SAENA_NO_VALUE_INDEX")) {
                     CHK(build_vidx(op->loc));
                     if (op->loc.vi_ok) variants.push_back(17);
+                    // ... and the same form with x in LDS windows (k_vidxw), a candidate of its own per workgroup size kept
+                    if (op->loc.vi_ok && !std::getenv("SAENA_NO_X_WINDOWS"))
+                        for (int k : XWIN_CANDIDATES) { CHK(build_xwin(op->loc, k)); if (op->loc.vw[k].ok) xwin_rows.push_back(256 << k); }
                 }
                 // ... and a lane per two rows: half the gathers.  With a table per workgroup (sp_wide: the 68-entry level) it wins on the
                 // operator of 128^3 (110 against 116 us, k_sellpx 114) and ties on that of 256^3 (940 / 945, k_sellpx 890), whose row-paired
@@ -2901,9 +3047,9 @@ int sgpu_op_autotune(sgpu_op *op) {
     const int epi = kind == 1 ? sk::EPI_JACOBI : sk::EPI_SPMV;
     ++g_plan_generation;                                 // frees/replaces buffers captured graphs may reference
     struct Guard {                                       // an error return inside the sweep leaves the operator as it was
-        sgpu_op *op; int v, l; hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = true;
-        ~Guard() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); if (armed) { op->loc.variant = v; op->loc.lanes = l; } }
-    } guard{op, op->loc.variant, op->loc.lanes};
+        sgpu_op *op; int v, l, xw; hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = true;
+        ~Guard() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); if (armed) { op->loc.variant = v; op->loc.lanes = l; op->loc.vw_rows = xw; } }
+    } guard{op, op->loc.variant, op->loc.lanes, op->loc.vw_rows};
     HIPCHK(hipEventCreate(&guard.e0)); HIPCHK(hipEventCreate(&guard.e1));
     const hipEvent_t e0 = guard.e0, e1 = guard.e1;
     std::vector<int> lanes_x;                            // k_csr_xlds: lanes per (row, window) piece, about a 64th of its length
@@ -2919,6 +3065,7 @@ int sgpu_op_autotune(sgpu_op *op) {
             if (v == 5 && gl != lanes.front()) continue;                   // one wave per dense row likewise
             cands.push_back({v, gl});
         }
+    for (int rows : xwin_rows) cands.push_back({17, rows});      // (variant 17, "lanes" >= 256: the x-window mode at that many rows per workgroup)
     {                                                    // a few milliseconds of the current plan first: a process's first kernels run at ramping clocks
         float ms = 0;
         for (int burst = 0; burst < 8 && ms < 2.0f; ++burst) {
@@ -2932,7 +3079,7 @@ int sgpu_op_autotune(sgpu_op *op) {
         }
     }
     auto sample = [&](int v, int gl, int reps, float *ms) -> int {
-        op->loc.variant = v; op->loc.lanes = gl;
+        op->loc.variant = v; op->loc.lanes = gl >= 256 ? lanes.front() : gl; op->loc.vw_rows = gl >= 256 ? gl : 0;
         HIPCHK(hipEventRecord(e0, g.cs));
         for (int i = 0; i < reps; ++i) CHK(launch_part(op->loc, epi, x.p, y.p, e));
         HIPCHK(hipEventRecord(e1, g.cs));
@@ -3008,17 +3155,23 @@ int sgpu_op_autotune(sgpu_op *op) {
         const int rank = sequential_sum(v, gl) ? 0 : 1;
         if (rank < brank || (rank == 0 && brank == 0 && kv.second < bms)) { brank = rank; bv = v; bg = gl; bms = kv.second; }
     }
+    if (bv == 17 && bg >= 256) {                          // the x-window mode has to win clearly: direct gathers inside the band come first
+        const auto it = seen.find({17, lanes.front()});
+        if (it != seen.end() && it->second <= bar) { bg = it->first.second; bms = it->second; }
+    }
     for (const auto &kv : seen)
         if ((kv.first.first != bv || kv.first.second != bg) && (rv < 0 || kv.second < rms)) { rv = kv.first.first; rg = kv.first.second; rms = kv.second; }
     guard.armed = false;
-    op->loc.variant = bv; op->loc.lanes = bg;
+    const int bxw = bg >= 256 ? bg : 0;
+    if (bxw) bg = lanes.front();
+    op->loc.variant = bv; op->loc.lanes = bg; op->loc.vw_rows = bxw;
     const double t_fin0 = now_s();
     finish_plan(op, bv);
     const double t_fin1 = now_s();
-    plan_cache_store(key, op, bv, bg, bms, rv, rg, rms);
+    plan_cache_store(key, op, bv, bg, bxw, bms, rv, rg, rms);
     if (verbose)
-        fprintf(stderr, "[sgpu] autotune of %d rows x %lld nnz (%.1f per row): %zu candidates, variant %d with %d lanes at %.1f us (fastest %.1f us; runner-up variant %d with %d lanes at %.1f us); sliced ELLPACK %.2f s, "
-                        "16-bit columns %.2f s, x in LDS %.2f s, column order %.2f s, timing %.2f s (of which freeing the forms that lost %.2f s)\n", op->M, (long long)op->loc.nnz, avg_row, cands.size(), bv, bg, bms * 1e3,
+        fprintf(stderr, "[sgpu] autotune of %d rows x %lld nnz (%.1f per row): %zu candidates, variant %d with %d lanes (x windows: %d rows per workgroup) at %.1f us (fastest %.1f us; runner-up variant %d with %d lanes at %.1f us); sliced ELLPACK %.2f s, "
+                        "16-bit columns %.2f s, x in LDS %.2f s, column order %.2f s, timing %.2f s (of which freeing the forms that lost %.2f s)\n", op->M, (long long)op->loc.nnz, avg_row, cands.size(), bv, bg, bxw, bms * 1e3,
                 (cm_wins ? best_cm : best) * 1e3, rv, rg, rms * 1e3, t_sell - t_begin, t_cc - t_sell, t_xl - t_cc, t_cm1 - t_cm0, now_s() - t_cm - (t_cm1 - t_cm0), t_fin1 - t_fin0);
     return SGPU_OK;
 }
