@@ -35,8 +35,9 @@ KEEP = {"SAENA_KEEP_HOST_VALUES": "1"}
 XL_MAX, NCU = 20224, 256                     # doubles of x in one LDS window; CUs of an MI355X (one x-in-LDS chunk each)
 
 # key, variant, kernel name (a trailing "*" matches a prefix), lanes per row, summation class, environment, tile:
-# the tile forms (0, 1, 3, 4, 7, 8) keep the sequential order at one lane per row for rows of at most `tile` entries
-Form = namedtuple("Form", "key variant name lanes cls env tile")
+# the tile forms (0, 1, 3, 4, 7, 8) keep the sequential order at one lane per row for rows of at most `tile` entries; xw: rows per
+# workgroup of the x-window launch mode of variant 17 (set_x_windows after set_variant; 0: the variant as it stands)
+Form = namedtuple("Form", "key variant name lanes cls env tile xw", defaults=(0,))
 FORMS = [
     Form("stream16", 0, "k_csr_stream<16KiB>", 1, SEQ, {}, 2048),
     Form("stream16.l8", 0, "k_csr_stream<16KiB>", 8, TREE, {}, 0),
@@ -73,12 +74,22 @@ FORMS = [
     Form("xldsr.natural", 16, "k_csr_xldsr", 8, TREE, {"SAENA_XLDS_NATURAL_ORDER": "1"}, 0),
     Form("vidx", 17, "k_vidx", 1, SEQ, {}, 0),
     Form("vidx.rowbase", 17, "k_vidx<rowbase>", 1, SEQ, {}, 0),
+    Form("vidx.w256", 17, "k_vidx", 1, SEQ, {}, 0, 256),
+    Form("vidx.w512", 17, "k_vidx", 1, SEQ, {}, 0, 512),
+    Form("vidx.w1024", 17, "k_vidx", 1, SEQ, {}, 0, 1024),
 ]
 BY_KEY = {f.key: f for f in FORMS}
 # what set_variant says when a form does not apply (variants 0, 1, 2 and 6 apply to every operator)
 REFUSAL = {3: "column segments", 4: "column segments", 5: "too large for the dense form", 7: "column-major", 8: "column-major",
            9: "sliced-ELLPACK form", 10: "x-in-LDS form", 11: "row-pattern form needs", 12: "sliced-ELLPACK-in-LDS",
            13: "row-template", 14: "row-paired", 15: "x in LDS", 16: "x-in-LDS form", 17: "value-indexed"}
+X_WINDOWS_REFUSAL = "x windows"              # what set_x_windows says where the operator is on variant 17 and the mode does not apply
+
+
+def refused_as_documented(form, what):
+    """the form's own message; for the window keys either the variant's or the mode's (make_gpu and form_world hold a refusal of
+    set_x_windows itself to the mode's)"""
+    return (form.variant in REFUSAL and REFUSAL[form.variant] in what) or (form.xw != 0 and X_WINDOWS_REFUSAL in what)
 
 
 @pytest.fixture(scope="module")
@@ -225,6 +236,13 @@ def make_gpu(capi, O, form, monkeypatch, r=0, halo_fp32=False):
         except capi.SgpuError as e:
             return None, str(e)
         G.set_lanes_per_row(form.lanes)
+        if form.xw:
+            try:
+                G.set_x_windows(form.xw)
+            except capi.SgpuError as e:
+                assert X_WINDOWS_REFUSAL in str(e), str(e)
+                return None, str(e)
+            assert G.x_windows() == form.xw
         return G, G.variant()[1]
     finally:
         for k in form.env:
@@ -354,7 +372,7 @@ def test_every_entry_point_against_the_oracle(capi, key, monkeypatch):
         O = oracle_op(p)
         G, what = make_gpu(capi, O, form, monkeypatch)
         if G is None:
-            assert form.variant in REFUSAL and REFUSAL[form.variant] in what, (name, what)
+            assert refused_as_documented(form, what), (name, what)
             continue
         if not name_matches(form, what):
             continue                                            # another sub-form of the variant serves this operator
@@ -372,10 +390,13 @@ HALO_OPERATORS = ["poisson13", "poisson20", "poisson13/planes", "band", "L1", "P
 
 def world_outputs(capi, p, O, W, forms, v, fp32):
     """spmv, residual, two Jacobi sweeps (halo exchanged before each), a Chebyshev step; u -= A e for the transfers.  forms[r]:
-    the form of rank r"""
+    the form of rank r as (variant, lanes, rows per workgroup of the x-window mode)"""
     split_r, split_c = O.split_row, O.split_col
     for r, (G, f) in enumerate(zip(W.g, forms)):
         G.set_variant(f[0]); G.set_lanes_per_row(f[1])
+        if f[2]:
+            G.set_x_windows(f[2])
+        assert G.variant()[0] == f[0] and G.x_windows() == f[2]
     out = {}
     xs, ys = W.slices(v["x"], split_c), [capi.DeviceVector(int(split_r[r + 1] - split_r[r])) for r in range(W.P)]
     W.exchange(xs)
@@ -407,8 +428,12 @@ def world_outputs(capi, p, O, W, forms, v, fp32):
     return out
 
 
+ANCHOR = (4, 1, 0)                           # k_csr_cc16 at one lane: what a rank runs where its slice refuses the form, and the halo tests' anchor
+
+
 def form_world(capi, O, fp32, form, monkeypatch):
-    """-> (world, [(variant, lanes)] per rank): the form where the rank's slice takes it, variant 4 at 1 lane where it refuses"""
+    """-> (world, [(variant, lanes, x-window rows)] per rank): the form where the rank's slice takes it, variant 4 at 1 lane where it
+    refuses"""
     out = []
     for k, v in form.env.items():
         monkeypatch.setenv(k, v)
@@ -421,7 +446,13 @@ def form_world(capi, O, fp32, form, monkeypatch):
             except capi.SgpuError as e:
                 assert form.variant in REFUSAL and REFUSAL[form.variant] in str(e), str(e)
                 ok = False
-            out.append((form.variant, form.lanes) if ok else (4, 1))
+            if ok and form.xw:
+                try:
+                    G.set_x_windows(form.xw)
+                except capi.SgpuError as e:
+                    assert X_WINDOWS_REFUSAL in str(e), str(e)
+                    ok = False
+            out.append((form.variant, form.lanes, form.xw) if ok else ANCHOR)
     finally:
         for k in form.env:
             monkeypatch.delenv(k, raising=False)
@@ -475,7 +506,7 @@ def test_emulated_halos(capi, key, nprocs, monkeypatch):
                 assert np.all(np.abs(got["spmv"] - O.matvec_dense(v["x"], as_float=True)) <= TOL * b + 1e-300), where
                 continue
             if form.cls == SEQ and sequential_rows(form, p).all():
-                anchor = world_outputs(capi, p, O, W, [(4, 1)] * nprocs, v, fp32)
+                anchor = world_outputs(capi, p, O, W, [ANCHOR] * nprocs, v, fp32)
                 for k in got:
                     np.testing.assert_array_equal(bits(got[k]), bits(anchor[k]), err_msg=f"{where} {k}")
             b = abs_bound(p.entries, p.M, v["x"])
@@ -520,7 +551,7 @@ def test_restriction_with_the_next_level_s_first_sweep(capi, monkeypatch):
     for form in FORMS:
         G, what = make_gpu(capi, OR[0], form, monkeypatch)
         if G is None:
-            assert REFUSAL[form.variant] in what, (form.key, what)
+            assert refused_as_documented(form, what), (form.key, what)
             continue
         if not name_matches(form, what):
             continue
@@ -683,11 +714,13 @@ def test_a_non_finite_value_stays_in_its_row(capi, name, monkeypatch):
                     continue
                 G, what = make_gpu(capi, O, form, monkeypatch)
                 if G is None:                                   # the special may take the operator out of a form (k_vidx's dictionary)
-                    assert form.variant == 17 and REFUSAL[17] in what, (form.key, what)
+                    assert form.variant == 17 and REFUSAL[17] in what, (form.key, what)      # (the window keys too: the variant itself goes)
                     continue
                 ran.append(form.key)
                 got = run_gpu(capi, G, q, v, CONTAIN_EPIS)
                 check_contained(got, clean[form.key], ref, f"{form.key} on {name}, value {s} at CSR position {pos} (row {row}):")
+    if name == "poisson13":
+        assert {"vidx", "vidx.w256", "vidx.w512", "vidx.w1024"} <= set(ran)
     if name == "hub":
         assert {"xlds.l8", "xlds.l64", "xlds.global", "xlds.natural", "xldsr.l4", "xldsr.l16", "xldsr.global", "xldsr.natural"} <= set(ran)
 
@@ -740,7 +773,7 @@ def test_a_non_finite_halo_value_stays_in_the_receiving_rows(capi, key, monkeypa
 
 
 # ---- the switches read once per process ---------------------------------------------------------------------------------------
-NT_FORMS = ["sellp", "sellp.wide", "sellp2", "sellp2.wide", "sellpx", "vidx"]
+NT_FORMS = ["sellp", "sellp.wide", "sellp2", "sellp2.wide", "sellpx", "vidx", "vidx.w256", "vidx.w512", "vidx.w1024"]
 NT_WORKER = r"""
 import sys, json, hashlib
 sys.path.insert(0, %(root)r)
@@ -779,7 +812,8 @@ def nt_outputs(capi, monkeypatch=None):
 
 def test_non_temporal_and_non_pre_instantiations_give_the_same_bits(capi, monkeypatch):
     """SAENA_SELLP_NT and SAENA_SELLP2_PRE are read once per process: a child process with SAENA_SELLP_NT=1 SAENA_SELLP2_PRE=0
-    runs the NT instantiations of 11, 14, 15 and 17 and 14 without PRE on operators far below the size where they switch on"""
+    runs the NT instantiations of 11, 14, 15 and 17 (k_vidx and, with the x windows on, k_vidxw) and 14 without PRE on operators far
+    below the size where they switch on"""
     here = nt_outputs(capi, monkeypatch)
     assert {k.split("/")[1] for k in here} == set(NT_FORMS)
     env = dict(os.environ, SAENA_SELLP_NT="1", SAENA_SELLP2_PRE="0")
