@@ -25,26 +25,10 @@ int block_auto_lanes(const sgpu_op *op) {
 }
 
 using BlockFn = void (*)(const sk::BlockArgs);
-template <int K, int EPI>
-BlockFn block_pick_g(int G) {
-    switch (G) {
-        case 1:  return sk::k_csr_block<K, EPI, 1>;
-        case 4:  return sk::k_csr_block<K, EPI, 4>;
-        case 16: return sk::k_csr_block<K, EPI, 16>;
-        default: return sk::k_csr_block<K, EPI, 64>;
-    }
-}
-template <int K>
-BlockFn block_pick_epi(int epi, int G) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return block_pick_g<K, sk::EPI_SPMV>(G);
-        case sk::EPI_RESIDUAL: return block_pick_g<K, sk::EPI_RESIDUAL>(G);
-        case sk::EPI_JACOBI:   return block_pick_g<K, sk::EPI_JACOBI>(G);
-        case sk::EPI_CHEBY0:   return block_pick_g<K, sk::EPI_CHEBY0>(G);
-        case sk::EPI_CHEBYK:   return block_pick_g<K, sk::EPI_CHEBYK>(G);
-        case sk::EPI_SUB:      return block_pick_g<K, sk::EPI_SUB>(G);
-        default:               return nullptr;
-    }
+// K columns in {2, 4, 8}; G lanes per row in {1, 4, 16}, anything else 64 (the pickers of sgpu_runtime.hip)
+BlockFn pick_block(int K, int epi, int G) {
+    return among<2, 4, 8>(K, [&](auto KK) { return per_epi_no_rsweep(epi, [&](auto E) { return among<1, 4, 16, 64>(G == 1 || G == 4 || G == 16 ? G : 64, [&](auto GG) -> BlockFn {
+        return sk::k_csr_block<KK(), E(), GG()>; }); }); });
 }
 
 // Y = epilogue(A X): one launch of k_csr_block over the operator's 16 KiB row-block plan
@@ -52,7 +36,7 @@ int apply_block(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs 
     if (op->M == 0 || op->loc.nblk == 0) return SGPU_OK;
     if (!op->block_lanes_auto) op->block_lanes_auto = block_auto_lanes(op);
     const int G = op->block_lanes ? op->block_lanes : op->block_lanes_auto;
-    const BlockFn fn = K == 2 ? block_pick_epi<2>(epi, G) : K == 4 ? block_pick_epi<4>(epi, G) : block_pick_epi<8>(epi, G);
+    const BlockFn fn = pick_block(K, epi, G);
     if (!fn) return fail(SGPU_ERR_ARG, "block apply: no kernel for epilogue %d", epi);   // a missing kernel is an error, never a fall-back
     sk::BlockArgs a;
     a.row_ptr = op->loc.row_ptr; a.col = op->loc.col; a.val = op->loc.val; a.blk_row = op->loc.blk_row; a.nblk = op->loc.nblk;

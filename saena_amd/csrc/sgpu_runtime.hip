@@ -11,6 +11,7 @@
 #include "kernels_block.hip.h"
 #include "kernels_gmres.hip.h"
 #include "kernels_eig.hip.h"
+#include "dispatch.h"
 #include "host/dense_eig.h"
 #include "host/comm.h"
 #include "host/par.h"
@@ -1507,366 +1508,174 @@ int build_dense_rem(sgpu_op *op) {
     return SGPU_OK;
 }
 
-using KernelFn = void (*)(const sk::SpmvArgs);
-using VecKernelFn = void (*)(const sk::SpmvArgs, int);
-
-// kernel family F: 0 k_csr_stream, 1 k_csr_cc16; H: interior half of a multi-rank apply (kernels.hip.h)
-template <int F, int EPI, int CAPV, int G, bool H>
-constexpr KernelFn kernel_of() {
-    if constexpr (F == 0) return sk::k_csr_stream<EPI, G, CAPV, H>;
-    else if constexpr (F == 2) return sk::k_csr_cm<EPI, G, CAPV, H>;
-    else return sk::k_csr_cc16<EPI, G, CAPV, H>;
-}
-template <int F, int EPI, int CAPV, bool H>
-KernelFn pick_g(int lanes) {
-    switch (lanes) {
-        case 1:  return kernel_of<F, EPI, CAPV, 1, H>();
-        case 2:  return kernel_of<F, EPI, CAPV, 2, H>();
-        case 4:  return kernel_of<F, EPI, CAPV, 4, H>();
-        case 8:  return kernel_of<F, EPI, CAPV, 8, H>();
-        case 16: return kernel_of<F, EPI, CAPV, 16, H>();
-        case 32: return kernel_of<F, EPI, CAPV, 32, H>();
-        default: return kernel_of<F, EPI, CAPV, 64, H>();
-    }
-}
-template <int F, int EPI, bool H>
-KernelFn pick_cap(int lanes, bool big) { return big ? pick_g<F, EPI, sk::CAP_BIG, H>(lanes) : pick_g<F, EPI, sk::CAP, H>(lanes); }
-template <int F, bool H>
-KernelFn pick_h(int epi, int lanes, bool big) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return pick_cap<F, sk::EPI_SPMV, H>(lanes, big);
-        case sk::EPI_RESIDUAL: return pick_cap<F, sk::EPI_RESIDUAL, H>(lanes, big);
-        case sk::EPI_JACOBI:   return pick_cap<F, sk::EPI_JACOBI, H>(lanes, big);
-        case sk::EPI_CHEBY0:   return pick_cap<F, sk::EPI_CHEBY0, H>(lanes, big);
-        case sk::EPI_CHEBYK:   return pick_cap<F, sk::EPI_CHEBYK, H>(lanes, big);
-        case sk::EPI_RSWEEP:   return pick_cap<F, sk::EPI_RSWEEP, H>(lanes, big);
-        default:               return pick_cap<F, sk::EPI_SUB, H>(lanes, big);
-    }
-}
-template <int F>
-KernelFn pick(int epi, int lanes, bool big, bool halo) { return halo ? pick_h<F, true>(epi, lanes, big) : pick_h<F, false>(epi, lanes, big); }
-template <int EPI, bool H>
-VecKernelFn pick_vec_g(int lanes) {
-    switch (lanes) {
-        case 1:  return sk::k_csr_vector<EPI, 1, H>;
-        case 2:  return sk::k_csr_vector<EPI, 2, H>;
-        case 4:  return sk::k_csr_vector<EPI, 4, H>;
-        case 8:  return sk::k_csr_vector<EPI, 8, H>;
-        case 16: return sk::k_csr_vector<EPI, 16, H>;
-        case 32: return sk::k_csr_vector<EPI, 32, H>;
-        default: return sk::k_csr_vector<EPI, 64, H>;
-    }
-}
-template <bool H>
-VecKernelFn pick_vec_h(int epi, int lanes) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return pick_vec_g<sk::EPI_SPMV, H>(lanes);
-        case sk::EPI_RESIDUAL: return pick_vec_g<sk::EPI_RESIDUAL, H>(lanes);
-        case sk::EPI_JACOBI:   return pick_vec_g<sk::EPI_JACOBI, H>(lanes);
-        case sk::EPI_CHEBY0:   return pick_vec_g<sk::EPI_CHEBY0, H>(lanes);
-        case sk::EPI_CHEBYK:   return pick_vec_g<sk::EPI_CHEBYK, H>(lanes);
-        case sk::EPI_RSWEEP:   return pick_vec_g<sk::EPI_RSWEEP, H>(lanes);
-        default:               return pick_vec_g<sk::EPI_SUB, H>(lanes);
-    }
-}
-VecKernelFn pick_vec(int epi, int lanes, bool halo) { return halo ? pick_vec_h<true>(epi, lanes) : pick_vec_h<false>(epi, lanes); }
-template <int EPI, bool H>
-VecKernelFn pick_wave_g(int lanes) {
-    switch (lanes) {
-        case 1: case 2: case 4: case 8:  return sk::k_csr_wave<EPI, 8, H>;
-        case 16: return sk::k_csr_wave<EPI, 16, H>;
-        case 32: return sk::k_csr_wave<EPI, 32, H>;
-        default: return sk::k_csr_wave<EPI, 64, H>;
-    }
-}
-template <bool H>
-VecKernelFn pick_wave_h(int epi, int lanes) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return pick_wave_g<sk::EPI_SPMV, H>(lanes);
-        case sk::EPI_RESIDUAL: return pick_wave_g<sk::EPI_RESIDUAL, H>(lanes);
-        case sk::EPI_JACOBI:   return pick_wave_g<sk::EPI_JACOBI, H>(lanes);
-        case sk::EPI_CHEBY0:   return pick_wave_g<sk::EPI_CHEBY0, H>(lanes);
-        case sk::EPI_CHEBYK:   return pick_wave_g<sk::EPI_CHEBYK, H>(lanes);
-        case sk::EPI_RSWEEP:   return pick_wave_g<sk::EPI_RSWEEP, H>(lanes);
-        default:               return pick_wave_g<sk::EPI_SUB, H>(lanes);
-    }
-}
-VecKernelFn pick_wave(int epi, int lanes, bool halo) { return halo ? pick_wave_h<true>(epi, lanes) : pick_wave_h<false>(epi, lanes); }
-
 struct EpiArgs {
     const double *rhs = nullptr, *inv_diag = nullptr, *u = nullptr;
     double       *d = nullptr, *y2 = nullptr;
     double        c0 = 0.0, c1 = 0.0;
 };
 
-// seq != 0: the launch carries the fork (block 0 stores flag_x = seq when it starts)
-using SellKernelFn = void (*)(const sk::SpmvArgs, int);
-template <bool HALO, bool PAIR, bool NT>
-SellKernelFn pick_sell_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_sell<sk::EPI_SPMV, HALO, PAIR, NT>;
-        case sk::EPI_RESIDUAL: return sk::k_sell<sk::EPI_RESIDUAL, HALO, PAIR, NT>;
-        case sk::EPI_JACOBI:   return sk::k_sell<sk::EPI_JACOBI, HALO, PAIR, NT>;
-        case sk::EPI_CHEBY0:   return sk::k_sell<sk::EPI_CHEBY0, HALO, PAIR, NT>;
-        case sk::EPI_CHEBYK:   return sk::k_sell<sk::EPI_CHEBYK, HALO, PAIR, NT>;
-        case sk::EPI_RSWEEP:   return sk::k_sell<sk::EPI_RSWEEP, HALO, PAIR, NT>;
-        default:               return sk::k_sell<sk::EPI_SUB, HALO, PAIR, NT>;
-    }
+// ---- kernel pickers: from the runtime's (epilogue, lanes, halo, ...) to a __global__ instantiation, through dispatch.h ----
+// A family names its kernel and its parameter lists once.  An epilogue outside a family's list yields NO kernel (nullptr) and the
+// launch fails with SGPU_ERR_STATE (SGPU_LAUNCH_PICKED): a missing kernel is an error, never a fall-back to another one.
+using dispatch::among;
+using dispatch::with_bool;
+using KernelFn = void (*)(const sk::SpmvArgs);
+using VecKernelFn = void (*)(const sk::SpmvArgs, int);
+using SellKernelFn = void (*)(const sk::SpmvArgs, int);     // seq != 0: the launch carries the fork (block 0 stores flag_x = seq when it starts)
+using XldsKernelFn = void (*)(const sk::SpmvArgs, const sk::XldsArgs);
+using SellxKernelFn = void (*)(const sk::SpmvArgs, const sk::SellxArgs);
+using DenseKernelFn = void (*)(const sk::SpmvArgs, const double *, int, int);
+using DenseHaloKernelFn = void (*)(const sk::SpmvArgs, const double *, const double *, int, int, int, const double *, const float *, int);
+using BndKernelFn = void (*)(const sk::BoundaryArgs);
+
+template <class F>
+auto per_epi(int epi, F &&f) { return among<sk::EPI_SPMV, sk::EPI_RESIDUAL, sk::EPI_JACOBI, sk::EPI_CHEBY0, sk::EPI_CHEBYK, sk::EPI_SUB, sk::EPI_RSWEEP>(epi, f); }
+// k_dense_rows_halo, k_csr_boundary, k_csr_block: no EPI_RSWEEP (vcycle_level fuses the restriction's sweep on one rank only, on a scalar operator without a remote part)
+template <class F>
+auto per_epi_no_rsweep(int epi, F &&f) { return among<sk::EPI_SPMV, sk::EPI_RESIDUAL, sk::EPI_JACOBI, sk::EPI_CHEBY0, sk::EPI_CHEBYK, sk::EPI_SUB>(epi, f); }
+
+// lanes per row -> an instantiated group size.  The tile, vector and boundary kernels: the powers of two up to a wave, anything else 64
+int lanes_or_64(int lanes) { return lanes == 1 || lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 ? lanes : 64; }
+template <class F>
+auto per_lanes(int lanes, F &&f) { return among<1, 2, 4, 8, 16, 32, 64>(lanes_or_64(lanes), f); }
+// the x-in-LDS kernels: the smallest power of two in lo .. hi that holds the lanes, else hi
+int lanes_up(int lanes, int lo, int hi) { int G = lo; while (G < lanes && G < hi) G *= 2; return G; }
+
+// tile family F: 0 k_csr_stream, 1 k_csr_cc16, 2 k_csr_cm; tiles of CAP / CAP_BIG products; H: interior half of a multi-rank apply (kernels.hip.h)
+template <int F>
+KernelFn pick_tile(int epi, int lanes, bool big, bool halo) {
+    return per_epi(epi, [&](auto E) { return among<sk::CAP, sk::CAP_BIG>(big ? sk::CAP_BIG : sk::CAP, [&](auto C) { return per_lanes(lanes, [&](auto G) { return with_bool(halo, [&](auto H) -> KernelFn {
+        if constexpr (F == 0) return sk::k_csr_stream<E(), G(), C(), H()>;
+        else if constexpr (F == 2) return sk::k_csr_cm<E(), G(), C(), H()>;
+        else return sk::k_csr_cc16<E(), G(), C(), H()>; }); }); }); });
 }
-template <bool NT>
-SellKernelFn pick_sell_n(int epi, bool halo, bool pair) {
-    return halo ? (pair ? pick_sell_h<true, true, NT>(epi) : pick_sell_h<true, false, NT>(epi)) : (pair ? pick_sell_h<false, true, NT>(epi) : pick_sell_h<false, false, NT>(epi));
+VecKernelFn pick_vec(int epi, int lanes, bool halo) {
+    return per_epi(epi, [&](auto E) { return per_lanes(lanes, [&](auto G) { return with_bool(halo, [&](auto H) -> VecKernelFn { return sk::k_csr_vector<E(), G(), H()>; }); }); });
 }
-SellKernelFn pick_sell(int epi, bool halo, bool pair, bool nt) { return nt ? pick_sell_n<true>(epi, halo, pair) : pick_sell_n<false>(epi, halo, pair); }
-template <bool HALO, bool PAIR, bool NT, bool WIDE>
-SellKernelFn pick_sellp_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_sellp<sk::EPI_SPMV, HALO, PAIR, NT, WIDE>;
-        case sk::EPI_RESIDUAL: return sk::k_sellp<sk::EPI_RESIDUAL, HALO, PAIR, NT, WIDE>;
-        case sk::EPI_JACOBI:   return sk::k_sellp<sk::EPI_JACOBI, HALO, PAIR, NT, WIDE>;
-        case sk::EPI_CHEBY0:   return sk::k_sellp<sk::EPI_CHEBY0, HALO, PAIR, NT, WIDE>;
-        case sk::EPI_CHEBYK:   return sk::k_sellp<sk::EPI_CHEBYK, HALO, PAIR, NT, WIDE>;
-        case sk::EPI_RSWEEP:   return sk::k_sellp<sk::EPI_RSWEEP, HALO, PAIR, NT, WIDE>;
-        default:               return sk::k_sellp<sk::EPI_SUB, HALO, PAIR, NT, WIDE>;
-    }
+VecKernelFn pick_wave(int epi, int lanes, bool halo) {                       // groups of 8 lanes at least
+    return per_epi(epi, [&](auto E) { return among<8, 16, 32, 64>(std::max(8, lanes_or_64(lanes)), [&](auto G) { return with_bool(halo, [&](auto H) -> VecKernelFn { return sk::k_csr_wave<E(), G(), H()>; }); }); });
 }
-template <bool NT, bool WIDE>
-SellKernelFn pick_sellp_n(int epi, bool halo, bool pair) {
-    return halo ? (pair ? pick_sellp_h<true, true, NT, WIDE>(epi) : pick_sellp_h<true, false, NT, WIDE>(epi)) : (pair ? pick_sellp_h<false, true, NT, WIDE>(epi) : pick_sellp_h<false, false, NT, WIDE>(epi));
+SellKernelFn pick_sell(int epi, bool halo, bool pair, bool nt) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(pair, [&](auto P) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_sell<E(), H(), P(), N()>; }); }); }); });
 }
 SellKernelFn pick_sellp(int epi, bool halo, bool pair, bool nt, bool wide) {
-    if (wide) return nt ? pick_sellp_n<true, true>(epi, halo, pair) : pick_sellp_n<false, true>(epi, halo, pair);
-    return nt ? pick_sellp_n<true, false>(epi, halo, pair) : pick_sellp_n<false, false>(epi, halo, pair);
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(pair, [&](auto P) { return with_bool(nt, [&](auto N) { return with_bool(wide, [&](auto W) -> SellKernelFn {
+        return sk::k_sellp<E(), H(), P(), N(), W()>; }); }); }); }); });
 }
-template <bool HALO, bool NT>
-SellKernelFn pick_vidx_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_vidx<sk::EPI_SPMV, HALO, NT>;
-        case sk::EPI_RESIDUAL: return sk::k_vidx<sk::EPI_RESIDUAL, HALO, NT>;
-        case sk::EPI_JACOBI:   return sk::k_vidx<sk::EPI_JACOBI, HALO, NT>;
-        case sk::EPI_CHEBY0:   return sk::k_vidx<sk::EPI_CHEBY0, HALO, NT>;
-        case sk::EPI_CHEBYK:   return sk::k_vidx<sk::EPI_CHEBYK, HALO, NT>;
-        case sk::EPI_RSWEEP:   return sk::k_vidx<sk::EPI_RSWEEP, HALO, NT>;
-        default:               return sk::k_vidx<sk::EPI_SUB, HALO, NT>;
-    }
-}
-SellKernelFn pick_vidx(int epi, bool halo, bool nt) { return halo ? (nt ? pick_vidx_h<true, true>(epi) : pick_vidx_h<true, false>(epi)) : (nt ? pick_vidx_h<false, true>(epi) : pick_vidx_h<false, false>(epi)); }
-template <bool HALO, bool NT>
-SellKernelFn pick_vidxw_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_vidxw<sk::EPI_SPMV, HALO, NT>;
-        case sk::EPI_RESIDUAL: return sk::k_vidxw<sk::EPI_RESIDUAL, HALO, NT>;
-        case sk::EPI_JACOBI:   return sk::k_vidxw<sk::EPI_JACOBI, HALO, NT>;
-        case sk::EPI_CHEBY0:   return sk::k_vidxw<sk::EPI_CHEBY0, HALO, NT>;
-        case sk::EPI_CHEBYK:   return sk::k_vidxw<sk::EPI_CHEBYK, HALO, NT>;
-        case sk::EPI_RSWEEP:   return sk::k_vidxw<sk::EPI_RSWEEP, HALO, NT>;
-        default:               return sk::k_vidxw<sk::EPI_SUB, HALO, NT>;
-    }
-}
-SellKernelFn pick_vidxw(int epi, bool halo, bool nt) { return halo ? (nt ? pick_vidxw_h<true, true>(epi) : pick_vidxw_h<true, false>(epi)) : (nt ? pick_vidxw_h<false, true>(epi) : pick_vidxw_h<false, false>(epi)); }
-template <bool HALO, bool PAIR, bool NT>
-SellKernelFn pick_sellpx_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_sellpx<sk::EPI_SPMV, HALO, PAIR, NT>;
-        case sk::EPI_RESIDUAL: return sk::k_sellpx<sk::EPI_RESIDUAL, HALO, PAIR, NT>;
-        case sk::EPI_JACOBI:   return sk::k_sellpx<sk::EPI_JACOBI, HALO, PAIR, NT>;
-        case sk::EPI_CHEBY0:   return sk::k_sellpx<sk::EPI_CHEBY0, HALO, PAIR, NT>;
-        case sk::EPI_CHEBYK:   return sk::k_sellpx<sk::EPI_CHEBYK, HALO, PAIR, NT>;
-        case sk::EPI_RSWEEP:   return sk::k_sellpx<sk::EPI_RSWEEP, HALO, PAIR, NT>;
-        default:               return sk::k_sellpx<sk::EPI_SUB, HALO, PAIR, NT>;
-    }
-}
-template <bool NT>
-SellKernelFn pick_sellpx_n(int epi, bool halo, bool pair) {
-    return halo ? (pair ? pick_sellpx_h<true, true, NT>(epi) : pick_sellpx_h<true, false, NT>(epi)) : (pair ? pick_sellpx_h<false, true, NT>(epi) : pick_sellpx_h<false, false, NT>(epi));
-}
-SellKernelFn pick_sellpx(int epi, bool halo, bool pair, bool nt) { return nt ? pick_sellpx_n<true>(epi, halo, pair) : pick_sellpx_n<false>(epi, halo, pair); }
-using XldsKernelFn = void (*)(const sk::SpmvArgs, const sk::XldsArgs);
-template <int EPI, bool HALO>
-XldsKernelFn pick_xlds_g(int lanes) {
-    return lanes <= 4 ? sk::k_csr_xlds<EPI, 4, HALO> : lanes <= 8 ? sk::k_csr_xlds<EPI, 8, HALO> : lanes <= 16 ? sk::k_csr_xlds<EPI, 16, HALO> : lanes <= 32 ? sk::k_csr_xlds<EPI, 32, HALO>
-                                                                                                         : sk::k_csr_xlds<EPI, 64, HALO>;
-}
-template <bool HALO>
-XldsKernelFn pick_xlds_h(int epi, int lanes) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return pick_xlds_g<sk::EPI_SPMV, HALO>(lanes);
-        case sk::EPI_RESIDUAL: return pick_xlds_g<sk::EPI_RESIDUAL, HALO>(lanes);
-        case sk::EPI_JACOBI:   return pick_xlds_g<sk::EPI_JACOBI, HALO>(lanes);
-        case sk::EPI_CHEBY0:   return pick_xlds_g<sk::EPI_CHEBY0, HALO>(lanes);
-        case sk::EPI_CHEBYK:   return pick_xlds_g<sk::EPI_CHEBYK, HALO>(lanes);
-        case sk::EPI_RSWEEP:   return pick_xlds_g<sk::EPI_RSWEEP, HALO>(lanes);
-        default:               return pick_xlds_g<sk::EPI_SUB, HALO>(lanes);
-    }
-}
-template <bool HALO, bool NT, bool WIDE, bool PRE = false>
-SellKernelFn pick_sellp2_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_sellp2<sk::EPI_SPMV, HALO, NT, WIDE, false>;
-        case sk::EPI_RESIDUAL: return sk::k_sellp2<sk::EPI_RESIDUAL, HALO, NT, WIDE, PRE>;
-        case sk::EPI_JACOBI:   return sk::k_sellp2<sk::EPI_JACOBI, HALO, NT, WIDE, PRE>;
-        case sk::EPI_CHEBY0:   return sk::k_sellp2<sk::EPI_CHEBY0, HALO, NT, WIDE, false>;
-        case sk::EPI_CHEBYK:   return sk::k_sellp2<sk::EPI_CHEBYK, HALO, NT, WIDE, false>;
-        case sk::EPI_RSWEEP:   return sk::k_sellp2<sk::EPI_RSWEEP, HALO, NT, WIDE, false>;
-        default:               return sk::k_sellp2<sk::EPI_SUB, HALO, NT, WIDE, false>;
-    }
-}
+// PRE exists for the residual and the Jacobi sweep only, and only without a halo
 template <bool WIDE>
 SellKernelFn pick_sellp2(int epi, bool halo, bool nt, bool pre = false) {
-    if (pre && !halo) return nt ? pick_sellp2_h<false, true, WIDE, true>(epi) : pick_sellp2_h<false, false, WIDE, true>(epi);
-    return halo ? (nt ? pick_sellp2_h<true, true, WIDE>(epi) : pick_sellp2_h<true, false, WIDE>(epi)) : (nt ? pick_sellp2_h<false, true, WIDE>(epi) : pick_sellp2_h<false, false, WIDE>(epi));
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) { return with_bool(pre, [&](auto R) -> SellKernelFn {
+        return sk::k_sellp2<E(), H(), N(), WIDE, R() && !H() && (E() == sk::EPI_RESIDUAL || E() == sk::EPI_JACOBI)>; }); }); }); });
 }
-template <bool HALO, bool NT>
-SellKernelFn pick_rowt_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_rowt<sk::EPI_SPMV, HALO, NT>;
-        case sk::EPI_RESIDUAL: return sk::k_rowt<sk::EPI_RESIDUAL, HALO, NT>;
-        case sk::EPI_JACOBI:   return sk::k_rowt<sk::EPI_JACOBI, HALO, NT>;
-        case sk::EPI_CHEBY0:   return sk::k_rowt<sk::EPI_CHEBY0, HALO, NT>;
-        case sk::EPI_CHEBYK:   return sk::k_rowt<sk::EPI_CHEBYK, HALO, NT>;
-        case sk::EPI_RSWEEP:   return sk::k_rowt<sk::EPI_RSWEEP, HALO, NT>;
-        default:               return sk::k_rowt<sk::EPI_SUB, HALO, NT>;
-    }
+SellKernelFn pick_sellpx(int epi, bool halo, bool pair, bool nt) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(pair, [&](auto P) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_sellpx<E(), H(), P(), N()>; }); }); }); });
 }
-using SellxKernelFn = void (*)(const sk::SpmvArgs, const sk::SellxArgs);
-template <bool HALO>
-SellxKernelFn pick_sellx_h(int epi) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return sk::k_sellx<sk::EPI_SPMV, HALO>;
-        case sk::EPI_RESIDUAL: return sk::k_sellx<sk::EPI_RESIDUAL, HALO>;
-        case sk::EPI_JACOBI:   return sk::k_sellx<sk::EPI_JACOBI, HALO>;
-        case sk::EPI_CHEBY0:   return sk::k_sellx<sk::EPI_CHEBY0, HALO>;
-        case sk::EPI_CHEBYK:   return sk::k_sellx<sk::EPI_CHEBYK, HALO>;
-        case sk::EPI_RSWEEP:   return sk::k_sellx<sk::EPI_RSWEEP, HALO>;
-        default:               return sk::k_sellx<sk::EPI_SUB, HALO>;
-    }
+SellKernelFn pick_vidx(int epi, bool halo, bool nt) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_vidx<E(), H(), N()>; }); }); });
 }
-XldsKernelFn pick_xlds(int epi, int lanes, bool halo) { return halo ? pick_xlds_h<true>(epi, lanes) : pick_xlds_h<false>(epi, lanes); }
-// k_csr_xldsr: four rows per group step (short rows), 4 / 8 / 16 lanes per group
-template <int EPI, bool HALO>
-XldsKernelFn pick_xldsr_g(int lanes) {
-    // (eight rows per step were tried: 128 registers per lane do not hold them -- 136 bytes of scratch per lane, 110 against 94.5 us)
-    return lanes <= 4 ? sk::k_csr_xlds<EPI, 4, HALO, 4> : lanes <= 8 ? sk::k_csr_xlds<EPI, 8, HALO, 4> : lanes <= 16 ? sk::k_csr_xlds<EPI, 16, HALO, 4> : sk::k_csr_xlds<EPI, 32, HALO, 4>;
+SellKernelFn pick_vidxw(int epi, bool halo, bool nt) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_vidxw<E(), H(), N()>; }); }); });
 }
-template <bool HALO>
-XldsKernelFn pick_xldsr_h(int epi, int lanes) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return pick_xldsr_g<sk::EPI_SPMV, HALO>(lanes);
-        case sk::EPI_RESIDUAL: return pick_xldsr_g<sk::EPI_RESIDUAL, HALO>(lanes);
-        case sk::EPI_JACOBI:   return pick_xldsr_g<sk::EPI_JACOBI, HALO>(lanes);
-        case sk::EPI_CHEBY0:   return pick_xldsr_g<sk::EPI_CHEBY0, HALO>(lanes);
-        case sk::EPI_CHEBYK:   return pick_xldsr_g<sk::EPI_CHEBYK, HALO>(lanes);
-        case sk::EPI_RSWEEP:   return pick_xldsr_g<sk::EPI_RSWEEP, HALO>(lanes);
-        default:               return pick_xldsr_g<sk::EPI_SUB, HALO>(lanes);
-    }
+SellKernelFn pick_rowt(int epi, bool halo, bool nt) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_rowt<E(), H(), N()>; }); }); });
 }
-XldsKernelFn pick_xldsr(int epi, int lanes, bool halo) { return halo ? pick_xldsr_h<true>(epi, lanes) : pick_xldsr_h<false>(epi, lanes); }
+SellxKernelFn pick_sellx(int epi, bool halo) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) -> SellxKernelFn { return sk::k_sellx<E(), H()>; }); });
+}
+XldsKernelFn pick_xlds(int epi, int lanes, bool halo) {
+    return per_epi(epi, [&](auto E) { return among<4, 8, 16, 32, 64>(lanes_up(lanes, 4, 64), [&](auto G) { return with_bool(halo, [&](auto H) -> XldsKernelFn { return sk::k_csr_xlds<E(), G(), H()>; }); }); });
+}
+// k_csr_xldsr: four rows per group step (short rows), 4 / 8 / 16 / 32 lanes per group
+// (eight rows per step were tried: 128 registers per lane do not hold them -- 136 bytes of scratch per lane, 110 against 94.5 us)
+XldsKernelFn pick_xldsr(int epi, int lanes, bool halo) {
+    return per_epi(epi, [&](auto E) { return among<4, 8, 16, 32>(lanes_up(lanes, 4, 32), [&](auto G) { return with_bool(halo, [&](auto H) -> XldsKernelFn { return sk::k_csr_xlds<E(), G(), H(), 4>; }); }); });
+}
+DenseKernelFn pick_dense(int epi) {
+    return per_epi(epi, [&](auto E) -> DenseKernelFn { return sk::k_dense_rows<E()>; });
+}
+DenseHaloKernelFn pick_dense_halo(int epi) {
+    return per_epi_no_rsweep(epi, [&](auto E) -> DenseHaloKernelFn { return sk::k_dense_rows_halo<E()>; });
+}
+BndKernelFn pick_bnd(int epi, int lanes) {
+    return per_epi_no_rsweep(epi, [&](auto E) { return per_lanes(lanes, [&](auto G) -> BndKernelFn { return sk::k_csr_boundary<E(), G()>; }); });
+}
+// launch what a picker returned for the caller's `epi`, or fail
+#define SGPU_LAUNCH_PICKED(family, k, ...)                                                                            \
+    do {                                                                                                             \
+        const auto k_ = (k);                                                                                         \
+        if (!k_) return fail(SGPU_ERR_STATE, "no %s kernel for epilogue %d", family, epi);                           \
+        SGPU_LAUNCH(k_, __VA_ARGS__);                                                                                \
+    } while (0)
+
+// what every SpMV launch shares: the vectors and the epilogue's operands; a form then sets its own fields, all others stay zero
+sk::SpmvArgs spmv_args(const double *x, double *y, const EpiArgs &e) {
+    sk::SpmvArgs a{};
+    a.x = x; a.y = y; a.rhs = e.rhs; a.inv_diag = e.inv_diag; a.u = e.u; a.d = e.d; a.y2 = e.y2; a.c0 = e.c0; a.c1 = e.c1; a.cc_ob = 12;
+    return a;
+}
+
+// The row-pattern forms (variants 11, 14, 15, 17): non-temporal streams once the stored operator (values, pattern ids, x, y) is beyond
+// the 256 MiB Infinity Cache, or as SAENA_SELLP_NT says; the first resident_slices slices keep their plain loads (SpmvArgs::nt_from)
+bool row_pattern_nt(sk::SpmvArgs &a, int64_t stored_bytes, int nslices, double bytes_per_slice) {
+    static const int nt_env = std::getenv("SAENA_SELLP_NT") ? std::atoi(std::getenv("SAENA_SELLP_NT")) : -1;
+    const bool nt = nt_env >= 0 ? nt_env != 0 : stored_bytes > (int64_t)256 * 1024 * 1024;
+    a.nt_from = nt ? resident_slices(nslices, bytes_per_slice) : 0;
+    return nt;
+}
 
 int launch_part(const CsrPart &P, int epi, const double *x, double *y, const EpiArgs &e, const unsigned *skip = nullptr, uint64_t seq = 0) {
     if (P.nblk == 0) return SGPU_OK;
-    sk::SpmvArgs a;
+    sk::SpmvArgs a = spmv_args(x, y, e);
     a.flag_x = seq ? g.kflag_x : nullptr; a.seq = seq;
     a.row_ptr = P.row_ptr; a.col = P.col; a.val = P.val;
-    a.x = x; a.y = y; a.rhs = e.rhs; a.inv_diag = e.inv_diag; a.u = e.u; a.d = e.d; a.y2 = e.y2;
-    a.c0 = e.c0; a.c1 = e.c1; a.skip = skip;
-    a.segtab = nullptr; a.segptr = nullptr; a.ccol = nullptr; a.cc_ob = 12; a.dst = nullptr; a.cmptr = nullptr;
-    a.ptab = nullptr; a.pt_w = 0; a.pt_n = 0; a.ncols = P.ncols; a.nt_from = 0; a.uw = 0; a.rbase = nullptr;
-    a.vcode = nullptr; a.vcptr = nullptr; a.vdict = nullptr; a.vdptr = nullptr;
+    a.skip = skip; a.ncols = P.ncols;
     static const int st_plain_env = std::getenv("SAENA_STORE_PLAIN") ? std::atoi(std::getenv("SAENA_STORE_PLAIN")) : 0;
     a.st_plain = st_plain_env;
     static const int nt_rt = std::getenv("SAENA_STREAM_NT") ? std::atoi(std::getenv("SAENA_STREAM_NT")) : 0;
     a.nt = nt_rt == 1 || (nt_rt == 2 && 12 * P.nnz > (int64_t)256 * 1024 * 1024) ? 1 : 0;
     const bool halo = skip != nullptr || seq != 0;
-    if (P.variant == 5) {                                         // dense rows, one wave per row
+    switch (P.variant) {
+    default: {                                                    // 0, 1: 32-bit columns, 16 / 32 KiB tiles
+        const bool big = P.variant == 1;
+        a.blk_row = big ? P.blk_row_big : P.blk_row;
+        a.nblk = big ? P.nblk_big : P.nblk;
+        SGPU_LAUNCH_PICKED("k_csr_stream", pick_tile<0>(epi, P.lanes, big, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
+    } break;
+    case 2: {                                                     // vector CSR
+        const int rpb = sk::BLOCK / P.lanes;
+        a.blk_row = nullptr; a.nblk = 0;
+        SGPU_LAUNCH_PICKED("k_csr_vector", pick_vec(epi, P.lanes, halo), dim3((P.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
+    } break;
+    case 3: case 4: {                                             // 16-bit compressed columns
+        const int k = P.variant - 3;
+        if (!P.cc_ok[k]) return fail(SGPU_ERR_STATE, "compressed columns of plan %d were not built", k);
+        a.blk_row = k ? P.blk_row_big : P.blk_row;
+        a.nblk = k ? P.nblk_big : P.nblk;
+        a.segtab = P.segtab[k]; a.segptr = P.segptr[k]; a.ccol = P.ccol[k]; a.cc_ob = P.cc_ob[k];
+        SGPU_LAUNCH_PICKED("k_csr_cc16", pick_tile<1>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
+    } break;
+    case 5: {                                                     // dense rows, one wave per row
         if (!P.dense) return fail(SGPU_ERR_STATE, "the dense form was not built");
         if (halo) return fail(SGPU_ERR_STATE, "the dense form serves operators without a halo");
         a.blk_row = nullptr; a.nblk = 0;
-        void (*kd)(const sk::SpmvArgs, const double *, int, int) =
-            epi == sk::EPI_SPMV ? sk::k_dense_rows<sk::EPI_SPMV> : epi == sk::EPI_RESIDUAL ? sk::k_dense_rows<sk::EPI_RESIDUAL>
-            : epi == sk::EPI_JACOBI ? sk::k_dense_rows<sk::EPI_JACOBI> : epi == sk::EPI_CHEBY0 ? sk::k_dense_rows<sk::EPI_CHEBY0>
-            : epi == sk::EPI_CHEBYK ? sk::k_dense_rows<sk::EPI_CHEBYK> : epi == sk::EPI_RSWEEP ? sk::k_dense_rows<sk::EPI_RSWEEP> : sk::k_dense_rows<sk::EPI_SUB>;
-        SGPU_LAUNCH(kd, dim3((P.nrows + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, (const double *)P.dense, P.nrows, P.ncols);
-    } else if (P.variant == 17) {                                 // row patterns + 8-bit value codes, a lane per row
-        if (!P.vi_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the value-indexed row-pattern form was not built");
-        a.blk_row = nullptr; a.nblk = P.nslices ? P.nslices : (P.nrows + 63) / 64;
-        a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n; a.rbase = P.sp_rbase;
-        a.vcode = P.vi_code; a.vcptr = P.vi_cptr; a.vdict = P.vi_dict; a.vdptr = P.vi_dptr; a.uw = P.vi_uw8;
-        static const int nt_envv = std::getenv("SAENA_SELLP_NT") ? std::atoi(std::getenv("SAENA_SELLP_NT")) : -1;
-        const bool nt = nt_envv >= 0 ? nt_envv != 0 : P.vi_bytes > (int64_t)256 * 1024 * 1024;
-        a.nt_from = nt ? resident_slices(a.nblk, (double)P.nnz / (double)std::max(1, a.nblk)) : 0;     // (about a byte of codes per entry)
-        const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
-        if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS positions
-            const int k = P.vw_rows == 256 ? 0 : P.vw_rows == 512 ? 1 : 2, spb = P.vw_rows / 64;
-            const CsrPart::XWin &X = P.vw[k];
-            if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
-            a.ptab = reinterpret_cast<const int *>(X.tab); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
-            SGPU_LAUNCH(pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, P.nrows);
-        } else
-        SGPU_LAUNCH(pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
-    } else if (P.variant == 15) {                                 // k_sellp with x in LDS windows
-        if (!P.spx_ok || !P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
-        a.blk_row = nullptr; a.nblk = P.nslices;
-        a.val = P.sl_val; a.cmptr = P.sl_ptr; a.dst = P.spx_pat; a.ptab = reinterpret_cast<const int *>(P.spx_tab); a.pt_w = 0; a.pt_n = P.sp_n;
-        a.segtab = P.spx_win; a.segptr = P.spx_wgptr; a.ncols = P.ncols;
-        static const int nt_envx = std::getenv("SAENA_SELLP_NT") ? std::atoi(std::getenv("SAENA_SELLP_NT")) : -1;
-        const bool nt = nt_envx >= 0 ? nt_envx != 0 : P.sp_bytes > (int64_t)256 * 1024 * 1024;
-        a.nt_from = nt ? resident_slices(P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices)) : 0;
-        SGPU_LAUNCH(pick_sellpx(epi, halo, P.sl_pair, nt), dim3((P.nslices + sk::SPX_ROWS / 64 - 1) / (sk::SPX_ROWS / 64)), dim3(sk::SPX_BLOCK), 0, g.cs, a, P.nrows);
-    } else if (P.variant == 14) {                                 // k_sellp with a lane per two rows
-        if (!P.sp2_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the row-paired row-pattern form was not built");
-        a.blk_row = nullptr; a.nblk = P.sp2_nslices;
-        a.val = P.sp2_val; a.cmptr = P.sp2_ptr; a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
-        static const int nt_env2 = std::getenv("SAENA_SELLP_NT") ? std::atoi(std::getenv("SAENA_SELLP_NT")) : -1;
-        const bool nt = nt_env2 >= 0 ? nt_env2 != 0 : P.sp_bytes > (int64_t)256 * 1024 * 1024;
-        a.nt_from = nt ? resident_slices(P.sp2_nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.sp2_nslices)) : 0;
-        a.ncols = P.ncols;
-        a.uw = P.sp2_uw;
-        static const int pre_env = std::getenv("SAENA_SELLP2_PRE") ? std::atoi(std::getenv("SAENA_SELLP2_PRE")) : 1;
-        const bool pre = pre_env != 0 && !halo;
-        if (P.sp_wide) {                                          // a table per workgroup: 512 threads, 8 slices of 128 rows
-            a.segptr = P.sp_wgptr;
-            SGPU_LAUNCH(pick_sellp2<true>(epi, halo, nt, pre), dim3((P.sp2_nslices + 7) / 8), dim3(sk::SPW2_BLOCK), (size_t)P.sp_w * sizeof(int), g.cs, a, P.nrows);
-        } else
-        SGPU_LAUNCH(pick_sellp2<false>(epi, halo, nt, pre), dim3((P.sp2_nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
-    } else if (P.variant == 13) {                                 // row templates: a thread per row, no operator stream at all
-        if (!P.rt_ok) return fail(SGPU_ERR_STATE, "the row-template form was not built");
+        SGPU_LAUNCH_PICKED("k_dense_rows", pick_dense(epi), dim3((P.nrows + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, (const double *)P.dense, P.nrows, P.ncols);
+    } break;
+    case 6: {                                                     // wave-streamed long rows, 16-byte loads
+        const int gl = std::max(8, P.lanes), rpb = sk::BLOCK / gl;
         a.blk_row = nullptr; a.nblk = 0;
-        a.val = P.rt_vtab; a.dst = P.rt_pat; a.ptab = P.rt_itab; a.pt_w = P.rt_w; a.pt_n = P.rt_n;
-        const bool nt = 26 * (int64_t)P.nrows > (int64_t)256 * 1024 * 1024;       // ids + x + y (+ rhs) beyond the Infinity Cache
-        const size_t lds = (size_t)P.rt_n * ((size_t)P.rt_w * 8 + (size_t)(P.rt_w + 1) * 4);
-        SellKernelFn k = halo ? (nt ? pick_rowt_h<true, true>(epi) : pick_rowt_h<true, false>(epi)) : (nt ? pick_rowt_h<false, true>(epi) : pick_rowt_h<false, false>(epi));
-        SGPU_LAUNCH(k, dim3((P.nrows + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
-    } else if (P.variant == 12) {                                 // sliced ELLPACK in the LDS windows, a workgroup per CU
-        if (!P.sx_ok || !P.xl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK-in-LDS form was not built");
-        a.blk_row = P.xl_blk; a.nblk = P.xl_nblk;
-        sk::SellxArgs w;
-        w.info = P.xl_info; w.bptr = P.sx_bptr; w.sptr = P.sx_sptr; w.meta = P.sx_meta; w.val = P.sx_val; w.col = P.sx_col; w.acc = P.xl_acc; w.ncols = P.ncols;
-        w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0;
-        if (nt_rt == 0 && !std::getenv("SAENA_STREAM_NT")) a.nt = 10 * P.nnz > (int64_t)256 * 1024 * 1024 ? 1 : 0;      // non-temporal streams beyond the Infinity Cache (438 -> 426 us)
-        SGPU_LAUNCH(halo ? pick_sellx_h<true>(epi) : pick_sellx_h<false>(epi), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
-    } else if (P.variant == 10 || P.variant == 16) {              // x in LDS, a workgroup per CU (16: four rows per group step -- short rows)
-        if (!P.xl_ok || !P.xl_col) return fail(SGPU_ERR_STATE, "the x-in-LDS form was not built");
-        a.blk_row = P.xl_blk; a.nblk = P.xl_nblk; a.ccol = P.xl_col;
-        sk::XldsArgs w;
-        w.info = P.xl_info; w.tab = P.xl_tab; w.acc = P.xl_acc; w.ncols = P.ncols;
-        w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0; w.ord = P.xl_ord;
-        SGPU_LAUNCH(P.variant == 16 ? pick_xldsr(epi, P.lanes, halo) : pick_xlds(epi, P.lanes, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
-    } else if (P.variant == 11) {                                 // sliced ELLPACK values + row patterns, a lane per row
-        if (!P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form was not built");
-        a.blk_row = nullptr; a.nblk = P.nslices;
-        a.val = P.sl_val; a.cmptr = P.sl_ptr; a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
-        a.rbase = P.sp_rbase;
-        // non-temporal streams once the stored operator (values, pattern ids, x, y) is beyond the 256 MiB Infinity Cache
-        static const int nt_env = std::getenv("SAENA_SELLP_NT") ? std::atoi(std::getenv("SAENA_SELLP_NT")) : -1;
-        const bool nt = nt_env >= 0 ? nt_env != 0 : P.sp_bytes > (int64_t)256 * 1024 * 1024;
-        a.nt_from = nt ? resident_slices(P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices)) : 0;
-        a.uw = P.sl_uw;
-        if (P.sp_wide) {                                          // a table per workgroup: 1024 threads, 16 slices of 64 rows
-            a.segptr = P.sp_wgptr;
-            SGPU_LAUNCH(pick_sellp(epi, halo, P.sl_pair, nt, true), dim3((P.nslices + 15) / 16), dim3(sk::SPW_BLOCK), (size_t)P.sp_w * sizeof(int), g.cs, a, P.nrows);
-        } else
-        SGPU_LAUNCH(pick_sellp(epi, halo, P.sl_pair, nt, false), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
-    } else if (P.variant == 9) {                                  // sliced ELLPACK, a lane per row
+        SGPU_LAUNCH_PICKED("k_csr_wave", pick_wave(epi, gl, halo), dim3((P.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
+    } break;
+    case 7: case 8: {                                             // compressed columns, entries in column order inside a block
+        const int k = P.variant - 7;
+        if (!P.cm_ok[k]) return fail(SGPU_ERR_STATE, "the column-major form of plan %d was not built", k);
+        a.blk_row = k ? P.blk_row_big : P.blk_row;
+        a.nblk = k ? P.nblk_big : P.nblk;
+        a.segtab = P.segtab[k]; a.segptr = P.segptr[k]; a.cc_ob = P.cc_ob[k];
+        a.val = P.cm_val[k]; a.ccol = P.cm_col[k]; a.dst = P.cm_dst[k]; a.cmptr = P.cm_ptr[k];
+        SGPU_LAUNCH_PICKED("k_csr_cm", pick_tile<2>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
+    } break;
+    case 9: {                                                     // sliced ELLPACK, a lane per row
         if (!P.sl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK form was not built");
         a.blk_row = P.sl_sorted ? P.sl_perm : nullptr; a.nblk = P.nslices;
         a.val = P.sl_val; a.ccol = P.sl_col; a.segtab = P.sl_base; a.segptr = P.sl_segptr; a.cc_ob = P.sl_ob; a.cmptr = P.sl_ptr; a.dst = P.sl_len;
@@ -1878,76 +1687,96 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         static const int sorted_plain = std::getenv("SAENA_SELL_SORTED_PLAIN_STORES") ? std::atoi(std::getenv("SAENA_SELL_SORTED_PLAIN_STORES")) : 1;
         if (P.sl_sorted && sorted_plain) a.st_plain = 1;
         a.nt_from = nt ? resident_slices(P.nslices, 10.0 * (double)P.nnz / (double)std::max(1, P.nslices)) : 0;
-        SGPU_LAUNCH(pick_sell(epi, halo, P.sl_pair, nt), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
-    } else if (P.variant == 7 || P.variant == 8) {                       // compressed columns, entries in column order inside a block
-        const int k = P.variant - 7;
-        if (!P.cm_ok[k]) return fail(SGPU_ERR_STATE, "the column-major form of plan %d was not built", k);
-        a.blk_row = k ? P.blk_row_big : P.blk_row;
-        a.nblk = k ? P.nblk_big : P.nblk;
-        a.segtab = P.segtab[k]; a.segptr = P.segptr[k]; a.cc_ob = P.cc_ob[k];
-        a.val = P.cm_val[k]; a.ccol = P.cm_col[k]; a.dst = P.cm_dst[k]; a.cmptr = P.cm_ptr[k];
-        SGPU_LAUNCH(pick<2>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
-    } else if (P.variant == 3 || P.variant == 4) {                       // 16-bit compressed columns
-        const int k = P.variant - 3;
-        if (!P.cc_ok[k]) return fail(SGPU_ERR_STATE, "compressed columns of plan %d were not built", k);
-        a.blk_row = k ? P.blk_row_big : P.blk_row;
-        a.nblk = k ? P.nblk_big : P.nblk;
-        a.segtab = P.segtab[k]; a.segptr = P.segptr[k]; a.ccol = P.ccol[k]; a.cc_ob = P.cc_ob[k];
-        SGPU_LAUNCH(pick<1>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
-    } else if (P.variant == 6) {                                  // wave-streamed long rows, 16-byte loads
-        const int gl = std::max(8, P.lanes), rpb = sk::BLOCK / gl;
+        SGPU_LAUNCH_PICKED("k_sell", pick_sell(epi, halo, P.sl_pair, nt), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
+    } break;
+    case 10: case 16: {                                           // x in LDS, a workgroup per CU (16: four rows per group step -- short rows)
+        if (!P.xl_ok || !P.xl_col) return fail(SGPU_ERR_STATE, "the x-in-LDS form was not built");
+        a.blk_row = P.xl_blk; a.nblk = P.xl_nblk; a.ccol = P.xl_col;
+        sk::XldsArgs w;
+        w.info = P.xl_info; w.tab = P.xl_tab; w.acc = P.xl_acc; w.ncols = P.ncols;
+        w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0; w.ord = P.xl_ord;
+        SGPU_LAUNCH_PICKED("k_csr_xlds", P.variant == 16 ? pick_xldsr(epi, P.lanes, halo) : pick_xlds(epi, P.lanes, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
+    } break;
+    case 11: {                                                    // sliced ELLPACK values + row patterns, a lane per row
+        if (!P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form was not built");
+        a.blk_row = nullptr; a.nblk = P.nslices;
+        a.val = P.sl_val; a.cmptr = P.sl_ptr; a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
+        a.rbase = P.sp_rbase;
+        const bool nt = row_pattern_nt(a, P.sp_bytes, P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices));
+        a.uw = P.sl_uw;
+        if (P.sp_wide) {                                          // a table per workgroup: 1024 threads, 16 slices of 64 rows
+            a.segptr = P.sp_wgptr;
+            SGPU_LAUNCH_PICKED("k_sellp", pick_sellp(epi, halo, P.sl_pair, nt, true), dim3((P.nslices + 15) / 16), dim3(sk::SPW_BLOCK), (size_t)P.sp_w * sizeof(int), g.cs, a, P.nrows);
+        } else
+        SGPU_LAUNCH_PICKED("k_sellp", pick_sellp(epi, halo, P.sl_pair, nt, false), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
+    } break;
+    case 12: {                                                    // sliced ELLPACK in the LDS windows, a workgroup per CU
+        if (!P.sx_ok || !P.xl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK-in-LDS form was not built");
+        a.blk_row = P.xl_blk; a.nblk = P.xl_nblk;
+        sk::SellxArgs w;
+        w.info = P.xl_info; w.bptr = P.sx_bptr; w.sptr = P.sx_sptr; w.meta = P.sx_meta; w.val = P.sx_val; w.col = P.sx_col; w.acc = P.xl_acc; w.ncols = P.ncols;
+        w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0;
+        if (nt_rt == 0 && !std::getenv("SAENA_STREAM_NT")) a.nt = 10 * P.nnz > (int64_t)256 * 1024 * 1024 ? 1 : 0;      // non-temporal streams beyond the Infinity Cache (438 -> 426 us)
+        SGPU_LAUNCH_PICKED("k_sellx", pick_sellx(epi, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
+    } break;
+    case 13: {                                                    // row templates: a thread per row, no operator stream at all
+        if (!P.rt_ok) return fail(SGPU_ERR_STATE, "the row-template form was not built");
         a.blk_row = nullptr; a.nblk = 0;
-        SGPU_LAUNCH(pick_wave(epi, gl, halo), dim3((P.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
-    } else if (P.variant == 2) {                                  // vector CSR
-        const int rpb = sk::BLOCK / P.lanes;
-        a.blk_row = nullptr; a.nblk = 0;
-        SGPU_LAUNCH(pick_vec(epi, P.lanes, halo), dim3((P.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
-    } else {                                                      // 32-bit columns, 16 / 32 KiB tiles
-        const bool big = P.variant == 1;
-        a.blk_row = big ? P.blk_row_big : P.blk_row;
-        a.nblk = big ? P.nblk_big : P.nblk;
-        SGPU_LAUNCH(pick<0>(epi, P.lanes, big, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
+        a.val = P.rt_vtab; a.dst = P.rt_pat; a.ptab = P.rt_itab; a.pt_w = P.rt_w; a.pt_n = P.rt_n;
+        const bool nt = 26 * (int64_t)P.nrows > (int64_t)256 * 1024 * 1024;       // ids + x + y (+ rhs) beyond the Infinity Cache
+        const size_t lds = (size_t)P.rt_n * ((size_t)P.rt_w * 8 + (size_t)(P.rt_w + 1) * 4);
+        SGPU_LAUNCH_PICKED("k_rowt", pick_rowt(epi, halo, nt), dim3((P.nrows + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
+    } break;
+    case 14: {                                                    // k_sellp with a lane per two rows
+        if (!P.sp2_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the row-paired row-pattern form was not built");
+        a.blk_row = nullptr; a.nblk = P.sp2_nslices;
+        a.val = P.sp2_val; a.cmptr = P.sp2_ptr; a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
+        const bool nt = row_pattern_nt(a, P.sp_bytes, P.sp2_nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.sp2_nslices));
+        a.ncols = P.ncols;
+        a.uw = P.sp2_uw;
+        static const int pre_env = std::getenv("SAENA_SELLP2_PRE") ? std::atoi(std::getenv("SAENA_SELLP2_PRE")) : 1;
+        const bool pre = pre_env != 0 && !halo;
+        if (P.sp_wide) {                                          // a table per workgroup: 512 threads, 8 slices of 128 rows
+            a.segptr = P.sp_wgptr;
+            SGPU_LAUNCH_PICKED("k_sellp2", pick_sellp2<true>(epi, halo, nt, pre), dim3((P.sp2_nslices + 7) / 8), dim3(sk::SPW2_BLOCK), (size_t)P.sp_w * sizeof(int), g.cs, a, P.nrows);
+        } else
+        SGPU_LAUNCH_PICKED("k_sellp2", pick_sellp2<false>(epi, halo, nt, pre), dim3((P.sp2_nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
+    } break;
+    case 15: {                                                    // k_sellp with x in LDS windows
+        if (!P.spx_ok || !P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
+        a.blk_row = nullptr; a.nblk = P.nslices;
+        a.val = P.sl_val; a.cmptr = P.sl_ptr; a.dst = P.spx_pat; a.ptab = reinterpret_cast<const int *>(P.spx_tab); a.pt_w = 0; a.pt_n = P.sp_n;
+        a.segtab = P.spx_win; a.segptr = P.spx_wgptr; a.ncols = P.ncols;
+        const bool nt = row_pattern_nt(a, P.sp_bytes, P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices));
+        SGPU_LAUNCH_PICKED("k_sellpx", pick_sellpx(epi, halo, P.sl_pair, nt), dim3((P.nslices + sk::SPX_ROWS / 64 - 1) / (sk::SPX_ROWS / 64)), dim3(sk::SPX_BLOCK), 0, g.cs, a, P.nrows);
+    } break;
+    case 17: {                                                    // row patterns + 8-bit value codes, a lane per row
+        if (!P.vi_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the value-indexed row-pattern form was not built");
+        a.blk_row = nullptr; a.nblk = P.nslices ? P.nslices : (P.nrows + 63) / 64;
+        a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n; a.rbase = P.sp_rbase;
+        a.vcode = P.vi_code; a.vcptr = P.vi_cptr; a.vdict = P.vi_dict; a.vdptr = P.vi_dptr; a.uw = P.vi_uw8;
+        const bool nt = row_pattern_nt(a, P.vi_bytes, a.nblk, (double)P.nnz / (double)std::max(1, a.nblk));     // (about a byte of codes per entry)
+        const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
+        if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS positions
+            const int k = P.vw_rows == 256 ? 0 : P.vw_rows == 512 ? 1 : 2, spb = P.vw_rows / 64;
+            const CsrPart::XWin &X = P.vw[k];
+            if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
+            a.ptab = reinterpret_cast<const int *>(X.tab); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
+            SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, P.nrows);
+        } else
+        SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
+    } break;
     }
     HIPCHK(hipGetLastError());
     return SGPU_OK;
-}
-
-using BndKernelFn = void (*)(const sk::BoundaryArgs);
-template <int EPI>
-BndKernelFn pick_bnd_g(int lanes) {
-    switch (lanes) {
-        case 1:  return sk::k_csr_boundary<EPI, 1>;
-        case 2:  return sk::k_csr_boundary<EPI, 2>;
-        case 4:  return sk::k_csr_boundary<EPI, 4>;
-        case 8:  return sk::k_csr_boundary<EPI, 8>;
-        case 16: return sk::k_csr_boundary<EPI, 16>;
-        case 32: return sk::k_csr_boundary<EPI, 32>;
-        default: return sk::k_csr_boundary<EPI, 64>;
-    }
-}
-BndKernelFn pick_bnd(int epi, int lanes) {
-    switch (epi) {
-        case sk::EPI_SPMV:     return pick_bnd_g<sk::EPI_SPMV>(lanes);
-        case sk::EPI_RESIDUAL: return pick_bnd_g<sk::EPI_RESIDUAL>(lanes);
-        case sk::EPI_JACOBI:   return pick_bnd_g<sk::EPI_JACOBI>(lanes);
-        case sk::EPI_CHEBY0:   return pick_bnd_g<sk::EPI_CHEBY0>(lanes);
-        case sk::EPI_CHEBYK:   return pick_bnd_g<sk::EPI_CHEBYK>(lanes);
-        default:               return pick_bnd_g<sk::EPI_SUB>(lanes);
-    }
 }
 
 // dense storage with a halo: all rows in one launch after the exchange (k_dense_rows_halo)
 int launch_dense_halo(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, bool halo_is_f32, hipStream_t stream) {
     if (op->M == 0) return SGPU_OK;
     if (!op->loc.dense || (!op->dense_rem && op->has_remote)) return fail(SGPU_ERR_STATE, "the dense form was not built");
-    sk::SpmvArgs a;
-    memset(&a, 0, sizeof a);
-    a.x = x; a.y = y; a.rhs = e.rhs; a.inv_diag = e.inv_diag; a.u = e.u; a.d = e.d; a.c0 = e.c0; a.c1 = e.c1; a.cc_ob = 12;
-    void (*kd)(const sk::SpmvArgs, const double *, const double *, int, int, int, const double *, const float *, int) =
-        epi == sk::EPI_SPMV ? sk::k_dense_rows_halo<sk::EPI_SPMV> : epi == sk::EPI_RESIDUAL ? sk::k_dense_rows_halo<sk::EPI_RESIDUAL>
-        : epi == sk::EPI_JACOBI ? sk::k_dense_rows_halo<sk::EPI_JACOBI> : epi == sk::EPI_CHEBY0 ? sk::k_dense_rows_halo<sk::EPI_CHEBY0>
-        : epi == sk::EPI_CHEBYK ? sk::k_dense_rows_halo<sk::EPI_CHEBYK> : sk::k_dense_rows_halo<sk::EPI_SUB>;
-    SGPU_LAUNCH(kd, dim3((op->M + 3) / 4), dim3(sk::BLOCK), 0, stream, a, (const double *)op->loc.dense, (const double *)op->dense_rem,
+    const sk::SpmvArgs a = spmv_args(x, y, e);
+    SGPU_LAUNCH_PICKED("k_dense_rows_halo", pick_dense_halo(epi), dim3((op->M + 3) / 4), dim3(sk::BLOCK), 0, stream, a, (const double *)op->loc.dense, (const double *)op->dense_rem,
                 (int)op->M, op->loc.ncols, op->has_remote ? op->recvSize : 0, (const double *)op->recv_buf, halo_is_f32 ? (const float *)op->recv_f : (const float *)nullptr,
                 op->halo_fp32 ? 1 : 0);       // (an injected halo arrives as float-rounded doubles: halo_f null, x still rounded)
     HIPCHK(hipGetLastError());
@@ -1960,15 +1789,13 @@ int launch_rows_after_exchange(sgpu_op *op, int epi, const double *x, double *y,
 int launch_boundary(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, bool halo_is_f32, hipStream_t stream) {
     if (op->rem.nrows == 0) return SGPU_OK;
     sk::BoundaryArgs b;
-    b.s.flag_x = nullptr; b.s.seq = 0;
-    b.s.row_ptr = op->loc.row_ptr; b.s.col = op->loc.col; b.s.val = op->loc.val; b.s.blk_row = nullptr; b.s.nblk = 0;
-    b.s.x = x; b.s.y = y; b.s.rhs = e.rhs; b.s.inv_diag = e.inv_diag; b.s.u = e.u; b.s.d = e.d; b.s.c0 = e.c0; b.s.c1 = e.c1;
-    b.s.skip = nullptr; b.s.segtab = nullptr; b.s.segptr = nullptr; b.s.ccol = nullptr; b.s.cc_ob = 12; b.s.dst = nullptr; b.s.cmptr = nullptr;
+    b.s = spmv_args(x, y, e);
+    b.s.row_ptr = op->loc.row_ptr; b.s.col = op->loc.col; b.s.val = op->loc.val;
     b.rows = op->rem.rows; b.nrows = op->rem.nrows;
     b.h_ptr = op->rem.row_ptr; b.h_col = op->rem.col; b.h_val = op->rem.val;
     b.halo = op->recv_buf; b.halo_f = halo_is_f32 ? op->recv_f : nullptr;
     const int rpb = sk::BLOCK / op->bnd_lanes;
-    SGPU_LAUNCH(pick_bnd(epi, op->bnd_lanes), dim3((b.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, stream, b);
+    SGPU_LAUNCH_PICKED("k_csr_boundary", pick_bnd(epi, op->bnd_lanes), dim3((b.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, stream, b);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
 }

@@ -773,7 +773,7 @@ def test_a_non_finite_halo_value_stays_in_the_receiving_rows(capi, key, monkeypa
 
 
 # ---- the switches read once per process ---------------------------------------------------------------------------------------
-NT_FORMS = ["sellp", "sellp.wide", "sellp2", "sellp2.wide", "sellpx", "vidx", "vidx.w256", "vidx.w512", "vidx.w1024"]
+NT_FORMS = ["sell", "sell.sorted", "sellp", "sellp.wide", "sellp2", "sellp2.wide", "sellpx", "vidx", "vidx.w256", "vidx.w512", "vidx.w1024"]
 NT_WORKER = r"""
 import sys, json, hashlib
 sys.path.insert(0, %(root)r)
@@ -793,11 +793,12 @@ class _Env:
 
 
 def nt_outputs(capi, monkeypatch=None):
-    """hashes of every epilogue of forms 11, 14, 15 and 17 on the Poisson and level-1 operators"""
+    """hashes of every epilogue of forms 9, 11, 14, 15 and 17 on the Poisson and level-1 operators, and on the uneven rows that
+    k_sell<sorted> is built for (SAENA_SELL_SORTED is read per build: make_gpu sets it in either process)"""
     import hashlib
     monkeypatch = monkeypatch or _Env()
     out = {}
-    for name in ("poisson13", "L1"):
+    for name in ("poisson13", "L1", "uneven"):
         p = problem(name)
         O = oracle_op(p)
         v = vectors(p)
@@ -811,12 +812,12 @@ def nt_outputs(capi, monkeypatch=None):
 
 
 def test_non_temporal_and_non_pre_instantiations_give_the_same_bits(capi, monkeypatch):
-    """SAENA_SELLP_NT and SAENA_SELLP2_PRE are read once per process: a child process with SAENA_SELLP_NT=1 SAENA_SELLP2_PRE=0
-    runs the NT instantiations of 11, 14, 15 and 17 (k_vidx and, with the x windows on, k_vidxw) and 14 without PRE on operators far
-    below the size where they switch on"""
+    """SAENA_SELL_NT, SAENA_SELLP_NT and SAENA_SELLP2_PRE are read once per process: a child process with SAENA_SELL_NT=1
+    SAENA_SELLP_NT=1 SAENA_SELLP2_PRE=0 runs the NT instantiations of 9 (k_sell, plain and sorted), 11, 14, 15 and 17 (k_vidx and,
+    with the x windows on, k_vidxw) and 14 without PRE on operators far below the size where they switch on"""
     here = nt_outputs(capi, monkeypatch)
     assert {k.split("/")[1] for k in here} == set(NT_FORMS)
-    env = dict(os.environ, SAENA_SELLP_NT="1", SAENA_SELLP2_PRE="0")
+    env = dict(os.environ, SAENA_SELL_NT="1", SAENA_SELLP_NT="1", SAENA_SELLP2_PRE="0")
     out = subprocess.run([sys.executable, "-c", NT_WORKER % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     child = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
