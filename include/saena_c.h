@@ -111,6 +111,16 @@ int  saena_debug_spgemm_result(nnz_t *c_ptr, index_t *c_col, value_t *c_val);
 int  saena_debug_spgemm_stats(long *last, long *total);
 void saena_debug_spgemm_stats_reset(void);
 
+/* ---- tests: the filter of the setup on a CSR block from plain arrays ----
+ * Rows [row_offset, row_offset + n) of a level (64-bit row pointers, global column ids, the columns of every row distinct
+ * and ascending -- checked here): off-diagonal entries with |v| <= thre leave the row and their sum, added up in row order,
+ * is added to the diagonal once; a diagonal that ends below 1e-14 in magnitude becomes 1.0; a row without a diagonal entry
+ * gets one of value 1.0 at its place in column order.  *c_nnz = entries kept; saena_debug_filter_result copies the block
+ * out: c_ptr[n + 1], c_col / c_val[*c_nnz]. */
+int  saena_debug_filter(index_t n, const nnz_t *ptr, const index_t *col, const value_t *val, double thre, index_t row_offset,
+                        nnz_t *c_nnz);
+int  saena_debug_filter_result(nnz_t *c_ptr, index_t *c_col, value_t *c_val);
+
 /* ---- transfer operators (prolong_matrix / restrict_matrix) ---- */
 typedef struct saena_transfer_h saena_transfer_h;
 /* rows/cols are GLOBAL ids of this rank's fine rows; split_row = fine partition, split_col = coarse partition */

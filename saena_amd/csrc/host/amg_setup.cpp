@@ -184,7 +184,9 @@ bool hook_wanted(spgemm_mode mode, size_t stored) {
         if (!g_spgemm_hook) throw std::runtime_error("spgemm: no device kernel is installed (host-only library, no sgpu_init, or SAENA_HOST_SPGEMM)");
         return true;
     }
-    return g_spgemm_hook && stored >= SPGEMM_HOOK_MIN;
+    // SAENA_SPGEMM_HOOK_MIN=<entries>: another threshold (tests: a small irregular hierarchy built through the device kernel)
+    static const size_t hook_min = [] { const char *e = std::getenv("SAENA_SPGEMM_HOOK_MIN"); return e ? (size_t)std::max(0L, std::atol(e)) : SPGEMM_HOOK_MIN; }();
+    return g_spgemm_hook && stored >= hook_min;
 }
 void hook_declined(spgemm_mode mode) {
     g_spgemm_last.v[SPGEMM_DECLINED] = 1;
@@ -1648,6 +1650,26 @@ void debug_spgemm(int mode, index_t a_rows, index_t b_rows, index_t b_cols, cons
     A.nrows = a_rows; A.ptr = a_ptr; A.col = a_col; A.val = a_val;
     Csr C = b_col1 ? spgemm_stacked(A, local, halo, row_offset, (spgemm_mode)mode) : spgemm(A, local, row_offset, (spgemm_mode)mode);
     if (C.ptr.empty()) C.ptr.assign((size_t)a_rows + 1, 0);
+    c_ptr = std::move(C.ptr); c_col = std::move(C.col); c_val = std::move(C.val);
+}
+
+// saena_debug_filter: the setup's filter (filter_csr) on a CSR block from plain arrays (tests): a row without a diagonal entry
+// does not come out of an assembled operator's Galerkin product, so that branch is reached from here only.
+void debug_filter(index_t n, const nnz_t *ptr, const index_t *col, const value_t *val, double thre, index_t row_offset,
+                  std::vector<nnz_t> &c_ptr, std::vector<index_t> &c_col, std::vector<value_t> &c_val) {
+    if (n < 0 || row_offset < 0 || !ptr || ptr[0] != 0) throw std::runtime_error("debug_filter: bad sizes or row pointers");
+    for (index_t i = 0; i < n; ++i) {
+        if (ptr[i + 1] < ptr[i]) throw std::runtime_error("debug_filter: the row pointers descend");
+        for (nnz_t k = ptr[i]; k < ptr[i + 1]; ++k) {
+            if (col[k] < 0) throw std::runtime_error("debug_filter: a column is negative");
+            if (k > ptr[i] && col[k - 1] >= col[k]) throw std::runtime_error("debug_filter: the columns of a row must be distinct and ascending");
+        }
+    }
+    Csr C;
+    C.nrows = n; C.ncols = n + row_offset;
+    C.ptr.assign(ptr, ptr + n + 1);
+    C.col.assign(col, col + ptr[n]); C.val.assign(val, val + ptr[n]);
+    filter_csr(C, thre, row_offset);
     c_ptr = std::move(C.ptr); c_col = std::move(C.col); c_val = std::move(C.val);
 }
 

@@ -55,6 +55,9 @@ void spgemm_stats_reset();
 void debug_spgemm(int mode, index_t a_rows, index_t b_rows, index_t b_cols, const nnz_t *a_ptr, const index_t *a_col, const value_t *a_val,
                   const nnz_t *b_ptr, const index_t *b_col, const value_t *b_val, nnz_t b_split, const index_t *b_col1, const value_t *b_val1,
                   index_t row_offset, std::vector<nnz_t> &c_ptr, std::vector<index_t> &c_col, std::vector<value_t> &c_val);
+// saena_debug_filter (include/saena_c.h): the setup's filter on rows [row_offset, row_offset + n) of a level, from plain arrays
+void debug_filter(index_t n, const nnz_t *ptr, const index_t *col, const value_t *val, double thre, index_t row_offset,
+                  std::vector<nnz_t> &c_ptr, std::vector<index_t> &c_col, std::vector<value_t> &c_val);
 // The exchange chain of one multi-rank apply in microseconds (pack -> RCCL send/recv -> boundary rows), as the GPU runtime
 // MEASURED it on this job's communicator at sgpu_init (a ping-pong with the neighbouring rank; the maximum over the
 // ranks, so every rank holds the same number); 0: not measured (host-only library, one rank).  The agglomeration model

@@ -49,6 +49,10 @@ void fill_desc(const DistLayout &L, const std::vector<value_t> *inv_diag, sgpu_o
 std::vector<nnz_t> dbg_ptr;
 std::vector<index_t> dbg_col;
 std::vector<value_t> dbg_val;
+// the block of the last saena_debug_filter, until saena_debug_filter_result fetches it
+std::vector<nnz_t> flt_ptr;
+std::vector<index_t> flt_col;
+std::vector<value_t> flt_val;
 } // namespace
 
 extern "C" {
@@ -185,6 +189,23 @@ int saena_debug_spgemm_stats(long *last, long *total) {
     return SPGEMM_NSTATS;
 }
 void saena_debug_spgemm_stats_reset(void) { spgemm_stats_reset(); }
+
+// ---- the setup's filter from plain arrays (tests); the result is fetched like a product's ----
+int saena_debug_filter(index_t n, const nnz_t *ptr, const index_t *col, const value_t *val, double thre, index_t row_offset, nnz_t *c_nnz) {
+    return guard([&] {
+        flt_ptr.clear(); flt_col.clear(); flt_val.clear();
+        debug_filter(n, ptr, col, val, thre, row_offset, flt_ptr, flt_col, flt_val);
+        if (c_nnz) *c_nnz = (nnz_t)flt_col.size();
+    });
+}
+int saena_debug_filter_result(nnz_t *c_ptr, index_t *c_col, value_t *c_val) {
+    return guard([&] {
+        if (flt_ptr.empty()) throw std::runtime_error("saena_debug_filter_result: no filtered block to fetch");
+        std::copy(flt_ptr.begin(), flt_ptr.end(), c_ptr);
+        std::copy(flt_col.begin(), flt_col.end(), c_col);
+        std::copy(flt_val.begin(), flt_val.end(), c_val);
+    });
+}
 
 int saena_laplacian3D_set_rhs(saena_matrix_h *Ah, index_t mx, index_t my, index_t mz, value_t *rhs_local) {
     return guard([&] {

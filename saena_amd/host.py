@@ -63,6 +63,8 @@ HOST_SYMBOLS = {
     "saena_debug_spgemm_result": (C.c_int, [_VP, _VP, _VP]),
     "saena_debug_spgemm_stats": (C.c_int, [_VP, _VP]),
     "saena_debug_spgemm_stats_reset": (None, []),
+    "saena_debug_filter": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_double, C.c_int, C.POINTER(C.c_long)]),
+    "saena_debug_filter_result": (C.c_int, [_VP, _VP, _VP]),
     "saena_prolong_new": (_VP, [_VP, C.c_int, C.c_int, _PI, _PI, _PI, _PI, _PD, C.c_long]),
     "saena_restrict_from_prolong": (_VP, [_VP]),
     "saena_transfer_free": (None, [_VP]),
@@ -437,6 +439,20 @@ def spgemm_stats(L, total=False):
 
 def spgemm_stats_reset(L):
     L.saena_debug_spgemm_stats_reset()
+
+
+def filter_csr(L, ptr, col, val, thre, row_offset=0):
+    """the setup's filter on rows [row_offset, row_offset + len(ptr) - 1) of a level (saena_debug_filter): entries with
+    |v| <= thre off the diagonal are lumped into it -> (ptr, col, val)"""
+    p, c, v = np.ascontiguousarray(ptr, np.int64), _ai(col), _ad(val)
+    if len(c) != p[-1] or len(v) != p[-1]:
+        raise ValueError("filter_csr: array lengths do not match the row pointers")
+    at = lambda a: a.ctypes.data_as(_VP)
+    n = C.c_long()
+    _check(L, L.saena_debug_filter(len(p) - 1, at(p), at(c), at(v), float(thre), int(row_offset), C.byref(n)))
+    o_ptr, o_col, o_val = np.zeros(len(p), np.int64), np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
+    _check(L, L.saena_debug_filter_result(at(o_ptr), at(o_col), at(o_val)))
+    return o_ptr, o_col, o_val
 
 
 def device_operator(obj, halo_fp32=False):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from saena_amd import host
+from tests import setup_ref, spgemm_ref
 
 
 def random_spd_graph(n, deg, seed):
@@ -29,37 +30,6 @@ def random_spd_graph(n, deg, seed):
     return rows.astype(np.int32), cols.astype(np.int32), vals
 
 
-def plain_rounds(n, rows, cols, vals, thr):
-    """the reference's algorithm without shortcuts; returns the coarse id of every row (roots numbered in ascending order)"""
-    order = np.lexsort((cols, rows))
-    rows, cols, vals = rows[order], cols[order], vals[order]
-    ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))])
-    off = rows != cols
-    mx = np.full(n, -np.inf); np.maximum.at(mx, rows[off], -vals[off])
-    strong = [[] for _ in range(n)]
-    for i in range(n):
-        for k in range(ptr[i], ptr[i + 1]):
-            j = cols[k]
-            if i == j or (-vals[k] / mx[i] > thr) or (-vals[k] / mx[j] > thr):
-                strong[i].append(j)
-    agg = np.arange(n); decided = np.zeros(n, bool); root = np.zeros(n, bool)
-    while not decided.all():
-        agg2 = agg.copy(); dec = np.ones(n, bool); rn = np.zeros(n, bool)
-        for i in np.flatnonzero(~decided):
-            for c in strong[i]:
-                if agg[c] < agg2[i] and (not decided[c] or root[c]):
-                    agg2[i], dec[i], rn[i] = agg[c], decided[c], root[c]
-        for i in np.flatnonzero(~decided):
-            if dec[i]:
-                decided[i] = True
-                if agg[i] == agg2[i]:
-                    root[i] = True
-                elif rn[i]:
-                    agg[i] = agg2[i]
-    ids = np.flatnonzero(root)
-    return np.searchsorted(ids, agg), len(ids)
-
-
 @pytest.mark.parametrize("n,deg,seed", [(600, 4, 1), (1500, 7, 2), (2500, 3, 3)])
 def test_aggregates_equal_the_plain_rounds(n, deg, seed):
     rows, cols, vals = random_spd_graph(n, deg, seed)
@@ -70,9 +40,33 @@ def test_aggregates_equal_the_plain_rounds(n, deg, seed):
     opts = dict(host.OPTIONS001)
     S = host.AmgSolver(A, host.options(L, **opts))
     got, ngot = S.level_aggregates(0)
-    want, nwant = plain_rounds(n, rows, cols, vals, float(np.float32(opts.get("connStrength", 0.2))))
+    Ar = setup_ref.from_coo(n, rows, cols, vals)
+    want, nwant = setup_ref.plain_rounds(Ar, setup_ref.strength(Ar, opts.get("connStrength", 0.2)))
     assert ngot == nwant
     np.testing.assert_array_equal(got, want)
+
+
+def gather_entries(layouts, row_split, col_split):
+    """the entries (global ids, sorted by row then column) of an operator from every rank's layout of its rows: the local
+    part as it stands, the halo part with slot s of rank r's receive buffer named by the sender's send list (vIndex)"""
+    world = len(layouts)
+    rows, cols, vals = [], [], []
+    for r, d in enumerate(layouts):
+        assert d["M"] == row_split[r + 1] - row_split[r] and d["col_offset"] == col_split[r]
+        rows.append(np.repeat(np.arange(d["M"]), d["nnzPerRow_local"]) + row_split[r]); cols.append(d["col_local"]); vals.append(d["val_local"])
+        slots = []
+        for q in d["recvProcRank"]:
+            src = layouts[q]
+            ofs = np.concatenate([[0], np.cumsum(src["sendProcCount"])])
+            k = int(np.flatnonzero(src["sendProcRank"] == r)[0])
+            slots.append(src["vIndex"][ofs[k]:ofs[k + 1]] + col_split[q])
+        slots = np.concatenate(slots + [np.zeros(0, np.int64)]).astype(np.int64)
+        assert len(slots) == len(d["nnzPerCol_remote"]) and int(d["recvProcCount"].sum()) == len(slots)
+        rows.append(d["row_remote"] + row_split[r]); cols.append(np.repeat(slots, d["nnzPerCol_remote"])); vals.append(d["val_remote"])
+    rows, cols, vals = np.concatenate(rows).astype(np.int64), np.concatenate(cols).astype(np.int64), np.concatenate(vals)
+    order = np.lexsort((cols, rows))
+    assert world == len(row_split) - 1
+    return rows[order], cols[order], vals[order]
 
 
 def _worker(rank, world, name, n, deg, seed, ret):
@@ -87,7 +81,9 @@ def _worker(rank, world, name, n, deg, seed, ret):
         A.set_many(rows[mine], cols[mine], vals[mine])
         A.assemble()
         S = host.AmgSolver(A, host.options(L, **host.OPTIONS001))
-        ret[rank] = [(S.level_info(l)["rows"], S.level_info(l)["nnzA"], S.level_info(l)["nnzP"]) for l in range(S.num_levels)]
+        counts = [(S.level_info(l)["rows"], S.level_info(l)["nnzA"], S.level_info(l)["nnzP"]) for l in range(S.num_levels)]
+        layouts = [(S.level_split(l), S.level_layout(l, 0), S.level_layout(l, 1) if l < S.num_levels - 1 else None) for l in range(S.num_levels)]
+        ret[rank] = (counts, layouts)
     except Exception as e:                              # noqa: BLE001 -- reported to the parent
         ret[rank] = f"{type(e).__name__}: {e}"
 
@@ -120,4 +116,18 @@ def test_row_distributed_aggregation_builds_the_one_rank_hierarchy(world):
                 p.terminate()
         got = dict(ret)
     for r in range(world):
-        assert got.get(r) == want, (r, got.get(r), want)
+        assert not isinstance(got.get(r), str) and got.get(r) is not None, (r, got.get(r))
+        assert got[r][0] == want, (r, got[r][0], want)
+    # ... and the entries: every level's A and P, the ranks' rows gathered by the level's partition, are the one-rank hierarchy's
+    for l in range(S1.num_levels):
+        splits = [got[r][1][l][0] for r in range(world)]
+        for s in splits[1:]:
+            np.testing.assert_array_equal(s, splits[0])
+        for which in (0, 1) if l < S1.num_levels - 1 else (0,):
+            col_split = splits[0] if which == 0 else got[0][1][l + 1][0]
+            rows_, cols_, vals_ = gather_entries([got[r][1][l][1 + which] for r in range(world)], splits[0], col_split)
+            one = S1.level_layout(l, which)
+            assert splits[0][-1] == one["M"] and col_split[-1] == one["N_local"]
+            np.testing.assert_array_equal(rows_, np.repeat(np.arange(one["M"]), one["nnzPerRow_local"]), err_msg=f"level {l} op {which}: rows")
+            np.testing.assert_array_equal(cols_, one["col_local"], err_msg=f"level {l} op {which}: columns")
+            spgemm_ref.assert_same_values(vals_, one["val_local"], f"level {l} op {which}, {world} ranks")

@@ -86,6 +86,11 @@ def test_setup_against_the_compiled_reference(fx, hierarchies):
         # the reference's coarse partition at this rank count counts the aggregates rooted in each rank's block of fine rows
         # (aggregate_index_update, setup1:2115-2127): a root is the first row of its aggregate's id in ascending numbering
         split, splitNew = G[f"split{l}"], G[f"splitNew{l}"]
-        _, first_row = np.unique(agg, return_index=True)                  # coarse ids ascend with their roots' fine ids
-        roots = np.sort(first_row) if l is None else None
-        del roots, first_row, split, splitNew
+        # (a row only ever joins a root of a smaller id than its own, so the root is the first row that carries the coarse id)
+        split, splitNew = G[f"split{l}"], G[f"splitNew{l}"]
+        ids, roots = np.unique(agg, return_index=True)
+        np.testing.assert_array_equal(ids, np.arange(nagg))
+        assert np.all(np.diff(roots) > 0), "coarse ids must ascend with their roots' fine ids"
+        assert len(split) == len(splitNew) == int(npart[2:]) + 1 and split[0] == 0 and split[-1] == dA["M"]
+        np.testing.assert_array_equal(splitNew, np.searchsorted(roots, split, side="left"),
+                                      err_msg=f"{fx} level {l}: splitNew[r] is not the number of roots below split[r]")
