@@ -67,6 +67,17 @@ int sgpu_debug_chain_us(double *us);
  * (tests: "fewer launches per V-cycle"); counts host-side enqueues, not GPU work */
 int sgpu_debug_launch_count(long *launches);
 
+/* tests (tests/test_gpu_plan_storage.py): which storage groups of the operator's local part hold device memory, and how many bytes
+ * all of the library's owned device and pinned arrays hold in this process (vectors from sgpu_vec_alloc belong to the caller and
+ * are not counted).  op may be NULL (the mask is then 0).  *group_mask, bit set = the group holds at least one array:
+ *    0 csr (row pointers, columns, values, row-block plans)     1 dense rows
+ *    2, 3 16-bit compressed columns of the 16 / 32 KiB plan      4, 5 column-major-in-block copies of the 16 / 32 KiB plan
+ *    6 sliced-ELLPACK values      7 sliced-ELLPACK column codes   8 row patterns (k_sellp's ids and tables)
+ *    9 value codes (k_vidx)      10, 11, 12 x-window tables for workgroups of 256 / 512 / 1024 rows
+ *   13 row-paired values (k_sellp2)   14 row patterns with x in LDS (k_sellpx)   15 row templates (k_rowt)
+ *   16 x-in-LDS chunk plan       17 x-in-LDS columns              18 sliced ELLPACK in LDS windows (k_sellx) */
+int sgpu_debug_op_storage(const sgpu_op *op, unsigned *group_mask, long long *live_bytes);
+
 /* one line describing the device of the context (name, architecture, compute units, clocks, L2, memory), for bench
  * lines and logs: the same kernel ran 1 055-1 213 us on different boxes of one pool.  `buf` receives at most len-1
  * characters and a terminator. */

@@ -99,6 +99,7 @@ SYMBOLS = {
     "sgpu_coarsest_solve": (C.c_int, [_VP, _VP, _VP, _PI]),
     "sgpu_debug_on_fatal_print": (C.c_int, [C.c_char_p]),
     "sgpu_debug_launch_count": (C.c_int, [C.POINTER(C.c_long)]),
+    "sgpu_debug_op_storage": (C.c_int, [_VP, C.POINTER(C.c_uint), C.POINTER(C.c_longlong)]),
     "sgpu_debug_chain_us": (C.c_int, [C.POINTER(C.c_double)]),
     "sgpu_debug_device_info": (C.c_int, [C.c_char_p, C.c_int]),
     "sgpu_debug_allow_local_only": (C.c_int, [_VP, C.c_int]),
@@ -410,6 +411,12 @@ class Operator:
         check(lib().sgpu_op_get_x_windows(self.h, C.byref(v)))
         return v.value
 
+    def storage_mask(self):
+        """bit mask of the local part's storage groups that hold device memory (sgpu_debug_op_storage; bit order: STORAGE_GROUPS)"""
+        m, b = C.c_uint(), C.c_longlong()
+        check(lib().sgpu_debug_op_storage(self.h, C.byref(m), C.byref(b)))
+        return m.value
+
     def spmv(self, v, w):
         check(lib().sgpu_spmv(self.h, v.ptr, w.ptr))
 
@@ -712,6 +719,19 @@ def block_mix(K, sources, coefs, out, n, add=None):
     for s in range(3):
         p += [sources[s].ptr, coefs[s].ptr] if s < ns else [None, None]
     check(lib().sgpu_debug_block_mix(int(K), ns, *p, add.ptr if add is not None else None, out.ptr, int(n)))
+
+
+# the storage groups of an operator's local part, in the bit order of sgpu_debug_op_storage
+STORAGE_GROUPS = ("csr", "dense", "cc0", "cc1", "cm0", "cm1", "sell_values", "sell_columns", "sellp", "vidx", "xwin256", "xwin512",
+                  "xwin1024", "sellp2", "sellpx", "rowt", "xlds_plan", "xlds_columns", "sellx")
+
+
+def live_bytes():
+    """bytes held by all of the library's owned device and pinned arrays in this process (sgpu_debug_op_storage)"""
+    m, b = C.c_uint(), C.c_longlong()
+    st = lib().sgpu_debug_op_storage(None, C.byref(m), C.byref(b))
+    check(st)
+    return b.value
 
 
 def launch_count():

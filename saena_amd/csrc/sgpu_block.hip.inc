@@ -39,7 +39,7 @@ int apply_block(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs 
     const BlockFn fn = pick_block(K, epi, G);
     if (!fn) return fail(SGPU_ERR_ARG, "block apply: no kernel for epilogue %d", epi);   // a missing kernel is an error, never a fall-back
     sk::BlockArgs a;
-    a.row_ptr = op->loc.row_ptr; a.col = op->loc.col; a.val = op->loc.val; a.blk_row = op->loc.blk_row; a.nblk = op->loc.nblk;
+    a.row_ptr = op->loc.csr.row_ptr; a.col = op->loc.csr.col; a.val = op->loc.csr.val; a.blk_row = op->loc.csr.blk_row; a.nblk = op->loc.nblk;
     a.x = x; a.y = y; a.rhs = e.rhs; a.inv_diag = e.inv_diag; a.u = e.u; a.d = e.d; a.c0 = e.c0; a.c1 = e.c1;
     SGPU_LAUNCH(fn, dim3(op->loc.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     HIPCHK(hipGetLastError());
@@ -50,16 +50,14 @@ int block_slot(int K) { return K == 2 ? 0 : K == 4 ? 1 : 2; }
 
 // the operator's block ping-pong buffer (the op-level smoother calls; a block V-cycle ping-pongs in its own work vectors) and its
 // Chebyshev direction for K columns: made when first needed, each on its own
-int ensure_blk_buf(double **p, const sgpu_op *op, int K) {
-    if (*p) return SGPU_OK;
-    if (hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, (size_t)op->M * K) * sizeof(double)) != hipSuccess) {
-        *p = nullptr;
+int ensure_blk_buf(DevArr<double> &p, const sgpu_op *op, int K) {
+    if (p) return SGPU_OK;
+    if (alloc_vec(p, (size_t)op->M * K) != hipSuccess)
         return fail(SGPU_ERR_NOMEM, "hipMalloc of a block work vector (%d rows x %d columns) failed", op->M, K);
-    }
     return SGPU_OK;
 }
-int ensure_blk_tmp(sgpu_op *op, int K) { return ensure_blk_buf(&op->tmp_blk[block_slot(K)], op, K); }
-int ensure_blk_d(sgpu_op *op, int K) { return ensure_blk_buf(&op->dvec_blk[block_slot(K)], op, K); }
+int ensure_blk_tmp(sgpu_op *op, int K) { return ensure_blk_buf(op->tmp_blk[block_slot(K)], op, K); }
+int ensure_blk_d(sgpu_op *op, int K) { return ensure_blk_buf(op->dvec_blk[block_slot(K)], op, K); }
 
 // jacobi_pp / cheby_pp on block vectors (no zero-iterate shortcut: a sweep from a zero-filled block gives the same numbers)
 int jacobi_block_pp(sgpu_op *op, int iter, double omega, double *u, double *alt, const double *rhs, double **out, int K) {
@@ -116,20 +114,19 @@ int amg_block(sgpu_amg *h, int K, AmgBlock **out) {
         std::unique_ptr<AmgBlock> B(new AmgBlock());
         B->K = K;
         const int L = h->nlevels;
-        B->res.assign(L, nullptr); B->rhs.assign(L, nullptr); B->u.assign(L, nullptr); B->alt.assign(L, nullptr);
-        auto alloc = [](double **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, n) * sizeof(double)); };
+        B->res.resize(L); B->rhs.resize(L); B->u.resize(L); B->alt.resize(L);
         for (int l = 0; l < L; ++l) {
             const size_t n = (size_t)h->A[l]->M * K;
-            if (l < L - 1) HIPCHK(alloc(&B->res[l], n));
-            if (l >= 1) { HIPCHK(alloc(&B->rhs[l], n)); HIPCHK(alloc(&B->u[l], n)); HIPCHK(alloc(&B->alt[l], n)); }
+            if (l < L - 1) HIPCHK(alloc_vec(B->res[l], n));
+            if (l >= 1) { HIPCHK(alloc_vec(B->rhs[l], n)); HIPCHK(alloc_vec(B->u[l], n)); HIPCHK(alloc_vec(B->alt[l], n)); }
             CHK(ensure_blk_d(h->A[l], K));                     // (Chebyshev direction) no allocation may happen inside a graph capture
         }
         const size_t n0 = (size_t)h->A[0]->M * K;
-        HIPCHK(alloc(&B->alt0, n0)); HIPCHK(alloc(&B->r, n0)); HIPCHK(alloc(&B->rho, n0)); HIPCHK(alloc(&B->hh, n0)); HIPCHK(alloc(&B->p, n0));
-        HIPCHK(alloc(&B->cm, 2 * (size_t)h->A[L - 1]->M * K));
-        HIPCHK(alloc(&B->S, 8 * (size_t)K));
-        HIPCHK(alloc(&B->partials, (size_t)g.n_partials * K));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&B->hS), K * sizeof(double), hipHostMallocDefault));
+        HIPCHK(alloc_vec(B->alt0, n0)); HIPCHK(alloc_vec(B->r, n0)); HIPCHK(alloc_vec(B->rho, n0)); HIPCHK(alloc_vec(B->hh, n0)); HIPCHK(alloc_vec(B->p, n0));
+        HIPCHK(alloc_vec(B->cm, 2 * (size_t)h->A[L - 1]->M * K));
+        HIPCHK(alloc_vec(B->S, 8 * (size_t)K));
+        HIPCHK(alloc_vec(B->partials, (size_t)g.n_partials * K));
+        HIPCHK(B->hS.alloc(K));
         h->blk[slot] = std::move(B);
     }
     AmgBlock *B = h->blk[slot].get();
@@ -219,19 +216,17 @@ int vcycle_block0(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, bool u
     B.graph_gen = g_plan_generation; B.block_gen = g_block_generation;
     for (auto &c : B.graphs)
         if (c.u == u && c.rhs == rhs && c.u_zero == u_zero) { ++g_launches; HIPCHK(hipGraphLaunch(c.exec, g.cs)); return SGPU_OK; }
-    AmgBlock::Captured c{u, rhs, u_zero, nullptr, nullptr};
+    CapturedCycle c;
+    c.u = u; c.rhs = rhs; c.u_zero = u_zero;
     HIPCHK(hipStreamBeginCapture(g.cs, hipStreamCaptureModeThreadLocal));
     const int st = vcycle_block_eager(h, B, u, rhs, u_zero);
     const hipError_t e = hipStreamEndCapture(g.cs, &c.graph);
-    if (st != SGPU_OK) { if (c.graph) hipGraphDestroy(c.graph); return st; }
+    if (st != SGPU_OK) return st;
     if (e != hipSuccess) return fail(SGPU_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
     HIPCHK(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
-    if (B.graphs.size() >= 8) {
-        hipGraphExecDestroy(B.graphs.front().exec); hipGraphDestroy(B.graphs.front().graph);
-        B.graphs.erase(B.graphs.begin());
-    }
-    B.graphs.push_back(c);
-    ++g_launches; HIPCHK(hipGraphLaunch(c.exec, g.cs));
+    if (B.graphs.size() >= 8) B.graphs.erase(B.graphs.begin());
+    B.graphs.push_back(std::move(c));
+    ++g_launches; HIPCHK(hipGraphLaunch(B.graphs.back().exec, g.cs));
     return SGPU_OK;
 }
 

@@ -67,14 +67,13 @@ int amg_eig(sgpu_amg *h, int K, AmgEig **out) {
         std::unique_ptr<AmgEig> E(new AmgEig());
         E->K = K;
         const size_t nK = (size_t)h->A[0]->M * K, KK = (size_t)K * K;
-        auto alloc = [](double **p, size_t k) { return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, k) * sizeof(double)); };
-        for (double **p : {&E->AX, &E->R, &E->W, &E->AW, &E->P, &E->AP}) HIPCHK(alloc(p, nK));
-        HIPCHK(alloc(&E->gpart, 12 * (size_t)g.n_partials * KK));
-        HIPCHK(alloc(&E->rpart, (size_t)g.n_partials * K));
-        HIPCHK(alloc(&E->coef, 15 * KK + 2 * K));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&E->hmix), 3 * KK * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&E->hlam), K * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&E->hdown), (12 * KK + K) * sizeof(double), hipHostMallocDefault));
+        for (DevArr<double> *p : {&E->AX, &E->R, &E->W, &E->AW, &E->P, &E->AP}) HIPCHK(alloc_vec(*p, nK));
+        HIPCHK(alloc_vec(E->gpart, 12 * (size_t)g.n_partials * KK));
+        HIPCHK(alloc_vec(E->rpart, (size_t)g.n_partials * K));
+        HIPCHK(alloc_vec(E->coef, 15 * KK + 2 * K));
+        HIPCHK(E->hmix.alloc(3 * KK));
+        HIPCHK(E->hlam.alloc(K));
+        HIPCHK(E->hdown.alloc(12 * KK + K));
         h->eigs[slot] = std::move(E);
     }
     *out = h->eigs[slot].get();
@@ -93,7 +92,7 @@ int eig_precondition(sgpu_amg *h, AmgBlock &B, AmgEig &E) {
         HIPCHK(hipStreamBeginCapture(g.cs, hipStreamCaptureModeThreadLocal));
         const int st = vcycle_block_eager(h, B, E.W, E.R, true);
         const hipError_t e = hipStreamEndCapture(g.cs, &E.graph);
-        if (st != SGPU_OK) { if (E.graph) { hipGraphDestroy(E.graph); E.graph = nullptr; } return st; }
+        if (st != SGPU_OK) { E.drop_graph(); return st; }
         if (e != hipSuccess) return fail(SGPU_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
         HIPCHK(hipGraphInstantiate(&E.exec, E.graph, nullptr, nullptr, 0));
         E.graph_gen = g_plan_generation; E.block_gen = g_block_generation;
@@ -236,7 +235,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
         return SGPU_OK;
     };
     auto send_lambda = [&](const double *lam) -> int {
-        std::copy(lam, lam + K, E.hlam);
+        std::copy(lam, lam + K, E.hlam.get());
         HIPCHK(hipMemcpyAsync(clam, E.hlam, (size_t)K * sizeof(double), hipMemcpyHostToDevice, g.cs));
         return SGPU_OK;
     };
@@ -264,7 +263,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
         if (saena_host::dense_sym_eig(K, S.data(), lam, Q.data()) < 0)
             return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: the Rayleigh-Ritz problem of the start vectors did not converge (X^T A X is not finite?)");
         if (!(lam[0] > 0.0)) return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: a Ritz value of the start vectors is %g: the operator is not symmetric positive definite", lam[0]);
-        std::copy(Q.begin(), Q.end(), E.hmix);
+        std::copy(Q.begin(), Q.end(), E.hmix.get());
         CHK(send_mix(1));
         CHK(eig_mix(K, 1, X, cmix, X, cmix, X, cmix, nullptr, X, n));
         CHK(eig_mix(K, 1, E.AX, cmix, E.AX, cmix, E.AX, cmix, nullptr, E.AX, n));
@@ -312,7 +311,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
         }
         const int na = (int)act.size();
         // ---- W -= X (X^T W); W^T W and P^T P: host synchronisation 2 ----
-        std::fill(E.hmix, E.hmix + KK, 0.0);
+        std::fill(E.hmix.get(), E.hmix + KK, 0.0);
         for (int a = 0; a < K; ++a)
             for (int j : act) E.hmix[a * K + j] = -hgram[a * K + j];
         CHK(send_mix(1));
@@ -367,7 +366,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
                         st == -1 ? "linearly dependent (S^T S is not numerically positive definite)" : "not finite");
         if (!(theta[0] > 0.0)) return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: a Ritz value is %g at iteration %d: the operator is not symmetric positive definite", theta[0], it + 1);
         // C_X | C_W | C_P: the K smallest Ritz vectors; rows of inactive columns are zero
-        std::fill(E.hmix, E.hmix + 3 * KK, 0.0);
+        std::fill(E.hmix.get(), E.hmix + 3 * KK, 0.0);
         for (int i = 0; i < m; ++i)
             for (int b = 0; b < K; ++b) E.hmix[blk[(size_t)i] * KK + col[(size_t)i] * K + b] = Vm[(size_t)i * m + b];
         CHK(send_mix(3));

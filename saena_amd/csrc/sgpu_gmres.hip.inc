@@ -91,13 +91,12 @@ int amg_gmres(sgpu_amg *h, int restart, AmgGmres **out) {
         const size_t n = (size_t)h->A[0]->M;
         G->restart = restart;
         G->ld = std::max<size_t>(2, (n + 1) & ~(size_t)1);
-        auto alloc = [](double **p, size_t k) { return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, k) * sizeof(double)); };
-        HIPCHK(alloc(&G->V, G->ld * (size_t)(restart + 1)));
-        HIPCHK(alloc(&G->Z, G->ld * (size_t)restart));
-        HIPCHK(alloc(&G->pin, G->ld)); HIPCHK(alloc(&G->pout, G->ld));
-        HIPCHK(alloc(&G->coef, 2 * (size_t)(restart + 1) + 1));
-        HIPCHK(alloc(&G->partials, (size_t)(restart + 1) * sk::GS_MAXBLK));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&G->hcoef), (2 * (size_t)(restart + 1) + 1) * sizeof(double), hipHostMallocDefault));
+        HIPCHK(alloc_vec(G->V, G->ld * (size_t)(restart + 1)));
+        HIPCHK(alloc_vec(G->Z, G->ld * (size_t)restart));
+        HIPCHK(alloc_vec(G->pin, G->ld)); HIPCHK(alloc_vec(G->pout, G->ld));
+        HIPCHK(alloc_vec(G->coef, 2 * (size_t)(restart + 1) + 1));
+        HIPCHK(alloc_vec(G->partials, (size_t)(restart + 1) * sk::GS_MAXBLK));
+        HIPCHK(G->hcoef.alloc(2 * (size_t)(restart + 1) + 1));
         h->gm = std::move(G);
     }
     *out = h->gm.get();
@@ -115,7 +114,7 @@ int gmres_precondition(sgpu_amg *h, AmgGmres &G) {
         HIPCHK(hipStreamBeginCapture(g.cs, hipStreamCaptureModeThreadLocal));
         const int st = vcycle0_eager(h, G.pout, G.pin, true);
         const hipError_t e = hipStreamEndCapture(g.cs, &G.graph);
-        if (st != SGPU_OK) { if (G.graph) { hipGraphDestroy(G.graph); G.graph = nullptr; } return st; }
+        if (st != SGPU_OK) { G.drop_graph(); return st; }
         if (e != hipSuccess) return fail(SGPU_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
         HIPCHK(hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0));
         G.graph_gen = g_plan_generation;
@@ -141,10 +140,10 @@ extern "C" {
 int sgpu_debug_gs_dots(const value_t *V, size_t ld, int ncols, const value_t *w, size_t n, value_t *out_host) {
     CHK(gs_debug_args(V, ld, ncols, w, n, "debug_gs_dots"));
     if (!out_host) return fail(SGPU_ERR_ARG, "debug_gs_dots: null argument");
-    DevBuf partials, out;
-    CHK(partials.alloc((size_t)ncols * sk::GS_MAXBLK)); CHK(out.alloc((size_t)ncols));
-    CHK(gs_dots(V, ld, ncols, w, n, partials.p, out.p));
-    HIPCHK(hipMemcpyAsync(out_host, out.p, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, g.cs));
+    DevArr<double> partials, out;
+    CHK(dev_alloc(partials, (size_t)ncols * sk::GS_MAXBLK)); CHK(dev_alloc(out, (size_t)ncols));
+    CHK(gs_dots(V, ld, ncols, w, n, partials, out));
+    HIPCHK(hipMemcpyAsync(out_host, out, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, g.cs));
     HIPCHK(hipStreamSynchronize(g.cs));
     return SGPU_OK;
 }
@@ -152,11 +151,11 @@ int sgpu_debug_gs_dots(const value_t *V, size_t ld, int ncols, const value_t *w,
 int sgpu_debug_gs_update(const value_t *V, size_t ld, int ncols, const value_t *h_host, value_t *w, size_t n, value_t *norm2_out_host) {
     CHK(gs_debug_args(V, ld, ncols, w, n, "debug_gs_update"));
     if (!h_host) return fail(SGPU_ERR_ARG, "debug_gs_update: null argument");
-    DevBuf partials, coef;
-    CHK(partials.alloc(sk::GS_MAXBLK)); CHK(coef.alloc((size_t)ncols + 1));
-    HIPCHK(hipMemcpyAsync(coef.p, h_host, (size_t)ncols * sizeof(double), hipMemcpyHostToDevice, g.cs));
-    CHK(gs_update(V, ld, ncols, coef.p, w, n, partials.p, norm2_out_host ? coef.p + ncols : nullptr));
-    if (norm2_out_host) HIPCHK(hipMemcpyAsync(norm2_out_host, coef.p + ncols, sizeof(double), hipMemcpyDeviceToHost, g.cs));
+    DevArr<double> partials, coef;
+    CHK(dev_alloc(partials, sk::GS_MAXBLK)); CHK(dev_alloc(coef, (size_t)ncols + 1));
+    HIPCHK(hipMemcpyAsync(coef, h_host, (size_t)ncols * sizeof(double), hipMemcpyHostToDevice, g.cs));
+    CHK(gs_update(V, ld, ncols, coef, w, n, partials, norm2_out_host ? coef + ncols : nullptr));
+    if (norm2_out_host) HIPCHK(hipMemcpyAsync(norm2_out_host, coef + ncols, sizeof(double), hipMemcpyDeviceToHost, g.cs));
     HIPCHK(hipStreamSynchronize(g.cs));
     return SGPU_OK;
 }
@@ -166,11 +165,11 @@ int sgpu_debug_gs_update(const value_t *V, size_t ld, int ncols, const value_t *
 int sgpu_debug_time_gs(int kind, const value_t *V, size_t ld, int ncols, value_t *w, size_t n, int reps, float *ms) {
     CHK(gs_debug_args(V, ld, ncols, w, n, "debug_time_gs"));
     if (!ms || reps < 1 || (kind != 0 && kind != 1)) return fail(SGPU_ERR_ARG, "debug_time_gs: bad argument");
-    DevBuf partials, coef;
-    CHK(partials.alloc((size_t)ncols * sk::GS_MAXBLK)); CHK(coef.alloc((size_t)ncols + 1));
-    CHK(sgpu_vec_fill(coef.p, 0.0, (size_t)ncols + 1));
+    DevArr<double> partials, coef;
+    CHK(dev_alloc(partials, (size_t)ncols * sk::GS_MAXBLK)); CHK(dev_alloc(coef, (size_t)ncols + 1));
+    CHK(sgpu_vec_fill(coef, 0.0, (size_t)ncols + 1));
     CHK(block_timer_events());
-    auto once = [&]() { return kind == 0 ? gs_dots(V, ld, ncols, w, n, partials.p, coef.p) : gs_update(V, ld, ncols, coef.p, w, n, partials.p, coef.p + ncols); };
+    auto once = [&]() { return kind == 0 ? gs_dots(V, ld, ncols, w, n, partials, coef) : gs_update(V, ld, ncols, coef, w, n, partials, coef + ncols); };
     if (kind == 1) CHK(once());                                // (after it the coefficients are still zero: the dots are not run)
     HIPCHK(hipEventRecord(g_bt0, g.cs));
     for (int i = 0; i < reps; ++i) CHK(once());

@@ -12,6 +12,7 @@
 #include "kernels_gmres.hip.h"
 #include "kernels_eig.hip.h"
 #include "dispatch.h"
+#include "devmem.h"
 #include "host/dense_eig.h"
 #include "host/comm.h"
 #include "host/par.h"
@@ -40,6 +41,9 @@
 #include <vector>
 
 extern "C" void sgpu_install_spgemm_hook(int on);
+
+using devmem::DevArr;
+using devmem::PinArr;
 
 namespace {
 
@@ -116,187 +120,197 @@ int host_allreduce(double *v, int n) {
 // sum of a few host doubles over the ranks (setup-time decisions every rank must take alike); identity at one rank
 int global_sum(double *v, int n);
 
-struct DevBuf {
-    double *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    int alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(1, n) * sizeof(double)) == hipSuccess ? SGPU_OK : fail(SGPU_ERR_NOMEM, "hipMalloc failed"); }
-};
+// work vectors of n doubles: at least one element, so that an empty level still has a pointer
+hipError_t alloc_vec(DevArr<double> &a, size_t n) { return a.alloc(std::max<size_t>(1, n)); }
+int dev_alloc(DevArr<double> &a, size_t n) { return alloc_vec(a, n) == hipSuccess ? SGPU_OK : fail(SGPU_ERR_NOMEM, "hipMalloc failed"); }
 
 template <class T>
-int dev_upload(T **dst, const T *src, size_t n, size_t pad = 0) {
-    *dst = nullptr;
+int dev_upload(DevArr<T> &dst, const T *src, size_t n, size_t pad = 0) {
     const size_t bytes = (n + pad) * sizeof(T);
-    if (hipMalloc(reinterpret_cast<void **>(dst), bytes ? bytes : sizeof(T)) != hipSuccess)
+    if (dst.alloc(std::max<size_t>(1, n + pad)) != hipSuccess)
         return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", bytes);
-    if (pad) HIPCHK(hipMemsetAsync(*dst, 0, bytes ? bytes : sizeof(T), g.cs));
-    if (n) HIPCHK(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, g.cs));
+    if (pad) HIPCHK(hipMemsetAsync(dst, 0, dst.bytes(), g.cs));
+    if (n) HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, g.cs));
     HIPCHK(hipStreamSynchronize(g.cs));
     return SGPU_OK;
 }
 
 // One CSR part (local, or remote-over-halo) laid out for k_csr_stream.
+//
+// Its device arrays live in GROUPS, one per unit of lifetime: a group holds the arrays and the built / tried flags that a free
+// clears with them, and `G = {}` frees it.  The scalars a launch reads (nslices, sl_pair, sl_uw, sp_w, sp_n, sp_bytes, sp2_uw,
+// sp2_nslices, vi_uw8, xl_nblk ...) stay outside: a surviving form may read them after the arrays they were computed with are gone.
+// Which plan keeps which group: plan_keeps() below, the one place a new form registers its storage.
 struct CsrPart {
     int     nrows = 0;            // rows covered by row_ptr (M, or number of remote rows)
     int64_t nnz = 0;
-    int    *row_ptr = nullptr, *col = nullptr, *blk_row = nullptr, *blk_row_big = nullptr, *rows = nullptr;
-    double *val = nullptr;
+    struct Csr { DevArr<int> row_ptr, col, blk_row, blk_row_big, rows; DevArr<double> val; } csr;
     int     nblk = 0, nblk_big = 0;
     int     lanes = 1;            // G
     int     variant = 0;          // 0 stream 16 KiB, 1 stream 32 KiB, 2 vector CSR, 3 cc16 16 KiB, 4 cc16 32 KiB, 5 dense rows
-    double *dense = nullptr;      // variant 5: row-major nrows x ncols (built on demand for small, mostly full operators)
+    struct Dense { DevArr<double> dense; } dn;   // variant 5: row-major nrows x ncols (built on demand for small, mostly full operators)
     int     ncols = 0;
     std::vector<double> h_val;    // host copy of the values, kept only while a dense form is still possible
     // 16-bit compressed columns (variants 3/4): per plan ([0] 16 KiB, [1] 32 KiB) a segment table and packed column ids
-    int            *segtab[2] = {nullptr, nullptr}, *segptr[2] = {nullptr, nullptr};
-    unsigned short *ccol[2] = {nullptr, nullptr};
-    bool            cc_ok[2] = {false, false};
+    struct Cc {
+        DevArr<int> segtab, segptr;
+        DevArr<unsigned short> ccol;
+        bool ok = false;
+        char tried = 0;           // build_cc16 ran and found no split that fits (do not try again)
+    } cc[2];
+    int     cc_ob[2] = {12, 12};  // offset bits of the slot/offset split (12: 16 segments of 4096 columns ... 8: 256 of 256)
     // column-major-in-block form (variants 7/8, on top of the compressed columns of the same plan)
-    double         *cm_val[2] = {nullptr, nullptr};
-    unsigned short *cm_col[2] = {nullptr, nullptr}, *cm_dst[2] = {nullptr, nullptr};
-    int            *cm_ptr[2] = {nullptr, nullptr};
-    bool            cm_ok[2] = {false, false};
-    char            cm_tried[2] = {0, 0};
-    // sliced ELLPACK (variant 9): slices of 64 rows, position-major, 16-bit column offsets from a per-(slice, position) base
-    double         *sl_val = nullptr;
-    unsigned short *sl_col = nullptr, *sl_len = nullptr;
-    int            *sl_base = nullptr, *sl_segptr = nullptr, *sl_ptr = nullptr;   // segment bases of all groups, group g owns [sl_segptr[g], sl_segptr[g+1])
+    struct Cm {
+        DevArr<double> val;
+        DevArr<unsigned short> col, dst;
+        DevArr<int> ptr;
+        bool ok = false;
+        char tried = 0;
+    } cm[2];
+    // sliced ELLPACK (variant 9): slices of 64 rows, position-major, 16-bit column offsets from a per-(slice, position) base.
+    // The values (sl_val, sl_ptr, nslices, sl_pair) are what the row-pattern forms need ...
+    struct SellValues {
+        DevArr<double> sl_val;
+        DevArr<int> sl_ptr;
+        DevArr<int> sl_perm;      // k_sell<sorted>: slice position -> row (rows sorted by length inside windows of SL_SORT_WINDOW rows)
+        bool sl_vals = false, sl_sorted = false;
+        char sl_vals_tried = 0;
+    } sv;
+    // ... the column codes are k_sell's alone
+    struct SellColumns {
+        DevArr<unsigned short> sl_col, sl_len;
+        DevArr<int> sl_base, sl_segptr;   // segment bases of all groups, group g owns [sl_segptr[g], sl_segptr[g+1])
+    } sc;
     int             nslices = 0, sl_ob = 12;
     bool            sl_pair = false;       // two positions per lane side by side (rows of >= 16 entries), else one
-    int            *sl_perm = nullptr;     // k_sell<sorted>: slice position -> row (rows sorted by length inside windows of SL_SORT_WINDOW rows)
-    bool            sl_sorted = false;
     int             sl_uw = 0, sp2_uw = 0; // every slice of 64 (k_sell / k_sellp) / 128 (k_sellp2) rows has this many positions (0: widths differ)
     bool            sl_ok = false;         // values AND column codes: k_sell can run
-    bool            sl_vals = false;       // the values (sl_val, sl_ptr, nslices, sl_pair): what the row-pattern forms need
-    char            sl_tried = 0, sl_vals_tried = 0;
+    char            sl_tried = 0;          // (stays set when the column codes alone are dropped: variant 9 is then gone for good)
     // row patterns on top of the sliced-ELLPACK values (variant 11, k_sellp): a 16-bit pattern id per row and the table of
     // patterns (sp_n rows of sp_w + 1 ints: length, then the columns relative to the row); shares sl_val / sl_ptr
-    unsigned short *sp_pat = nullptr;
-    int            *sp_tab = nullptr;
+    struct Sellp {
+        DevArr<unsigned short> sp_pat;
+        DevArr<int> sp_tab;
+        DevArr<int> sp_wgptr;     // sp_wide: table of row group g = sp_tab[sp_wgptr[g] .. sp_wgptr[g + 1])
+        DevArr<int> sp_rbase;     // "k_sellp<rowbase>" (round 4): the patterns are relative to the row's FIRST COLUMN, kept here (a transfer operator
+                                  // of a structured grid: its rows repeat relative to where they start, not to the row index); k_sellp only
+        bool sp_ok = false, sp_wide = false;   // sp_wide: a table per group of 1024 rows (k_sellp<WIDE>; sp_w = the largest, in ints)
+        char sp_tried = 0;
+    } sp;
     int             sp_w = 0, sp_n = 0;
-    int            *sp_wgptr = nullptr;   // sp_wide: table of row group g = sp_tab[sp_wgptr[g] .. sp_wgptr[g + 1])
-    int            *sp_rbase = nullptr;   // "k_sellp<rowbase>" (round 4): the patterns are relative to the row's FIRST COLUMN, kept here (a transfer operator
-                                          // of a structured grid: its rows repeat relative to where they start, not to the row index); k_sellp only
     int64_t         sp_bytes = 0;      // values + pattern ids + x + y as this form stores them
-    bool            sp_ok = false, sp_wide = false;   // sp_wide: a table per group of 1024 rows (k_sellp<WIDE>; sp_w = the largest, in ints)
-    char            sp_tried = 0;
     // value-indexed row patterns (variant 17, k_vidx): 8-bit codes into per-workgroup dictionaries instead of the values; shares
-    // sp_pat / sp_tab / sp_rbase (freed with them)
-    unsigned char  *vi_code = nullptr;
-    int            *vi_cptr = nullptr, *vi_dptr = nullptr;
-    double         *vi_dict = nullptr;
+    // sp_pat / sp_tab / sp_rbase
+    struct Vidx {
+        DevArr<unsigned char> vi_code;
+        DevArr<int> vi_cptr, vi_dptr;
+        DevArr<double> vi_dict;
+        bool vi_ok = false;
+        char vi_tried = 0;
+    } vi;
     int             vi_uw8 = 0;           // every slice has this many code positions (a multiple of 8), or 0: read vi_cptr
     int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
-    bool            vi_ok = false;
-    char            vi_tried = 0;
     // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
     // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS positions; vw_rows: the R in
-    // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays, kept and freed with them
-    struct XWin { unsigned short *tab = nullptr; int *win = nullptr; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
+    // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays
+    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
     XWin            vw[3];
     int             vw_rows = 0;
-    void free_xwin(int keep_rows = 0) {
-        for (int k = 0; k < 3; ++k) {
-            if ((256 << k) == keep_rows) continue;
-            hipFree(vw[k].tab); hipFree(vw[k].win);
-            vw[k] = XWin();
-        }
-        if (vw_rows != keep_rows) vw_rows = 0;
-    }
-    void free_vidx() {
-        free_xwin();
-        hipFree(vi_code); hipFree(vi_cptr); hipFree(vi_dptr); hipFree(vi_dict);
-        vi_code = nullptr; vi_cptr = vi_dptr = nullptr; vi_dict = nullptr; vi_ok = false; vi_tried = 0;
-    }
-    void free_sellp() { free_vidx(); hipFree(sp_pat); hipFree(sp_tab); hipFree(sp_wgptr); hipFree(sp_rbase); sp_pat = nullptr; sp_tab = nullptr; sp_wgptr = nullptr; sp_rbase = nullptr; sp_ok = false; sp_wide = false; sp_tried = 0; }      // (and k_sellpx with it: free_sell)
-    // the column codes of k_sell alone (k_sellp keeps the values and the slice pointers)
-    void free_sell_columns() {
-        hipFree(sl_col); hipFree(sl_len); hipFree(sl_base); hipFree(sl_segptr);
-        sl_col = sl_len = nullptr; sl_base = sl_segptr = nullptr;
-        sl_ok = false;                                             // (variant 9 is gone for good: sl_tried stays set)
-    }
-    void free_sell() {
-        free_sellp();
-        hipFree(spx_tab); hipFree(spx_pat); hipFree(spx_win); hipFree(spx_wgptr);                                 // (free_sellpx, declared below)
-        spx_tab = spx_pat = nullptr; spx_win = spx_wgptr = nullptr; spx_ok = false; spx_tried = 0;
-        hipFree(sl_val); hipFree(sl_col); hipFree(sl_len); hipFree(sl_base); hipFree(sl_segptr); hipFree(sl_ptr); hipFree(sl_perm);
-        sl_val = nullptr; sl_col = sl_len = nullptr; sl_base = sl_segptr = sl_ptr = sl_perm = nullptr; sl_ok = false; sl_tried = 0; sl_vals = false; sl_vals_tried = 0;
-        sl_sorted = false;
-    }
-    // x in LDS (variant 10): absolute 16-bit column ids and nnz-balanced row chunks, one per CU
-    unsigned short *xl_col = nullptr;
-    int            *xl_blk = nullptr, *xl_tab = nullptr;
-    int4           *xl_info = nullptr;
-    double         *xl_acc = nullptr;
+    // x in LDS (variant 10): absolute 16-bit column ids and nnz-balanced row chunks, one per CU.  The chunk plan (k_sellx is built
+    // on top of it) ...
+    struct XldsPlan {
+        DevArr<int> xl_blk;
+        DevArr<int4> xl_info;
+        DevArr<double> xl_acc;
+        DevArr<int> xl_ord;       // [M] or empty: per chunk, the order its rows are taken in (longest first where a chunk holds long rows)
+        bool xl_ok = false;
+        char xl_tried = 0;
+    } xlp;
+    // ... and the columns, k_csr_xlds's alone
+    struct XldsColumns { DevArr<unsigned short> xl_col; DevArr<int> xl_tab; } xlc;
     int             xl_nblk = 0, xl_maxt = 1;
-    int            *xl_ord = nullptr;      // [M] or nullptr: per chunk, the order its rows are taken in (longest first where a chunk holds long rows)
     int             xl_win = 0;            // columns per window of x in LDS: XL_MAX, or less where the chunks' partial row sums live in LDS behind the window
     bool            xl_acc_lds = false;
     std::vector<int>  xl_blk_h;            // host copies of the chunk plan (k_sellx is built on top of it)
     std::vector<int4> xl_info_h;
     double          xl_piece = 0.0;
-    bool            xl_ok = false;
-    char            xl_tried = 0;
-    void free_xlds() {
-        hipFree(xl_col); hipFree(xl_blk); hipFree(xl_tab); hipFree(xl_info); hipFree(xl_acc); hipFree(xl_ord);
-        xl_col = nullptr; xl_blk = xl_tab = xl_ord = nullptr; xl_info = nullptr; xl_acc = nullptr; xl_ok = false; xl_tried = 0;
-    }
     // k_sellp with a lane per two rows (variant 14, k_sellp2): the values row-paired in slices of 128 rows; shares sp_pat / sp_tab
-    double         *sp2_val = nullptr;
-    int            *sp2_ptr = nullptr;
+    struct Sellp2 { DevArr<double> sp2_val; DevArr<int> sp2_ptr; bool sp2_ok = false; char sp2_tried = 0; } sp2;
     int             sp2_nslices = 0;
-    bool            sp2_ok = false;
-    char            sp2_tried = 0;
-    void free_sellp2() { hipFree(sp2_val); hipFree(sp2_ptr); sp2_val = nullptr; sp2_ptr = nullptr; sp2_ok = false; sp2_tried = 0; }
     // k_sellp with x in LDS windows (variant 15, k_sellpx): the table as 16-bit LDS positions, the windows of x per workgroup;
     // shares sl_val / sl_ptr / sp_pat.  h_pstart / h_ptab: host copy of the patterns (start of each, then length + offsets), kept
     // until the plan settles
     std::vector<int> h_pstart, h_ptab;
     std::vector<unsigned short> h_pat;     // ... and of the rows' pattern ids
-    unsigned short *spx_tab = nullptr, *spx_pat = nullptr;       // the workgroups' tables back to back; workgroup-local pattern ids per row
-    int            *spx_win = nullptr, *spx_wgptr = nullptr;     // windows (count, then omin / LDS base / size each); table of workgroup g: words [spx_wgptr[g], spx_wgptr[g + 1])
-    bool            spx_ok = false;
-    char            spx_tried = 0;
-    void free_sellpx() {
-        hipFree(spx_tab); hipFree(spx_pat); hipFree(spx_win); hipFree(spx_wgptr);
-        spx_tab = spx_pat = nullptr; spx_win = spx_wgptr = nullptr; spx_ok = false; spx_tried = 0;
-    }
+    struct Sellpx {
+        DevArr<unsigned short> spx_tab, spx_pat;   // the workgroups' tables back to back; workgroup-local pattern ids per row
+        DevArr<int> spx_win, spx_wgptr;            // windows (count, then omin / LDS base / size each); table of workgroup g: words [spx_wgptr[g], spx_wgptr[g + 1])
+        bool spx_ok = false;
+        char spx_tried = 0;
+    } spx;
     // row templates (variant 13, k_rowt, opt-in): a template id per row; tables of (length, relative columns) and of values
-    unsigned short *rt_pat = nullptr;
-    int            *rt_itab = nullptr;
-    double         *rt_vtab = nullptr;
+    struct Rowt { DevArr<unsigned short> rt_pat; DevArr<int> rt_itab; DevArr<double> rt_vtab; bool rt_ok = false; char rt_tried = 0; } rt;
     int             rt_w = 0, rt_n = 0;
-    bool            rt_ok = false;
-    char            rt_tried = 0;
-    void free_rowt() { hipFree(rt_pat); hipFree(rt_itab); hipFree(rt_vtab); rt_pat = nullptr; rt_itab = nullptr; rt_vtab = nullptr; rt_ok = false; rt_tried = 0; }
     // sliced ELLPACK inside the (chunk, window) blocks of the x-in-LDS form (variant 12, k_sellx): shares xl_blk / xl_info / xl_acc
-    double         *sx_val = nullptr;
-    unsigned short *sx_col = nullptr;
-    unsigned       *sx_meta = nullptr;
-    int            *sx_bptr = nullptr, *sx_sptr = nullptr;
+    struct Sellx {
+        DevArr<double> sx_val;
+        DevArr<unsigned short> sx_col;
+        DevArr<unsigned> sx_meta;
+        DevArr<int> sx_bptr, sx_sptr;
+        bool sx_ok = false;
+        char sx_tried = 0;
+    } sx;
     double          sx_pad = 0.0;          // stored / actual entries
-    bool            sx_ok = false;
-    char            sx_tried = 0;
-    void free_sellx() {
-        hipFree(sx_val); hipFree(sx_col); hipFree(sx_meta); hipFree(sx_bptr); hipFree(sx_sptr);
-        sx_val = nullptr; sx_col = nullptr; sx_meta = nullptr; sx_bptr = sx_sptr = nullptr; sx_ok = false; sx_tried = 0;
-    }
-    int             cc_ob[2] = {12, 12};   // offset bits of the slot/offset split (12: 16 segments of 4096 columns ... 8: 256 of 256)
-    char            cc_tried[2] = {0, 0};  // build_cc16 ran and found no split that fits (do not try again)
     std::vector<int> h_rp, h_col, h_blk, h_blk_big;   // host copies kept for build_cc16 / the coarsest factorisation
-    void free_all() {
-        hipFree(row_ptr); hipFree(col); hipFree(blk_row); hipFree(blk_row_big); hipFree(rows); hipFree(val); hipFree(dense);
-        dense = nullptr;
-        for (int k = 0; k < 2; ++k) { hipFree(segtab[k]); hipFree(segptr[k]); hipFree(ccol[k]); segtab[k] = segptr[k] = nullptr; ccol[k] = nullptr; }
-        for (int k = 0; k < 2; ++k) { hipFree(cm_val[k]); hipFree(cm_col[k]); hipFree(cm_dst[k]); hipFree(cm_ptr[k]); cm_val[k] = nullptr; cm_col[k] = cm_dst[k] = nullptr; cm_ptr[k] = nullptr; }
-        row_ptr = col = blk_row = blk_row_big = rows = nullptr; val = nullptr;
-        free_sell();
-        free_xlds();
-        free_sellx();
-        free_rowt();
-        free_sellp2();
-        free_sellpx();
-    }
 };
+
+// The storage groups of a part in the order of sgpu_debug_op_storage's bits, and which of them the plan that settles on variant
+// `bv` keeps (finish_plan resets the others).  vw_rows: the x-window workgroup size in use, its tables alone stay with variant 17.
+enum PartGroup { G_CSR, G_DENSE, G_CC0, G_CC1, G_CM0, G_CM1, G_SELL_VALUES, G_SELL_COLUMNS, G_SELLP, G_VIDX, G_XWIN0, G_XWIN1, G_XWIN2,
+                 G_SELLP2, G_SELLPX, G_ROWT, G_XLDS_PLAN, G_XLDS_COLUMNS, G_SELLX, G_COUNT };
+bool plan_keeps(int grp, int bv, int vw_rows) {
+    switch (grp) {
+    case G_CSR:          return true;
+    case G_DENSE:        return bv == 5;
+    case G_CC0: case G_CC1: { const int k = grp - G_CC0; return bv == 3 + k || bv == 7 + k; }
+    case G_CM0: case G_CM1: return bv == 7 + (grp - G_CM0);
+    case G_SELL_VALUES:  return bv == 9 || bv == 11 || bv == 15;
+    case G_SELL_COLUMNS: return bv == 9;
+    case G_SELLP:        return bv == 11 || bv == 14 || bv == 15 || bv == 17;
+    case G_VIDX:         return bv == 17;
+    case G_XWIN0: case G_XWIN1: case G_XWIN2: return bv == 17 && (256 << (grp - G_XWIN0)) == vw_rows;
+    case G_SELLP2:       return bv == 14;
+    case G_SELLPX:       return bv == 15;
+    case G_ROWT:         return bv == 13;
+    case G_XLDS_PLAN:    return bv == 10 || bv == 12 || bv == 16;
+    case G_XLDS_COLUMNS: return bv == 10 || bv == 16;
+    case G_SELLX:        return bv == 12;
+    }
+    return true;
+}
+// does the group hold memory? (sgpu_debug_op_storage)
+unsigned part_storage_mask(const CsrPart &P) {
+    const bool held[G_COUNT] = {
+        P.csr.row_ptr || P.csr.col || P.csr.val || P.csr.blk_row || P.csr.blk_row_big || P.csr.rows,
+        P.dn.dense != nullptr,
+        P.cc[0].segtab || P.cc[0].segptr || P.cc[0].ccol, P.cc[1].segtab || P.cc[1].segptr || P.cc[1].ccol,
+        P.cm[0].val || P.cm[0].col || P.cm[0].dst || P.cm[0].ptr, P.cm[1].val || P.cm[1].col || P.cm[1].dst || P.cm[1].ptr,
+        P.sv.sl_val || P.sv.sl_ptr || P.sv.sl_perm,
+        P.sc.sl_col || P.sc.sl_len || P.sc.sl_base || P.sc.sl_segptr,
+        P.sp.sp_pat || P.sp.sp_tab || P.sp.sp_wgptr || P.sp.sp_rbase,
+        P.vi.vi_code || P.vi.vi_cptr || P.vi.vi_dptr || P.vi.vi_dict,
+        P.vw[0].tab || P.vw[0].win, P.vw[1].tab || P.vw[1].win, P.vw[2].tab || P.vw[2].win,
+        P.sp2.sp2_val || P.sp2.sp2_ptr,
+        P.spx.spx_tab || P.spx.spx_pat || P.spx.spx_win || P.spx.spx_wgptr,
+        P.rt.rt_pat || P.rt.rt_itab || P.rt.rt_vtab,
+        P.xlp.xl_blk || P.xlp.xl_info || P.xlp.xl_acc || P.xlp.xl_ord,
+        P.xlc.xl_col || P.xlc.xl_tab,
+        P.sx.sx_val || P.sx.sx_col || P.sx.sx_meta || P.sx.sx_bptr || P.sx.sx_sptr,
+    };
+    unsigned m = 0;
+    for (int i = 0; i < G_COUNT; ++i) if (held[i]) m |= 1u << i;
+    return m;
+}
 
 // How many leading slices of a sliced-ELLPACK operator beyond the 256 MiB Infinity Cache are read with plain loads (they
 // allocate in the cache and the next sweep over the operator finds them there), the rest being non-temporal (they do not
@@ -341,13 +355,13 @@ int build_part(CsrPart &P, std::vector<int> &&rp, std::vector<int> &&col, const 
     P.nblk  = (int)blk.size() - 1;
     P.nblk_big = (int)blk_big.size() - 1;
     P.lanes = auto_lanes(P.nrows, P.nblk);
-    CHK(dev_upload(&P.blk_row_big, blk_big.data(), blk_big.size()));
-    CHK(dev_upload(&P.row_ptr, rp.data(), rp.size()));
-    CHK(dev_upload(&P.col, col.data(), col.size(), 8));
-    CHK(dev_upload(&P.val, val, nval, 8));
-    CHK(dev_upload(&P.blk_row, blk.data(), blk.size()));
+    CHK(dev_upload(P.csr.blk_row_big, blk_big.data(), blk_big.size()));
+    CHK(dev_upload(P.csr.row_ptr, rp.data(), rp.size()));
+    CHK(dev_upload(P.csr.col, col.data(), col.size(), 8));
+    CHK(dev_upload(P.csr.val, val, nval, 8));
+    CHK(dev_upload(P.csr.blk_row, blk.data(), blk.size()));
     P.h_rp = std::move(rp); P.h_col = std::move(col); P.h_blk = blk; P.h_blk_big = blk_big;
-    if (rows) CHK(dev_upload(&P.rows, rows->data(), rows->size()));
+    if (rows) CHK(dev_upload(P.csr.rows, rows->data(), rows->size()));
     return SGPU_OK;
 }
 
@@ -360,12 +374,12 @@ bool dense_candidate(int nrows, int ncols, int64_t nnz) {
     return nrows > 0 && ncols > 0 && nnz > 0 && nrows <= DENSE_MAX_ROWS && (int64_t)nrows * ncols <= (int64_t)DENSE_MAX_ROWS * DENSE_MAX_ROWS;
 }
 int build_dense(CsrPart &P) {
-    if (P.dense) return SGPU_OK;
+    if (P.dn.dense) return SGPU_OK;
     if (P.h_val.empty() || P.h_rp.empty()) return fail(SGPU_ERR_ARG, "this operator is too large for the dense form (more than 8192 rows or 64 M entries on this rank)");
     std::vector<double> d((size_t)P.nrows * P.ncols, 0.0);
     for (int i = 0; i < P.nrows; ++i)
         for (int k = P.h_rp[i]; k < P.h_rp[i + 1]; ++k) d[(size_t)i * P.ncols + P.h_col[k]] = P.h_val[k];
-    CHK(dev_upload(&P.dense, d.data(), d.size()));
+    CHK(dev_upload(P.dn.dense, d.data(), d.size()));
     return SGPU_OK;
 }
 
@@ -440,24 +454,21 @@ bool encode_cc16(const CsrPart &P, const std::vector<int> &blk, std::vector<unsi
 // The same encoding ON THE DEVICE (round 4), from the 32-bit columns already there: *ok = false when a block touches more than 256
 // segments of 256 columns (the form does not apply) or the operator has more columns than the kernels' bitmap covers (the caller
 // falls back to the host encoder).  d_blk: the row-block boundaries on the device; ccol gets nnz + 8 codes (CSR order).
-int encode_cc16_device(const CsrPart &P, const int *d_blk, int nblk, unsigned short **ccol, int **segptr_d, int **segtab_d, int *ob_out, bool *ok, bool *host_fallback,
+int encode_cc16_device(const CsrPart &P, const int *d_blk, int nblk, DevArr<unsigned short> &ccol, DevArr<int> &segptr_d, DevArr<int> &segtab_d, int *ob_out, bool *ok, bool *host_fallback,
                        const int *d_perm = nullptr) {       // d_perm (k_sell<sorted>): d_blk bounds slice POSITIONS, position q holds row d_perm[q]
     *ok = false; *host_fallback = false;
-    *ccol = nullptr; *segptr_d = nullptr; *segtab_d = nullptr;
     const int ncols = std::max(1, P.ncols);
-    if (!P.col || !P.row_ptr || nblk <= 0) { *host_fallback = true; return SGPU_OK; }
+    if (!P.csr.col || !P.csr.row_ptr || nblk <= 0) { *host_fallback = true; return SGPU_OK; }
     if (std::getenv("SAENA_HOST_CC16")) { *host_fallback = true; return SGPU_OK; }
-    int *d_cnt = nullptr, *d_bad = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_cnt), ((size_t)nblk + 1) * sizeof(int)));
-    struct Tmp { int *a, *b; ~Tmp() { hipFree(a); hipFree(b); } } tmp{d_cnt, nullptr};
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(int)));
-    tmp.b = d_bad;
+    DevArr<int> d_cnt, d_bad;
+    HIPCHK(d_cnt.alloc((size_t)nblk + 1));
+    HIPCHK(d_bad.alloc(1));
     std::vector<int> cnt((size_t)nblk), segptr((size_t)nblk + 1, 0);
     for (int ob = 12; ob >= 8; --ob) {
         const int maxseg = 1 << (16 - ob), nsegs_total = (ncols >> ob) + 1, nwords = (nsegs_total + 31) / 32;
         if (nwords > sk::CC_BM_WORDS) { if (ob == 8) { *host_fallback = true; return SGPU_OK; } continue; }   // (a finer split needs a larger bitmap still)
         HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), g.cs));
-        SGPU_LAUNCH(sk::k_cc16_count, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const int *)P.col, (const int *)P.row_ptr, d_blk, ob, nwords, maxseg, d_cnt, d_bad, d_perm);
+        SGPU_LAUNCH(sk::k_cc16_count, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const int *)P.csr.col, (const int *)P.csr.row_ptr, d_blk, ob, nwords, maxseg, d_cnt.get(), d_bad.get(), d_perm);
         HIPCHK(hipGetLastError());
         int bad = 0;
         HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, g.cs));
@@ -467,12 +478,12 @@ int encode_cc16_device(const CsrPart &P, const int *d_blk, int nblk, unsigned sh
         for (int b = 0; b < nblk; ++b) segptr[(size_t)b + 1] = segptr[(size_t)b] + cnt[(size_t)b];
         CHK(dev_upload(segptr_d, segptr.data(), segptr.size()));
         const size_t nt = (size_t)segptr.back() + 1;
-        if (hipMalloc(reinterpret_cast<void **>(segtab_d), nt * sizeof(int)) != hipSuccess) { *segtab_d = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the segment tables failed"); }
-        HIPCHK(hipMemsetAsync(*segtab_d, 0, nt * sizeof(int), g.cs));
+        if (segtab_d.alloc(nt) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the segment tables failed");
+        HIPCHK(hipMemsetAsync(segtab_d, 0, nt * sizeof(int), g.cs));
         const size_t nc = (size_t)P.nnz + 8;
-        if (hipMalloc(reinterpret_cast<void **>(ccol), nc * sizeof(unsigned short)) != hipSuccess) { *ccol = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the column codes failed"); }
-        HIPCHK(hipMemsetAsync(*ccol, 0, nc * sizeof(unsigned short), g.cs));
-        SGPU_LAUNCH(sk::k_cc16_encode, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const int *)P.col, (const int *)P.row_ptr, d_blk, ob, nwords, (const int *)*segptr_d, *segtab_d, *ccol, d_perm);
+        if (ccol.alloc(nc) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the column codes failed");
+        HIPCHK(hipMemsetAsync(ccol, 0, nc * sizeof(unsigned short), g.cs));
+        SGPU_LAUNCH(sk::k_cc16_encode, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const int *)P.csr.col, (const int *)P.csr.row_ptr, d_blk, ob, nwords, (const int *)segptr_d, segtab_d.get(), ccol.get(), d_perm);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(g.cs));
         *ob_out = ob; *ok = true;
@@ -482,36 +493,35 @@ int encode_cc16_device(const CsrPart &P, const int *d_blk, int nblk, unsigned sh
 }
 
 int build_cc16(CsrPart &P, int k) {
-    if (P.cc_ok[k] || P.cc_tried[k] || P.h_rp.empty()) return SGPU_OK;
-    P.cc_tried[k] = 1;
+    if (P.cc[k].ok || P.cc[k].tried || P.h_rp.empty()) return SGPU_OK;
+    P.cc[k].tried = 1;
     const std::vector<int> &blk = k ? P.h_blk_big : P.h_blk;
     if (blk.size() < 2) return SGPU_OK;
     int ob = 12;
     {   // on the device, from the 32-bit columns already there (round 4)
         bool ok = false, fallback = false;
-        unsigned short *d_ccol = nullptr; int *d_segptr = nullptr, *d_segtab = nullptr;
-        CHK(encode_cc16_device(P, k ? P.blk_row_big : P.blk_row, (int)blk.size() - 1, &d_ccol, &d_segptr, &d_segtab, &ob, &ok, &fallback));
-        if (ok) { P.ccol[k] = d_ccol; P.segptr[k] = d_segptr; P.segtab[k] = d_segtab; P.cc_ob[k] = ob; P.cc_ok[k] = true; return SGPU_OK; }
+        CHK(encode_cc16_device(P, k ? P.csr.blk_row_big : P.csr.blk_row, (int)blk.size() - 1, P.cc[k].ccol, P.cc[k].segptr, P.cc[k].segtab, &ob, &ok, &fallback));
+        if (ok) { P.cc_ob[k] = ob; P.cc[k].ok = true; return SGPU_OK; }
         if (!fallback) return SGPU_OK;                                    // a block touches more than 256 segments of 256 columns
     }
     std::vector<unsigned short> ccol;
     std::vector<int> segptr, segtab;
     if (!encode_cc16(P, blk, ccol, segptr, segtab, ob)) return SGPU_OK;   // a block touches more than 256 segments of 256 columns
-    CHK(dev_upload(&P.segtab[k], segtab.data(), segtab.size(), 1));
-    CHK(dev_upload(&P.segptr[k], segptr.data(), segptr.size()));
-    CHK(dev_upload(&P.ccol[k], ccol.data(), ccol.size()));
+    CHK(dev_upload(P.cc[k].segtab, segtab.data(), segtab.size(), 1));
+    CHK(dev_upload(P.cc[k].segptr, segptr.data(), segptr.size()));
+    CHK(dev_upload(P.cc[k].ccol, ccol.data(), ccol.size()));
     P.cc_ob[k] = ob;
-    P.cc_ok[k] = true;
+    P.cc[k].ok = true;
     return SGPU_OK;
 }
 
 // column-major-in-block form of plan k (needs the compressed columns of the same plan and the host copy of the values)
 int build_cm(CsrPart &P, int k, const std::vector<double> &h_val_all) {
-    if (P.cm_ok[k] || P.cm_tried[k] || P.h_rp.empty()) return SGPU_OK;
-    P.cm_tried[k] = 1;
+    if (P.cm[k].ok || P.cm[k].tried || P.h_rp.empty()) return SGPU_OK;
+    P.cm[k].tried = 1;
     CHK(build_cc16(P, k));
-    const bool on_device = P.val && P.col && P.ccol[k] && P.row_ptr && !std::getenv("SAENA_HOST_CM_BUILD");
-    if (!P.cc_ok[k] || (!on_device && h_val_all.size() != P.h_col.size())) return SGPU_OK;
+    const bool on_device = P.csr.val && P.csr.col && P.cc[k].ccol && P.csr.row_ptr && !std::getenv("SAENA_HOST_CM_BUILD");
+    if (!P.cc[k].ok || (!on_device && h_val_all.size() != P.h_col.size())) return SGPU_OK;
     const std::vector<int> &blk = k ? P.h_blk_big : P.h_blk;
     const int cap = k ? sk::CAP_BIG : sk::CAP;
     const int nblk = (int)blk.size() - 1;
@@ -526,25 +536,25 @@ int build_cm(CsrPart &P, int k, const std::vector<double> &h_val_all) {
         cmptr[(size_t)b + 1] = cmptr[(size_t)b] + ((n + 3) & ~3);
     }
     const size_t tot = (size_t)cmptr[(size_t)nblk];
-    if (P.val && P.col && P.ccol[k] && P.row_ptr && !std::getenv("SAENA_HOST_CM_BUILD")) {
+    if (P.csr.val && P.csr.col && P.cc[k].ccol && P.csr.row_ptr && !std::getenv("SAENA_HOST_CM_BUILD")) {
         // on the device (round 4): the block's entries sorted by (column, CSR position) in LDS, values and column codes taken from the
         // arrays already there
-        CHK(dev_upload(&P.cm_ptr[k], cmptr.data(), cmptr.size()));
+        CHK(dev_upload(P.cm[k].ptr, cmptr.data(), cmptr.size()));
         const size_t nv = tot + 8;
-        if (hipMalloc(reinterpret_cast<void **>(&P.cm_val[k]), nv * sizeof(double)) != hipSuccess) { P.cm_val[k] = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the column-ordered values failed"); }
-        if (hipMalloc(reinterpret_cast<void **>(&P.cm_col[k]), nv * sizeof(unsigned short)) != hipSuccess) { P.cm_col[k] = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the column-ordered codes failed"); }
-        if (hipMalloc(reinterpret_cast<void **>(&P.cm_dst[k]), nv * sizeof(unsigned short)) != hipSuccess) { P.cm_dst[k] = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the tile slots failed"); }
-        HIPCHK(hipMemsetAsync(P.cm_val[k], 0, nv * sizeof(double), g.cs));
-        HIPCHK(hipMemsetAsync(P.cm_col[k], 0, nv * sizeof(unsigned short), g.cs));
-        HIPCHK(hipMemsetAsync(P.cm_dst[k], 0xff, nv * sizeof(unsigned short), g.cs));      // (the 8 spare entries past the end: never a valid slot)
-        const int *d_blk = k ? P.blk_row_big : P.blk_row;
-        if (k) SGPU_LAUNCH(sk::k_cm_build<sk::CAP_BIG>, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const double *)P.val, (const int *)P.col, (const unsigned short *)P.ccol[k],
-                           (const int *)P.row_ptr, d_blk, (const int *)P.cm_ptr[k], P.cm_val[k], P.cm_col[k], P.cm_dst[k]);
-        else SGPU_LAUNCH(sk::k_cm_build<sk::CAP>, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const double *)P.val, (const int *)P.col, (const unsigned short *)P.ccol[k],
-                         (const int *)P.row_ptr, d_blk, (const int *)P.cm_ptr[k], P.cm_val[k], P.cm_col[k], P.cm_dst[k]);
+        if (P.cm[k].val.alloc(nv) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the column-ordered values failed");
+        if (P.cm[k].col.alloc(nv) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the column-ordered codes failed");
+        if (P.cm[k].dst.alloc(nv) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the tile slots failed");
+        HIPCHK(hipMemsetAsync(P.cm[k].val, 0, nv * sizeof(double), g.cs));
+        HIPCHK(hipMemsetAsync(P.cm[k].col, 0, nv * sizeof(unsigned short), g.cs));
+        HIPCHK(hipMemsetAsync(P.cm[k].dst, 0xff, nv * sizeof(unsigned short), g.cs));      // (the 8 spare entries past the end: never a valid slot)
+        const int *d_blk = k ? P.csr.blk_row_big : P.csr.blk_row;
+        if (k) SGPU_LAUNCH(sk::k_cm_build<sk::CAP_BIG>, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const double *)P.csr.val, (const int *)P.csr.col, (const unsigned short *)P.cc[k].ccol,
+                           (const int *)P.csr.row_ptr, d_blk, (const int *)P.cm[k].ptr, P.cm[k].val, P.cm[k].col, P.cm[k].dst);
+        else SGPU_LAUNCH(sk::k_cm_build<sk::CAP>, dim3(nblk), dim3(sk::BLOCK), 0, g.cs, (const double *)P.csr.val, (const int *)P.csr.col, (const unsigned short *)P.cc[k].ccol,
+                         (const int *)P.csr.row_ptr, d_blk, (const int *)P.cm[k].ptr, P.cm[k].val, P.cm[k].col, P.cm[k].dst);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(g.cs));
-        P.cm_ok[k] = true;
+        P.cm[k].ok = true;
         return SGPU_OK;
     }
     // the 16-bit column codes of plan k live on the device only: re-encode on the host with the block's (sorted) table
@@ -581,11 +591,11 @@ int build_cm(CsrPart &P, int k, const std::vector<double> &h_val_all) {
         for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
         for (auto &x : th) x.join();
     }
-    CHK(dev_upload(&P.cm_val[k], val.data(), val.size()));
-    CHK(dev_upload(&P.cm_col[k], col.data(), col.size()));
-    CHK(dev_upload(&P.cm_dst[k], dst.data(), dst.size()));
-    CHK(dev_upload(&P.cm_ptr[k], cmptr.data(), cmptr.size()));
-    P.cm_ok[k] = true;
+    CHK(dev_upload(P.cm[k].val, val.data(), val.size()));
+    CHK(dev_upload(P.cm[k].col, col.data(), col.size()));
+    CHK(dev_upload(P.cm[k].dst, dst.data(), dst.size()));
+    CHK(dev_upload(P.cm[k].ptr, cmptr.data(), cmptr.size()));
+    P.cm[k].ok = true;
     return SGPU_OK;
 }
 
@@ -593,8 +603,8 @@ int build_cm(CsrPart &P, int k, const std::vector<double> &h_val_all) {
 // touches into windows of XL_MAX; 16-bit column ids relative to the window, per chunk a table of each row's entry offsets
 // per window.  Refused when a chunk needs more than XL_MAXT windows.
 int build_xlds(CsrPart &P) {
-    if (P.xl_ok || P.xl_tried || P.h_rp.empty()) return SGPU_OK;
-    P.xl_tried = 1;
+    if (P.xlp.xl_ok || P.xlp.xl_tried || P.h_rp.empty()) return SGPU_OK;
+    P.xlp.xl_tried = 1;
     const int M = P.nrows;
     if (M == 0 || P.nnz == 0) return SGPU_OK;
     const int nb = std::min(std::max(1, sk::XL_PER_CU * g.ncu), M);
@@ -660,21 +670,21 @@ int build_xlds(CsrPart &P) {
             std::stable_sort(ord.begin() + r0, ord.begin() + r0 + rows, [&](int x, int y) {
                 return P.h_rp[r0 + x + 1] - P.h_rp[r0 + x] > P.h_rp[r0 + y + 1] - P.h_rp[r0 + y]; });
         }
-        if (!ord.empty()) CHK(dev_upload(&P.xl_ord, ord.data(), ord.size()));
+        if (!ord.empty()) CHK(dev_upload(P.xlp.xl_ord, ord.data(), ord.size()));
     }
     P.xl_piece = (double)P.nnz / (double)std::max<int64_t>(1, pieces);    // mean entries per (row, window): the autotune wants >= 24
     P.xl_blk_h = blk; P.xl_info_h = info;
-    CHK(dev_upload(&P.xl_blk, blk.data(), blk.size()));
-    CHK(dev_upload(&P.xl_info, info.data(), info.size()));
-    if (P.col && P.row_ptr && !std::getenv("SAENA_HOST_XLDS_BUILD")) {
+    CHK(dev_upload(P.xlp.xl_blk, blk.data(), blk.size()));
+    CHK(dev_upload(P.xlp.xl_info, info.data(), info.size()));
+    if (P.csr.col && P.csr.row_ptr && !std::getenv("SAENA_HOST_XLDS_BUILD")) {
         // the window-relative columns and the (row, window) offsets on the device, from the 32-bit columns already there (round 4)
         const size_t nc = P.h_col.size() + 8, ntab = (size_t)tabsz + 1;
-        if (hipMalloc(reinterpret_cast<void **>(&P.xl_col), nc * sizeof(unsigned short)) != hipSuccess) { P.xl_col = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the x-in-LDS columns failed"); }
-        if (hipMalloc(reinterpret_cast<void **>(&P.xl_tab), ntab * sizeof(int)) != hipSuccess) { P.xl_tab = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of the x-in-LDS table failed"); }
-        HIPCHK(hipMemsetAsync(P.xl_col, 0, nc * sizeof(unsigned short), g.cs));
-        HIPCHK(hipMemsetAsync(P.xl_tab, 0, ntab * sizeof(int), g.cs));
-        SGPU_LAUNCH(sk::k_xlds_build, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const int *)P.col, (const int *)P.row_ptr, (const int *)P.xl_blk, (const int4 *)P.xl_info,
-                    P.xl_tab, P.xl_col, win);
+        if (P.xlc.xl_col.alloc(nc) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the x-in-LDS columns failed");
+        if (P.xlc.xl_tab.alloc(ntab) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of the x-in-LDS table failed");
+        HIPCHK(hipMemsetAsync(P.xlc.xl_col, 0, nc * sizeof(unsigned short), g.cs));
+        HIPCHK(hipMemsetAsync(P.xlc.xl_tab, 0, ntab * sizeof(int), g.cs));
+        SGPU_LAUNCH(sk::k_xlds_build, dim3(nb), dim3(sk::BLOCK), 0, g.cs, (const int *)P.csr.col, (const int *)P.csr.row_ptr, (const int *)P.xlp.xl_blk, (const int4 *)P.xlp.xl_info,
+                    P.xlc.xl_tab, P.xlc.xl_col, win);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(g.cs));
     } else {
@@ -705,13 +715,13 @@ int build_xlds(CsrPart &P) {
         for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
         for (auto &x : th) x.join();
     }
-    CHK(dev_upload(&P.xl_col, col.data(), col.size()));
-    CHK(dev_upload(&P.xl_tab, tab.data(), tab.size()));
+    CHK(dev_upload(P.xlc.xl_col, col.data(), col.size()));
+    CHK(dev_upload(P.xlc.xl_tab, tab.data(), tab.size()));
     }
-    if (maxt > 1 && !acc_lds) HIPCHK(hipMalloc(&P.xl_acc, (size_t)M * sizeof(double)));
+    if (maxt > 1 && !acc_lds) HIPCHK(P.xlp.xl_acc.alloc((size_t)M));
     P.xl_nblk = nb;
     P.xl_maxt = maxt;
-    P.xl_ok = true;
+    P.xlp.xl_ok = true;
     return SGPU_OK;
 }
 
@@ -747,8 +757,8 @@ static const int SL_SORT_WINDOW = [] {
     return std::max(256, (w / 256) * 256);
 }();
 int build_sell_values(CsrPart &P) {
-    if (P.sl_vals || P.sl_vals_tried || P.h_rp.empty() || !P.val || !P.row_ptr) return SGPU_OK;
-    P.sl_vals_tried = 1;
+    if (P.sv.sl_vals || P.sv.sl_vals_tried || P.h_rp.empty() || !P.csr.val || !P.csr.row_ptr) return SGPU_OK;
+    P.sv.sl_vals_tried = 1;
     const int M = P.nrows;
     if (M == 0) return SGPU_OK;
     const int ns = (M + 63) / 64;
@@ -793,24 +803,24 @@ int build_sell_values(CsrPart &P) {
         }
         static const double sorted_limit = std::getenv("SAENA_SELL_SORTED_PAD") ? atof(std::getenv("SAENA_SELL_SORTED_PAD")) : 1.05;
         if ((double)tot > sorted_limit * (double)P.nnz) return SGPU_OK;
-        CHK(dev_upload(&P.sl_perm, perm.data(), perm.size()));
-        P.sl_sorted = true;
+        CHK(dev_upload(P.sv.sl_perm, perm.data(), perm.size()));
+        P.sv.sl_sorted = true;
     }
-    if (!P.sl_sorted) P.sl_uw = uniform_width(ptr, 64, &tot);      // (pads the last slice up to the others' width where that makes them all equal)
+    if (!P.sv.sl_sorted) P.sl_uw = uniform_width(ptr, 64, &tot);      // (pads the last slice up to the others' width where that makes them all equal)
     // 16-byte value loads pay from a few pairs per row on, and on any operator that streams from HBM (256^3 L0, 7 entries
     // per row: 338 vs 343-350 us); the cache-resident 128^3 fine level is the one case that prefers single positions
     const bool pair = P.nnz >= 16 * (int64_t)M || 10 * P.nnz > (int64_t)256 * 1024 * 1024;
     P.sl_pair = pair;
-    CHK(dev_upload(&P.sl_ptr, ptr.data(), ptr.size()));
+    CHK(dev_upload(P.sv.sl_ptr, ptr.data(), ptr.size()));
     const size_t nv = (size_t)tot + 64;
-    if (hipMalloc(reinterpret_cast<void **>(&P.sl_val), nv * sizeof(double)) != hipSuccess) { P.sl_val = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nv * sizeof(double)); }
-    HIPCHK(hipMemsetAsync(P.sl_val, 0, nv * sizeof(double), g.cs));
-    SGPU_LAUNCH(sk::k_sell_scatter<double>, dim3((M + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), 0, g.cs, (const double *)P.val, (const int *)P.row_ptr,
-                (const int *)P.sl_ptr, P.sl_val, M, pair ? 1 : 0, (const int *)P.sl_perm);
+    if (P.sv.sl_val.alloc(nv) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nv * sizeof(double));
+    HIPCHK(hipMemsetAsync(P.sv.sl_val, 0, nv * sizeof(double), g.cs));
+    SGPU_LAUNCH(sk::k_sell_scatter<double>, dim3((M + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), 0, g.cs, (const double *)P.csr.val, (const int *)P.csr.row_ptr,
+                (const int *)P.sv.sl_ptr, P.sv.sl_val, M, pair ? 1 : 0, (const int *)P.sv.sl_perm);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
     P.nslices = ns;
-    P.sl_vals = true;
+    P.sv.sl_vals = true;
     return SGPU_OK;
 }
 
@@ -818,7 +828,7 @@ int build_sell(CsrPart &P, const std::vector<double> &) {
     if (P.sl_ok || P.sl_tried || P.h_rp.empty()) return SGPU_OK;
     P.sl_tried = 1;
     CHK(build_sell_values(P));
-    if (!P.sl_vals) return SGPU_OK;
+    if (!P.sv.sl_vals) return SGPU_OK;
     const int M = P.nrows, ns = P.nslices;
     std::vector<int> grp;                                        // row groups of one workgroup: 4 slices
     for (int r = 0; r < M; r += 256) grp.push_back(r);
@@ -826,47 +836,44 @@ int build_sell(CsrPart &P, const std::vector<double> &) {
     std::vector<unsigned short> ccol, len((size_t)ns * 64, 0);
     std::vector<int> segptr, segtab;
     int ob = 12;
-    if (P.sl_sorted) {                                            // the length of the row that sits at each slice position
+    if (P.sv.sl_sorted) {                                            // the length of the row that sits at each slice position
         std::vector<int> perm((size_t)ns * 64);
-        HIPCHK(hipMemcpy(perm.data(), P.sl_perm, perm.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(perm.data(), P.sv.sl_perm, perm.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int q = 0; q < M; ++q) len[(size_t)q] = (unsigned short)(P.h_rp[perm[(size_t)q] + 1] - P.h_rp[perm[(size_t)q]]);
     } else
     for (int r = 0; r < M; ++r) len[(size_t)r] = (unsigned short)(P.h_rp[r + 1] - P.h_rp[r]);
     // the codes in CSR order (made on the device where the bitmap covers the operator's columns, else on the host and uploaded)
     // take the values' way into the slice layout (padding keeps code 0: slot 0, offset 0 = a valid column of the group)
-    unsigned short *d_ccol = nullptr;
+    DevArr<unsigned short> d_ccol;
     bool dev_tabs = false;
     {
-        int *d_grp = nullptr;
-        CHK(dev_upload(&d_grp, grp.data(), grp.size()));
-        struct G { int *p; ~G() { hipFree(p); } } gfree{d_grp};
+        DevArr<int> d_grp;
+        CHK(dev_upload(d_grp, grp.data(), grp.size()));
         bool ok = false, fallback = false;
-        int *d_segptr = nullptr, *d_segtab = nullptr;
-        CHK(encode_cc16_device(P, d_grp, (int)grp.size() - 1, &d_ccol, &d_segptr, &d_segtab, &ob, &ok, &fallback, P.sl_perm));
-        if (ok) { P.sl_segptr = d_segptr; P.sl_base = d_segtab; dev_tabs = true; }
-        else if (!fallback || P.sl_sorted) return SGPU_OK;             // (the host encoder knows no permutation: operators of more columns than the device's bitmap covers keep CSR)
+        CHK(encode_cc16_device(P, d_grp, (int)grp.size() - 1, d_ccol, P.sc.sl_segptr, P.sc.sl_base, &ob, &ok, &fallback, P.sv.sl_perm));
+        if (ok) dev_tabs = true;
+        else if (!fallback || P.sv.sl_sorted) return SGPU_OK;             // (the host encoder knows no permutation: operators of more columns than the device's bitmap covers keep CSR)
     }
     if (!dev_tabs) {
         if (!encode_cc16(P, grp, ccol, segptr, segtab, ob)) return SGPU_OK;
-        CHK(dev_upload(&d_ccol, ccol.data(), ccol.size()));
+        CHK(dev_upload(d_ccol, ccol.data(), ccol.size()));
     }
-    struct Tmp { unsigned short *p; ~Tmp() { hipFree(p); } } tmp{d_ccol};
     int tot = 0;
-    HIPCHK(hipMemcpy(&tot, P.sl_ptr + ns, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&tot, P.sv.sl_ptr + ns, sizeof(int), hipMemcpyDeviceToHost));
     const size_t nc = (size_t)tot + 64;
-    if (hipMalloc(reinterpret_cast<void **>(&P.sl_col), nc * sizeof(unsigned short)) != hipSuccess) { P.sl_col = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nc * 2); }
-    HIPCHK(hipMemsetAsync(P.sl_col, 0, nc * sizeof(unsigned short), g.cs));
-    SGPU_LAUNCH(sk::k_sell_scatter<unsigned short>, dim3((M + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), 0, g.cs, (const unsigned short *)d_ccol, (const int *)P.row_ptr,
-                (const int *)P.sl_ptr, P.sl_col, M, P.sl_pair ? 1 : 0, (const int *)P.sl_perm);
+    if (P.sc.sl_col.alloc(nc) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nc * 2);
+    HIPCHK(hipMemsetAsync(P.sc.sl_col, 0, nc * sizeof(unsigned short), g.cs));
+    SGPU_LAUNCH(sk::k_sell_scatter<unsigned short>, dim3((M + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), 0, g.cs, (const unsigned short *)d_ccol, (const int *)P.csr.row_ptr,
+                (const int *)P.sv.sl_ptr, P.sc.sl_col, M, P.sl_pair ? 1 : 0, (const int *)P.sv.sl_perm);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
     if (std::getenv("SAENA_SETUP_TIMING"))
-        fprintf(stderr, "[sgpu] sliced ELLPACK%s: %d rows, %lld entries, %.1f %% padding, columns %d+%d bits\n", P.sl_sorted ? " (rows sorted by length per window)" : "",
+        fprintf(stderr, "[sgpu] sliced ELLPACK%s: %d rows, %lld entries, %.1f %% padding, columns %d+%d bits\n", P.sv.sl_sorted ? " (rows sorted by length per window)" : "",
                 M, (long long)P.nnz, 100.0 * ((double)tot / (double)P.nnz - 1.0), 16 - ob, ob);
-    CHK(dev_upload(&P.sl_len, len.data(), len.size()));
+    CHK(dev_upload(P.sc.sl_len, len.data(), len.size()));
     if (!dev_tabs) {
-        CHK(dev_upload(&P.sl_base, segtab.data(), segtab.size(), 1));
-        CHK(dev_upload(&P.sl_segptr, segptr.data(), segptr.size()));
+        CHK(dev_upload(P.sc.sl_base, segtab.data(), segtab.size(), 1));
+        CHK(dev_upload(P.sc.sl_segptr, segptr.data(), segptr.size()));
     }
     P.sl_ob = ob;
     P.sl_ok = true;
@@ -888,10 +895,10 @@ constexpr int SP_MAX_TABLE = 4096;
 // Poisson hierarchy repeat 30 (R0) / 33 (P0) such patterns where they follow tens of thousands relative to the row index.
 int build_sellp_mode(CsrPart &P, bool rowbase);
 int build_sellp(CsrPart &P) {
-    if (P.sp_ok || P.sp_tried || !P.sl_vals || P.sl_sorted || P.h_rp.empty()) return SGPU_OK;     // (sorted slices: positions are not rows)
-    P.sp_tried = 1;
+    if (P.sp.sp_ok || P.sp.sp_tried || !P.sv.sl_vals || P.sv.sl_sorted || P.h_rp.empty()) return SGPU_OK;     // (sorted slices: positions are not rows)
+    P.sp.sp_tried = 1;
     CHK(build_sellp_mode(P, false));
-    if (!P.sp_ok && !std::getenv("SAENA_NO_SELLP_ROWBASE")) CHK(build_sellp_mode(P, true));
+    if (!P.sp.sp_ok && !std::getenv("SAENA_NO_SELLP_ROWBASE")) CHK(build_sellp_mode(P, true));
     return SGPU_OK;
 }
 int build_sellp_mode(CsrPart &P, bool rowbase) {
@@ -1026,15 +1033,15 @@ int build_sellp_mode(CsrPart &P, bool rowbase) {
     if (rowbase) {
         std::vector<int> rb((size_t)((M + 127) / 128 * 128), 0);
         for (int r = 0; r < M; ++r) rb[(size_t)r] = ref(r);
-        CHK(dev_upload(&P.sp_rbase, rb.data(), rb.size()));
+        CHK(dev_upload(P.sp.sp_rbase, rb.data(), rb.size()));
     }
-    CHK(dev_upload(&P.sp_pat, wide ? lpat.data() : pat.data(), pat.size()));
-    CHK(dev_upload(&P.sp_tab, tab.data(), tab.size()));
-    if (wide) CHK(dev_upload(&P.sp_wgptr, wgptr.data(), wgptr.size()));
-    P.sp_w = wide ? (int)max_group : W; P.sp_n = npat; P.sp_wide = wide;
+    CHK(dev_upload(P.sp.sp_pat, wide ? lpat.data() : pat.data(), pat.size()));
+    CHK(dev_upload(P.sp.sp_tab, tab.data(), tab.size()));
+    if (wide) CHK(dev_upload(P.sp.sp_wgptr, wgptr.data(), wgptr.size()));
+    P.sp_w = wide ? (int)max_group : W; P.sp_n = npat; P.sp.sp_wide = wide;
     P.h_pstart = std::move(cstart); P.h_ptab = std::move(ctab); P.h_pat = std::move(pat);      // (for build_sellpx; dropped when the plan settles)
     P.sp_bytes = 8 * (int64_t)P.h_rp.back() + (rowbase ? 6 : 2) * (int64_t)M + 8 * (int64_t)P.ncols + 8 * (int64_t)M + (wide ? 4 * (int64_t)tab.size() : 0);
-    P.sp_ok = true;
+    P.sp.sp_ok = true;
     return SGPU_OK;
 }
 
@@ -1045,8 +1052,8 @@ int build_sellp_mode(CsrPart &P, bool rowbase) {
 // appearance -- and its rows' ids count within it.  The form applies when windows and the largest of these tables fit
 // SPX_LDS_BYTES (two workgroups per CU).
 int build_sellpx(CsrPart &P) {
-    if (P.spx_ok || P.spx_tried || !P.sp_ok || P.sp_rbase || !P.sl_val || P.h_ptab.empty() || P.h_pat.empty()) return SGPU_OK;
-    P.spx_tried = 1;
+    if (P.spx.spx_ok || P.spx.spx_tried || !P.sp.sp_ok || P.sp.sp_rbase || !P.sv.sl_val || P.h_ptab.empty() || P.h_pat.empty()) return SGPU_OK;
+    P.spx.spx_tried = 1;
     const int npat = (int)P.h_pstart.size(), M = P.nrows;
     std::vector<int> offs;
     for (int i = 0; i < npat; ++i) {
@@ -1118,11 +1125,11 @@ int build_sellpx(CsrPart &P) {
     win[0] = nwin;
     for (int c = 0; c < nwin; ++c) { win[1 + 3 * (size_t)c] = omin[(size_t)c]; win[2 + 3 * (size_t)c] = base[(size_t)c]; win[3 + 3 * (size_t)c] = sk::SPX_ROWS + (omax[(size_t)c] - omin[(size_t)c]); }
     tab.resize(tab.size() + 8, 0);
-    CHK(dev_upload(&P.spx_tab, tab.data(), tab.size()));
-    CHK(dev_upload(&P.spx_wgptr, wgptr.data(), wgptr.size()));
-    CHK(dev_upload(&P.spx_pat, lpat.data(), lpat.size()));
-    CHK(dev_upload(&P.spx_win, win.data(), win.size()));
-    P.spx_ok = true;
+    CHK(dev_upload(P.spx.spx_tab, tab.data(), tab.size()));
+    CHK(dev_upload(P.spx.spx_wgptr, wgptr.data(), wgptr.size()));
+    CHK(dev_upload(P.spx.spx_pat, lpat.data(), lpat.size()));
+    CHK(dev_upload(P.spx.spx_win, win.data(), win.size()));
+    P.spx.spx_ok = true;
     return SGPU_OK;
 }
 
@@ -1130,8 +1137,8 @@ int build_sellpx(CsrPart &P) {
 // dictionary per workgroup of 256 rows, built on the device from the CSR values (k_vi_build).  Slices of 64 rows, each padded to its
 // longest row rounded up to 8 positions.  The operator is refused where a workgroup holds more than VI_MAX distinct values.
 int build_vidx(CsrPart &P) {
-    if (P.vi_ok || P.vi_tried || !P.sp_ok || P.sp_wide || P.h_rp.empty() || !P.val || !P.row_ptr) return SGPU_OK;
-    P.vi_tried = 1;
+    if (P.vi.vi_ok || P.vi.vi_tried || !P.sp.sp_ok || P.sp.sp_wide || P.h_rp.empty() || !P.csr.val || !P.csr.row_ptr) return SGPU_OK;
+    P.vi.vi_tried = 1;
     const int M = P.nrows;
     if (M == 0) return SGPU_OK;
     const int ns = (M + 63) / 64, ngrp = (ns + 3) / 4;
@@ -1152,38 +1159,37 @@ int build_vidx(CsrPart &P) {
     if (uniform && w8_0 > 0 && (int64_t)ns * w8_0 * 64 <= (int64_t)INT32_MAX - 1024) tot = (int64_t)ns * w8_0 * 64;
     else uniform = false;
     const size_t nb = (size_t)tot + 512;
-    if (hipMalloc(reinterpret_cast<void **>(&P.vi_code), nb) != hipSuccess) { P.vi_code = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nb); }
-    HIPCHK(hipMemsetAsync(P.vi_code, 0, nb, g.cs));
-    if (!uniform) CHK(dev_upload(&P.vi_cptr, ptr.data(), ptr.size()));
-    DevBuf tmp;
-    int *d_cnt = nullptr, *d_flag = nullptr;
-    CHK(tmp.alloc((size_t)ngrp * sk::VI_MAX));
-    if (hipMalloc(reinterpret_cast<void **>(&d_cnt), ((size_t)ngrp + 1) * sizeof(int)) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc failed");
-    struct F { int *p; ~F() { hipFree(p); } } fcnt{d_cnt};
-    d_flag = d_cnt + ngrp;
+    if (P.vi.vi_code.alloc(nb) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nb);
+    HIPCHK(hipMemsetAsync(P.vi.vi_code, 0, nb, g.cs));
+    if (!uniform) CHK(dev_upload(P.vi.vi_cptr, ptr.data(), ptr.size()));
+    DevArr<double> tmp;
+    DevArr<int> d_cnt;
+    CHK(dev_alloc(tmp, (size_t)ngrp * sk::VI_MAX));
+    if (d_cnt.alloc((size_t)ngrp + 1) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc failed");
+    int *d_flag = d_cnt + ngrp;
     HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g.cs));
-    SGPU_LAUNCH(sk::k_vi_build, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)P.val, (const int *)P.row_ptr, (const int *)P.vi_cptr,
-                uniform ? w8_0 : 0, M, P.vi_code, tmp.p, d_cnt, d_flag);
+    SGPU_LAUNCH(sk::k_vi_build, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)P.csr.val, (const int *)P.csr.row_ptr, (const int *)P.vi.vi_cptr,
+                uniform ? w8_0 : 0, M, P.vi.vi_code.get(), tmp.get(), d_cnt.get(), d_flag);
     HIPCHK(hipGetLastError());
     std::vector<int> cnt((size_t)ngrp + 1);
     HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
     HIPCHK(hipStreamSynchronize(g.cs));
     if (cnt[(size_t)ngrp]) {                                   // a workgroup holds more than VI_MAX distinct values: refused
         if (std::getenv("SAENA_SETUP_TIMING")) fprintf(stderr, "[sgpu] value-indexed form refused: a workgroup of 256 rows holds more than %d distinct values\n", sk::VI_MAX);
-        hipFree(P.vi_code); hipFree(P.vi_cptr); P.vi_code = nullptr; P.vi_cptr = nullptr;
+        P.vi.vi_code = {}; P.vi.vi_cptr = {};
         return SGPU_OK;
     }
     std::vector<int> dptr((size_t)ngrp + 1, 0);
     int dmax = 0;
     for (int b = 0; b < ngrp; ++b) { dptr[(size_t)b + 1] = dptr[(size_t)b] + cnt[(size_t)b]; dmax = std::max(dmax, cnt[(size_t)b]); }
-    CHK(dev_upload(&P.vi_dptr, dptr.data(), dptr.size()));
-    CHK(dev_upload(&P.vi_dict, (const double *)nullptr, 0, (size_t)dptr[(size_t)ngrp] + 1));
-    SGPU_LAUNCH(sk::k_vi_compact, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)tmp.p, (const int *)P.vi_dptr, P.vi_dict);
+    CHK(dev_upload(P.vi.vi_dptr, dptr.data(), dptr.size()));
+    CHK(dev_upload(P.vi.vi_dict, (const double *)nullptr, 0, (size_t)dptr[(size_t)ngrp] + 1));
+    SGPU_LAUNCH(sk::k_vi_compact, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)tmp, (const int *)P.vi.vi_dptr, P.vi.vi_dict.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
     P.vi_uw8 = uniform ? w8_0 : 0;
-    P.vi_bytes = tot + (P.sp_rbase ? 6 : 2) * (int64_t)M + 8 * (int64_t)P.ncols + 8 * (int64_t)M + 8 * (int64_t)dptr[(size_t)ngrp];
-    P.vi_ok = true;
+    P.vi_bytes = tot + (P.sp.sp_rbase ? 6 : 2) * (int64_t)M + 8 * (int64_t)P.ncols + 8 * (int64_t)M + 8 * (int64_t)dptr[(size_t)ngrp];
+    P.vi.vi_ok = true;
     if (std::getenv("SAENA_SETUP_TIMING"))
         fprintf(stderr, "[sgpu] value-indexed row patterns: %d rows, %lld entries, %lld code bytes (%.2f per entry), at most %d distinct values per workgroup of 256 rows, %d in all dictionaries\n",
                 M, (long long)P.nnz, (long long)tot, (double)tot / (double)std::max<int64_t>(1, P.nnz), dmax, dptr[(size_t)ngrp]);
@@ -1200,15 +1206,15 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     const int R = 256 << k;
     auto no = [&](const char *m) { if (why) *why = m; return SGPU_OK; };
     if (X.ok) return SGPU_OK;
-    if (!P.vi_ok || !P.sp_ok || !P.sp_tab) return no("the value-indexed form was not built");
-    if (P.sp_rbase) return no("the patterns are relative to the rows' first columns (rowbase)");
-    if (P.sp_wide) return no("the patterns sit in per-workgroup tables");
+    if (!P.vi.vi_ok || !P.sp.sp_ok || !P.sp.sp_tab) return no("the value-indexed form was not built");
+    if (P.sp.sp_rbase) return no("the patterns are relative to the rows' first columns (rowbase)");
+    if (P.sp.sp_wide) return no("the patterns sit in per-workgroup tables");
     if (X.tried) return no("refused before");
     X.tried = 1;
     const int npat = P.sp_n, W = P.sp_w, M = P.nrows;
     if (npat <= 0 || W <= 0) return no("no patterns");
     std::vector<int> tab((size_t)npat * (W + 1));
-    HIPCHK(hipMemcpyAsync(tab.data(), P.sp_tab, tab.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
+    HIPCHK(hipMemcpyAsync(tab.data(), P.sp.sp_tab, tab.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
     HIPCHK(hipStreamSynchronize(g.cs));
     std::vector<int> offs;
     for (int i = 0; i < npat; ++i) {
@@ -1250,8 +1256,8 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     std::vector<int> win(2 + 2 * (size_t)std::max(nwin, 4), INT32_MAX);          // (the kernel reads the first four windows unconditionally: unused ones never match)
     win[0] = nwin; win[1] = (int)S;
     for (int c = 0; c < nwin; ++c) { win[2 + 2 * (size_t)c] = base[(size_t)c]; win[3 + 2 * (size_t)c] = omin[(size_t)c] - base[(size_t)c]; }
-    CHK(dev_upload(&X.tab, t16.data(), t16.size(), 8));
-    CHK(dev_upload(&X.win, win.data(), win.size()));
+    CHK(dev_upload(X.tab, t16.data(), t16.size(), 8));
+    CHK(dev_upload(X.win, win.data(), win.size()));
     X.wp = wp; X.lds = (int)lds; X.ok = true;
     if (std::getenv("SAENA_SETUP_TIMING"))
         fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row)\n",
@@ -1262,10 +1268,10 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
 // The row-paired values of k_sellp2 on top of build_sellp's pattern ids: slices of 128 rows, a slice padded to its longest
 // row, position-major with the values of rows 2 l and 2 l + 1 side by side.
 int build_sellp2(CsrPart &P, const std::vector<double> &h_val_all) {
-    if (P.sp2_ok || P.sp2_tried || !P.sp_ok || P.sp_rbase || P.h_rp.empty()) return SGPU_OK;      // (rows r and r + 1 of a rowbase operator do not read adjacent columns)
-    P.sp2_tried = 1;
+    if (P.sp2.sp2_ok || P.sp2.sp2_tried || !P.sp.sp_ok || P.sp.sp_rbase || P.h_rp.empty()) return SGPU_OK;      // (rows r and r + 1 of a rowbase operator do not read adjacent columns)
+    P.sp2.sp2_tried = 1;
     const int M = P.nrows;
-    if (M < 2 || P.ncols < 2 || !P.val || !P.row_ptr) return SGPU_OK;      // (the kernel reads x 16 bytes at a time)
+    if (M < 2 || P.ncols < 2 || !P.csr.val || !P.csr.row_ptr) return SGPU_OK;      // (the kernel reads x 16 bytes at a time)
     const int ns = (M + 127) / 128;
     std::vector<int> ptr((size_t)ns + 1, 0);
     int64_t tot = 0;
@@ -1278,16 +1284,16 @@ int build_sellp2(CsrPart &P, const std::vector<double> &h_val_all) {
     }
     if ((double)tot > 1.12 * (double)P.nnz) return SGPU_OK;
     P.sp2_uw = uniform_width(ptr, 128, &tot);
-    CHK(dev_upload(&P.sp2_ptr, ptr.data(), ptr.size()));
+    CHK(dev_upload(P.sp2.sp2_ptr, ptr.data(), ptr.size()));
     const size_t nv = (size_t)tot + 128;
-    if (hipMalloc(reinterpret_cast<void **>(&P.sp2_val), nv * sizeof(double)) != hipSuccess) { P.sp2_val = nullptr; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nv * sizeof(double)); }
-    HIPCHK(hipMemsetAsync(P.sp2_val, 0, nv * sizeof(double), g.cs));
-    SGPU_LAUNCH(sk::k_sell_scatter<double>, dim3((M + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), 0, g.cs, (const double *)P.val, (const int *)P.row_ptr,
-                (const int *)P.sp2_ptr, P.sp2_val, M, 2);            // (round 4: from the CSR values on the device, like build_sell_values)
+    if (P.sp2.sp2_val.alloc(nv) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nv * sizeof(double));
+    HIPCHK(hipMemsetAsync(P.sp2.sp2_val, 0, nv * sizeof(double), g.cs));
+    SGPU_LAUNCH(sk::k_sell_scatter<double>, dim3((M + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), 0, g.cs, (const double *)P.csr.val, (const int *)P.csr.row_ptr,
+                (const int *)P.sp2.sp2_ptr, P.sp2.sp2_val, M, 2);            // (round 4: from the CSR values on the device, like build_sell_values)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
     P.sp2_nslices = ns;
-    P.sp2_ok = true;
+    P.sp2.sp2_ok = true;
     return SGPU_OK;
 }
 
@@ -1295,8 +1301,8 @@ int build_sellp2(CsrPart &P, const std::vector<double> &h_val_all) {
 // follow at most 65 535 templates whose tables fit 32 KiB of LDS.  Ids in order of first appearance.
 constexpr int RT_MAX_BYTES = 32768;
 int build_rowt(CsrPart &P, const std::vector<double> &h_val_all) {
-    if (P.rt_ok || P.rt_tried || P.h_rp.empty()) return SGPU_OK;
-    P.rt_tried = 1;
+    if (P.rt.rt_ok || P.rt.rt_tried || P.h_rp.empty()) return SGPU_OK;
+    P.rt.rt_tried = 1;
     const int M = P.nrows;
     if (M == 0 || h_val_all.size() != P.h_col.size()) return SGPU_OK;
     int W = 1;
@@ -1335,11 +1341,11 @@ int build_rowt(CsrPart &P, const std::vector<double> &h_val_all) {
     }
     if (npat == 0) return SGPU_OK;
     if (std::getenv("SAENA_SETUP_TIMING")) fprintf(stderr, "[sgpu] row templates: %d rows follow %d templates of <= %d entries\n", M, npat, W);
-    CHK(dev_upload(&P.rt_pat, pat.data(), pat.size()));
-    CHK(dev_upload(&P.rt_itab, itab.data(), itab.size()));
-    CHK(dev_upload(&P.rt_vtab, vtab.data(), vtab.size()));
+    CHK(dev_upload(P.rt.rt_pat, pat.data(), pat.size()));
+    CHK(dev_upload(P.rt.rt_itab, itab.data(), itab.size()));
+    CHK(dev_upload(P.rt.rt_vtab, vtab.data(), vtab.size()));
     P.rt_w = W; P.rt_n = npat;
-    P.rt_ok = true;
+    P.rt.rt_ok = true;
     return SGPU_OK;
 }
 
@@ -1347,8 +1353,8 @@ int build_rowt(CsrPart &P, const std::vector<double> &h_val_all) {
 // in that window (every row in the chunk's last window), sorted by piece length, 64 to a slice, position-major in pairs.
 // Built where it can pay: at most 25 % padding, chunks of at most 65 534 rows.
 int build_sellx(CsrPart &P, const std::vector<double> &h_val_all) {
-    if (P.sx_ok || P.sx_tried || !P.xl_ok || P.xl_blk_h.empty()) return SGPU_OK;
-    P.sx_tried = 1;
+    if (P.sx.sx_ok || P.sx.sx_tried || !P.xlp.xl_ok || P.xl_blk_h.empty()) return SGPU_OK;
+    P.sx.sx_tried = 1;
     if (h_val_all.size() != P.h_col.size()) return SGPU_OK;
     const int nb = P.xl_nblk;
     const std::vector<int> &blk = P.xl_blk_h;
@@ -1440,13 +1446,13 @@ int build_sellx(CsrPart &P, const std::vector<double> &h_val_all) {
     if (std::getenv("SAENA_SETUP_TIMING"))
         fprintf(stderr, "[sgpu] sliced ELLPACK in LDS windows: %d rows, %lld entries, %.1f %% padding, %lld slices in %d chunks of <= %d windows\n", P.nrows,
                 (long long)P.nnz, 100.0 * (P.sx_pad - 1.0), (long long)nsl, nb, P.xl_maxt);
-    CHK(dev_upload(&P.sx_val, val.data(), val.size()));
-    CHK(dev_upload(&P.sx_col, col.data(), col.size()));
-    CHK(dev_upload(&P.sx_meta, meta.data(), meta.size(), 64));
-    CHK(dev_upload(&P.sx_sptr, sptr.data(), sptr.size()));
-    CHK(dev_upload(&P.sx_bptr, bptr.data(), bptr.size()));
-    if (!P.xl_acc && P.xl_maxt > 1 && !P.xl_acc_lds) HIPCHK(hipMalloc(&P.xl_acc, (size_t)P.nrows * sizeof(double)));
-    P.sx_ok = true;
+    CHK(dev_upload(P.sx.sx_val, val.data(), val.size()));
+    CHK(dev_upload(P.sx.sx_col, col.data(), col.size()));
+    CHK(dev_upload(P.sx.sx_meta, meta.data(), meta.size(), 64));
+    CHK(dev_upload(P.sx.sx_sptr, sptr.data(), sptr.size()));
+    CHK(dev_upload(P.sx.sx_bptr, bptr.data(), bptr.size()));
+    if (!P.xlp.xl_acc && P.xl_maxt > 1 && !P.xl_acc_lds) HIPCHK(P.xlp.xl_acc.alloc((size_t)P.nrows));
+    P.sx.sx_ok = true;
     return SGPU_OK;
 }
 
@@ -1456,20 +1462,20 @@ struct sgpu_op {
     index_t M = 0, N_local = 0;
     CsrPart loc, rem;
     bool    has_remote = false;
-    double *inv_diag = nullptr;
-    double *tmp = nullptr;        // smoother ping-pong buffer [M]
-    double *ones = nullptr;       // [M] of 1.0 (sgpu_residual_negative: rhs - A u as 1 * 1 * (rhs - A u)), made at its first call
-    double *dvec = nullptr;       // chebyshev d [M]
+    DevArr<double> inv_diag;
+    DevArr<double> tmp;           // smoother ping-pong buffer [M]
+    DevArr<double> ones;          // [M] of 1.0 (sgpu_residual_negative: rhs - A u as 1 * 1 * (rhs - A u)), made at its first call
+    DevArr<double> dvec;          // chebyshev d [M]
     // block entry points (sgpu_*_block): lanes per row of k_csr_block (0: from the mean row length at the first block apply),
     // and the block ping-pong buffer / Chebyshev d of [M * K] per K = 2, 4, 8, made at the first block smoother call with that K
     // (never re-allocated: captured block V-cycles hold the pointers)
     int     block_lanes = 0, block_lanes_auto = 0;
-    double *tmp_blk[3] = {nullptr, nullptr, nullptr}, *dvec_blk[3] = {nullptr, nullptr, nullptr};
+    DevArr<double> tmp_blk[3], dvec_blk[3];
     // halo plan
     int     vIndexSize = 0, recvSize = 0;
-    int    *vIndex = nullptr;
-    double *send_buf = nullptr, *recv_buf = nullptr;
-    float  *send_f = nullptr, *recv_f = nullptr;      // fp32 wire buffers (halo_fp32 && nranks > 1)
+    DevArr<int>    vIndex;
+    DevArr<double> send_buf, recv_buf;
+    DevArr<float>  send_f, recv_f;                    // fp32 wire buffers (halo_fp32 && nranks > 1)
     std::vector<int> sendRank, sendCount, sendDispl, recvRank, recvCount, recvDispl;
     int     halo_fp32 = 0;
     bool    injected = false;     // test hook: halo supplied by sgpu_debug_inject_halo
@@ -1477,18 +1483,14 @@ struct sgpu_op {
     bool    single_stream = false; // exchange and rows on the compute stream, in order (short local kernels): apply() mode S
     bool    events_only = false;   // long interior kernel: the two streams are ordered by plain events (apply() mode E)
     std::string vname;            // sgpu_op_get_variant's kernel name (owns the string it returns)
-    double *dense_rem = nullptr;  // variant 5 with a halo: row-major M x recvSize over the receive buffer
-    std::vector<int> rem_rows_h;  // host copy of rem.rows (compact boundary row -> local row)
+    DevArr<double> dense_rem;     // variant 5 with a halo: row-major M x recvSize over the receive buffer
+    std::vector<int> rem_rows_h;  // host copy of rem.csr.rows (compact boundary row -> local row)
     std::vector<double> h_val;   // host copy of the values of small local parts (coarsest-level factorisation)
     std::vector<double> h_val_all;   // host copy of all local values (kept while the column-major form may still be built)
-    unsigned *skip = nullptr;     // bitmask over the M rows: set = boundary row (has remote entries), written by k_csr_boundary
+    DevArr<unsigned> skip;        // bitmask over the M rows: set = boundary row (has remote entries), written by k_csr_boundary
     int     bnd_lanes = 1;        // lanes per boundary row
     hipEvent_t ev_x = nullptr, ev_halo = nullptr;   // cs -> hs: inputs ready; hs -> cs: exchange + boundary rows done
-    ~sgpu_op() {                  // also runs when sgpu_op_create bails out half-way: nothing leaks
-        loc.free_all(); rem.free_all();
-        hipFree(dense_rem);
-        for (int k = 0; k < 3; ++k) { hipFree(tmp_blk[k]); hipFree(dvec_blk[k]); }
-        hipFree(skip); hipFree(inv_diag); hipFree(tmp); hipFree(ones); hipFree(dvec); hipFree(vIndex); hipFree(send_buf); hipFree(recv_buf); hipFree(send_f); hipFree(recv_f);
+    ~sgpu_op() {                  // also runs when sgpu_op_create bails out half-way; the arrays free themselves
         if (ev_x) hipEventDestroy(ev_x);
         if (ev_halo) hipEventDestroy(ev_halo);
     }
@@ -1504,7 +1506,7 @@ int build_dense_rem(sgpu_op *op) {
     // rem: CSR over the boundary rows (h_rows maps compact -> local row), columns = receive-buffer positions
     for (int i = 0; i < op->rem.nrows; ++i)
         for (int k = op->rem.h_rp[i]; k < op->rem.h_rp[i + 1]; ++k) d[(size_t)op->rem_rows_h[(size_t)i] * nh + op->rem.h_col[k]] = op->rem.h_val[k];
-    CHK(dev_upload(&op->dense_rem, d.data(), d.size()));
+    CHK(dev_upload(op->dense_rem, d.data(), d.size()));
     return SGPU_OK;
 }
 
@@ -1628,7 +1630,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
     if (P.nblk == 0) return SGPU_OK;
     sk::SpmvArgs a = spmv_args(x, y, e);
     a.flag_x = seq ? g.kflag_x : nullptr; a.seq = seq;
-    a.row_ptr = P.row_ptr; a.col = P.col; a.val = P.val;
+    a.row_ptr = P.csr.row_ptr; a.col = P.csr.col; a.val = P.csr.val;
     a.skip = skip; a.ncols = P.ncols;
     static const int st_plain_env = std::getenv("SAENA_STORE_PLAIN") ? std::atoi(std::getenv("SAENA_STORE_PLAIN")) : 0;
     a.st_plain = st_plain_env;
@@ -1638,7 +1640,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
     switch (P.variant) {
     default: {                                                    // 0, 1: 32-bit columns, 16 / 32 KiB tiles
         const bool big = P.variant == 1;
-        a.blk_row = big ? P.blk_row_big : P.blk_row;
+        a.blk_row = big ? P.csr.blk_row_big : P.csr.blk_row;
         a.nblk = big ? P.nblk_big : P.nblk;
         SGPU_LAUNCH_PICKED("k_csr_stream", pick_tile<0>(epi, P.lanes, big, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     } break;
@@ -1649,17 +1651,17 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
     } break;
     case 3: case 4: {                                             // 16-bit compressed columns
         const int k = P.variant - 3;
-        if (!P.cc_ok[k]) return fail(SGPU_ERR_STATE, "compressed columns of plan %d were not built", k);
-        a.blk_row = k ? P.blk_row_big : P.blk_row;
+        if (!P.cc[k].ok) return fail(SGPU_ERR_STATE, "compressed columns of plan %d were not built", k);
+        a.blk_row = k ? P.csr.blk_row_big : P.csr.blk_row;
         a.nblk = k ? P.nblk_big : P.nblk;
-        a.segtab = P.segtab[k]; a.segptr = P.segptr[k]; a.ccol = P.ccol[k]; a.cc_ob = P.cc_ob[k];
+        a.segtab = P.cc[k].segtab; a.segptr = P.cc[k].segptr; a.ccol = P.cc[k].ccol; a.cc_ob = P.cc_ob[k];
         SGPU_LAUNCH_PICKED("k_csr_cc16", pick_tile<1>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     } break;
     case 5: {                                                     // dense rows, one wave per row
-        if (!P.dense) return fail(SGPU_ERR_STATE, "the dense form was not built");
+        if (!P.dn.dense) return fail(SGPU_ERR_STATE, "the dense form was not built");
         if (halo) return fail(SGPU_ERR_STATE, "the dense form serves operators without a halo");
         a.blk_row = nullptr; a.nblk = 0;
-        SGPU_LAUNCH_PICKED("k_dense_rows", pick_dense(epi), dim3((P.nrows + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, (const double *)P.dense, P.nrows, P.ncols);
+        SGPU_LAUNCH_PICKED("k_dense_rows", pick_dense(epi), dim3((P.nrows + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, (const double *)P.dn.dense, P.nrows, P.ncols);
     } break;
     case 6: {                                                     // wave-streamed long rows, 16-byte loads
         const int gl = std::max(8, P.lanes), rpb = sk::BLOCK / gl;
@@ -1668,100 +1670,100 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
     } break;
     case 7: case 8: {                                             // compressed columns, entries in column order inside a block
         const int k = P.variant - 7;
-        if (!P.cm_ok[k]) return fail(SGPU_ERR_STATE, "the column-major form of plan %d was not built", k);
-        a.blk_row = k ? P.blk_row_big : P.blk_row;
+        if (!P.cm[k].ok) return fail(SGPU_ERR_STATE, "the column-major form of plan %d was not built", k);
+        a.blk_row = k ? P.csr.blk_row_big : P.csr.blk_row;
         a.nblk = k ? P.nblk_big : P.nblk;
-        a.segtab = P.segtab[k]; a.segptr = P.segptr[k]; a.cc_ob = P.cc_ob[k];
-        a.val = P.cm_val[k]; a.ccol = P.cm_col[k]; a.dst = P.cm_dst[k]; a.cmptr = P.cm_ptr[k];
+        a.segtab = P.cc[k].segtab; a.segptr = P.cc[k].segptr; a.cc_ob = P.cc_ob[k];
+        a.val = P.cm[k].val; a.ccol = P.cm[k].col; a.dst = P.cm[k].dst; a.cmptr = P.cm[k].ptr;
         SGPU_LAUNCH_PICKED("k_csr_cm", pick_tile<2>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     } break;
     case 9: {                                                     // sliced ELLPACK, a lane per row
         if (!P.sl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK form was not built");
-        a.blk_row = P.sl_sorted ? P.sl_perm : nullptr; a.nblk = P.nslices;
-        a.val = P.sl_val; a.ccol = P.sl_col; a.segtab = P.sl_base; a.segptr = P.sl_segptr; a.cc_ob = P.sl_ob; a.cmptr = P.sl_ptr; a.dst = P.sl_len;
+        a.blk_row = P.sv.sl_sorted ? P.sv.sl_perm : nullptr; a.nblk = P.nslices;
+        a.val = P.sv.sl_val; a.ccol = P.sc.sl_col; a.segtab = P.sc.sl_base; a.segptr = P.sc.sl_segptr; a.cc_ob = P.sl_ob; a.cmptr = P.sv.sl_ptr; a.dst = P.sc.sl_len;
         // non-temporal streams once the stored operator is beyond the 256 MiB Infinity Cache (k_sellp in kernels.hip.h; 128^3 L1,
         // 843 MB: 127 -> 121 us, profiles/r03_sell_nt.log)
         static const int nt_env = std::getenv("SAENA_SELL_NT") ? std::atoi(std::getenv("SAENA_SELL_NT")) : -1;
         const bool nt = nt_env >= 0 ? nt_env != 0 : 10 * P.nnz + 18 * (int64_t)P.nrows > (int64_t)256 * 1024 * 1024;
         // sorted slices: a wave's 64 stores of y name up to 64 lines of its window -- plain stores, which the L2 merges into whole lines
         static const int sorted_plain = std::getenv("SAENA_SELL_SORTED_PLAIN_STORES") ? std::atoi(std::getenv("SAENA_SELL_SORTED_PLAIN_STORES")) : 1;
-        if (P.sl_sorted && sorted_plain) a.st_plain = 1;
+        if (P.sv.sl_sorted && sorted_plain) a.st_plain = 1;
         a.nt_from = nt ? resident_slices(P.nslices, 10.0 * (double)P.nnz / (double)std::max(1, P.nslices)) : 0;
         SGPU_LAUNCH_PICKED("k_sell", pick_sell(epi, halo, P.sl_pair, nt), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
     } break;
     case 10: case 16: {                                           // x in LDS, a workgroup per CU (16: four rows per group step -- short rows)
-        if (!P.xl_ok || !P.xl_col) return fail(SGPU_ERR_STATE, "the x-in-LDS form was not built");
-        a.blk_row = P.xl_blk; a.nblk = P.xl_nblk; a.ccol = P.xl_col;
+        if (!P.xlp.xl_ok || !P.xlc.xl_col) return fail(SGPU_ERR_STATE, "the x-in-LDS form was not built");
+        a.blk_row = P.xlp.xl_blk; a.nblk = P.xl_nblk; a.ccol = P.xlc.xl_col;
         sk::XldsArgs w;
-        w.info = P.xl_info; w.tab = P.xl_tab; w.acc = P.xl_acc; w.ncols = P.ncols;
-        w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0; w.ord = P.xl_ord;
+        w.info = P.xlp.xl_info; w.tab = P.xlc.xl_tab; w.acc = P.xlp.xl_acc; w.ncols = P.ncols;
+        w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0; w.ord = P.xlp.xl_ord;
         SGPU_LAUNCH_PICKED("k_csr_xlds", P.variant == 16 ? pick_xldsr(epi, P.lanes, halo) : pick_xlds(epi, P.lanes, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
     } break;
     case 11: {                                                    // sliced ELLPACK values + row patterns, a lane per row
-        if (!P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form was not built");
+        if (!P.sp.sp_ok || !P.sv.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form was not built");
         a.blk_row = nullptr; a.nblk = P.nslices;
-        a.val = P.sl_val; a.cmptr = P.sl_ptr; a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
-        a.rbase = P.sp_rbase;
+        a.val = P.sv.sl_val; a.cmptr = P.sv.sl_ptr; a.dst = P.sp.sp_pat; a.ptab = P.sp.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
+        a.rbase = P.sp.sp_rbase;
         const bool nt = row_pattern_nt(a, P.sp_bytes, P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices));
         a.uw = P.sl_uw;
-        if (P.sp_wide) {                                          // a table per workgroup: 1024 threads, 16 slices of 64 rows
-            a.segptr = P.sp_wgptr;
+        if (P.sp.sp_wide) {                                          // a table per workgroup: 1024 threads, 16 slices of 64 rows
+            a.segptr = P.sp.sp_wgptr;
             SGPU_LAUNCH_PICKED("k_sellp", pick_sellp(epi, halo, P.sl_pair, nt, true), dim3((P.nslices + 15) / 16), dim3(sk::SPW_BLOCK), (size_t)P.sp_w * sizeof(int), g.cs, a, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_sellp", pick_sellp(epi, halo, P.sl_pair, nt, false), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
     } break;
     case 12: {                                                    // sliced ELLPACK in the LDS windows, a workgroup per CU
-        if (!P.sx_ok || !P.xl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK-in-LDS form was not built");
-        a.blk_row = P.xl_blk; a.nblk = P.xl_nblk;
+        if (!P.sx.sx_ok || !P.xlp.xl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK-in-LDS form was not built");
+        a.blk_row = P.xlp.xl_blk; a.nblk = P.xl_nblk;
         sk::SellxArgs w;
-        w.info = P.xl_info; w.bptr = P.sx_bptr; w.sptr = P.sx_sptr; w.meta = P.sx_meta; w.val = P.sx_val; w.col = P.sx_col; w.acc = P.xl_acc; w.ncols = P.ncols;
+        w.info = P.xlp.xl_info; w.bptr = P.sx.sx_bptr; w.sptr = P.sx.sx_sptr; w.meta = P.sx.sx_meta; w.val = P.sx.sx_val; w.col = P.sx.sx_col; w.acc = P.xlp.xl_acc; w.ncols = P.ncols;
         w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0;
         if (nt_rt == 0 && !std::getenv("SAENA_STREAM_NT")) a.nt = 10 * P.nnz > (int64_t)256 * 1024 * 1024 ? 1 : 0;      // non-temporal streams beyond the Infinity Cache (438 -> 426 us)
         SGPU_LAUNCH_PICKED("k_sellx", pick_sellx(epi, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
     } break;
     case 13: {                                                    // row templates: a thread per row, no operator stream at all
-        if (!P.rt_ok) return fail(SGPU_ERR_STATE, "the row-template form was not built");
+        if (!P.rt.rt_ok) return fail(SGPU_ERR_STATE, "the row-template form was not built");
         a.blk_row = nullptr; a.nblk = 0;
-        a.val = P.rt_vtab; a.dst = P.rt_pat; a.ptab = P.rt_itab; a.pt_w = P.rt_w; a.pt_n = P.rt_n;
+        a.val = P.rt.rt_vtab; a.dst = P.rt.rt_pat; a.ptab = P.rt.rt_itab; a.pt_w = P.rt_w; a.pt_n = P.rt_n;
         const bool nt = 26 * (int64_t)P.nrows > (int64_t)256 * 1024 * 1024;       // ids + x + y (+ rhs) beyond the Infinity Cache
         const size_t lds = (size_t)P.rt_n * ((size_t)P.rt_w * 8 + (size_t)(P.rt_w + 1) * 4);
         SGPU_LAUNCH_PICKED("k_rowt", pick_rowt(epi, halo, nt), dim3((P.nrows + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
     } break;
     case 14: {                                                    // k_sellp with a lane per two rows
-        if (!P.sp2_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the row-paired row-pattern form was not built");
+        if (!P.sp2.sp2_ok || !P.sp.sp_ok) return fail(SGPU_ERR_STATE, "the row-paired row-pattern form was not built");
         a.blk_row = nullptr; a.nblk = P.sp2_nslices;
-        a.val = P.sp2_val; a.cmptr = P.sp2_ptr; a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
+        a.val = P.sp2.sp2_val; a.cmptr = P.sp2.sp2_ptr; a.dst = P.sp.sp_pat; a.ptab = P.sp.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
         const bool nt = row_pattern_nt(a, P.sp_bytes, P.sp2_nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.sp2_nslices));
         a.ncols = P.ncols;
         a.uw = P.sp2_uw;
         static const int pre_env = std::getenv("SAENA_SELLP2_PRE") ? std::atoi(std::getenv("SAENA_SELLP2_PRE")) : 1;
         const bool pre = pre_env != 0 && !halo;
-        if (P.sp_wide) {                                          // a table per workgroup: 512 threads, 8 slices of 128 rows
-            a.segptr = P.sp_wgptr;
+        if (P.sp.sp_wide) {                                          // a table per workgroup: 512 threads, 8 slices of 128 rows
+            a.segptr = P.sp.sp_wgptr;
             SGPU_LAUNCH_PICKED("k_sellp2", pick_sellp2<true>(epi, halo, nt, pre), dim3((P.sp2_nslices + 7) / 8), dim3(sk::SPW2_BLOCK), (size_t)P.sp_w * sizeof(int), g.cs, a, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_sellp2", pick_sellp2<false>(epi, halo, nt, pre), dim3((P.sp2_nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
     } break;
     case 15: {                                                    // k_sellp with x in LDS windows
-        if (!P.spx_ok || !P.sp_ok || !P.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
+        if (!P.spx.spx_ok || !P.sp.sp_ok || !P.sv.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
         a.blk_row = nullptr; a.nblk = P.nslices;
-        a.val = P.sl_val; a.cmptr = P.sl_ptr; a.dst = P.spx_pat; a.ptab = reinterpret_cast<const int *>(P.spx_tab); a.pt_w = 0; a.pt_n = P.sp_n;
-        a.segtab = P.spx_win; a.segptr = P.spx_wgptr; a.ncols = P.ncols;
+        a.val = P.sv.sl_val; a.cmptr = P.sv.sl_ptr; a.dst = P.spx.spx_pat; a.ptab = reinterpret_cast<const int *>(P.spx.spx_tab.get()); a.pt_w = 0; a.pt_n = P.sp_n;
+        a.segtab = P.spx.spx_win; a.segptr = P.spx.spx_wgptr; a.ncols = P.ncols;
         const bool nt = row_pattern_nt(a, P.sp_bytes, P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices));
         SGPU_LAUNCH_PICKED("k_sellpx", pick_sellpx(epi, halo, P.sl_pair, nt), dim3((P.nslices + sk::SPX_ROWS / 64 - 1) / (sk::SPX_ROWS / 64)), dim3(sk::SPX_BLOCK), 0, g.cs, a, P.nrows);
     } break;
     case 17: {                                                    // row patterns + 8-bit value codes, a lane per row
-        if (!P.vi_ok || !P.sp_ok) return fail(SGPU_ERR_STATE, "the value-indexed row-pattern form was not built");
+        if (!P.vi.vi_ok || !P.sp.sp_ok) return fail(SGPU_ERR_STATE, "the value-indexed row-pattern form was not built");
         a.blk_row = nullptr; a.nblk = P.nslices ? P.nslices : (P.nrows + 63) / 64;
-        a.dst = P.sp_pat; a.ptab = P.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n; a.rbase = P.sp_rbase;
-        a.vcode = P.vi_code; a.vcptr = P.vi_cptr; a.vdict = P.vi_dict; a.vdptr = P.vi_dptr; a.uw = P.vi_uw8;
+        a.dst = P.sp.sp_pat; a.ptab = P.sp.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n; a.rbase = P.sp.sp_rbase;
+        a.vcode = P.vi.vi_code; a.vcptr = P.vi.vi_cptr; a.vdict = P.vi.vi_dict; a.vdptr = P.vi.vi_dptr; a.uw = P.vi_uw8;
         const bool nt = row_pattern_nt(a, P.vi_bytes, a.nblk, (double)P.nnz / (double)std::max(1, a.nblk));     // (about a byte of codes per entry)
         const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
         if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS positions
             const int k = P.vw_rows == 256 ? 0 : P.vw_rows == 512 ? 1 : 2, spb = P.vw_rows / 64;
             const CsrPart::XWin &X = P.vw[k];
             if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
-            a.ptab = reinterpret_cast<const int *>(X.tab); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
+            a.ptab = reinterpret_cast<const int *>(X.tab.get()); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
             SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
@@ -1774,9 +1776,9 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
 // dense storage with a halo: all rows in one launch after the exchange (k_dense_rows_halo)
 int launch_dense_halo(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, bool halo_is_f32, hipStream_t stream) {
     if (op->M == 0) return SGPU_OK;
-    if (!op->loc.dense || (!op->dense_rem && op->has_remote)) return fail(SGPU_ERR_STATE, "the dense form was not built");
+    if (!op->loc.dn.dense || (!op->dense_rem && op->has_remote)) return fail(SGPU_ERR_STATE, "the dense form was not built");
     const sk::SpmvArgs a = spmv_args(x, y, e);
-    SGPU_LAUNCH_PICKED("k_dense_rows_halo", pick_dense_halo(epi), dim3((op->M + 3) / 4), dim3(sk::BLOCK), 0, stream, a, (const double *)op->loc.dense, (const double *)op->dense_rem,
+    SGPU_LAUNCH_PICKED("k_dense_rows_halo", pick_dense_halo(epi), dim3((op->M + 3) / 4), dim3(sk::BLOCK), 0, stream, a, (const double *)op->loc.dn.dense, (const double *)op->dense_rem,
                 (int)op->M, op->loc.ncols, op->has_remote ? op->recvSize : 0, (const double *)op->recv_buf, halo_is_f32 ? (const float *)op->recv_f : (const float *)nullptr,
                 op->halo_fp32 ? 1 : 0);       // (an injected halo arrives as float-rounded doubles: halo_f null, x still rounded)
     HIPCHK(hipGetLastError());
@@ -1790,9 +1792,9 @@ int launch_boundary(sgpu_op *op, int epi, const double *x, double *y, const EpiA
     if (op->rem.nrows == 0) return SGPU_OK;
     sk::BoundaryArgs b;
     b.s = spmv_args(x, y, e);
-    b.s.row_ptr = op->loc.row_ptr; b.s.col = op->loc.col; b.s.val = op->loc.val;
-    b.rows = op->rem.rows; b.nrows = op->rem.nrows;
-    b.h_ptr = op->rem.row_ptr; b.h_col = op->rem.col; b.h_val = op->rem.val;
+    b.s.row_ptr = op->loc.csr.row_ptr; b.s.col = op->loc.csr.col; b.s.val = op->loc.csr.val;
+    b.rows = op->rem.csr.rows; b.nrows = op->rem.nrows;
+    b.h_ptr = op->rem.csr.row_ptr; b.h_col = op->rem.csr.col; b.h_val = op->rem.csr.val;
     b.halo = op->recv_buf; b.halo_f = halo_is_f32 ? op->recv_f : nullptr;
     const int rpb = sk::BLOCK / op->bnd_lanes;
     SGPU_LAUNCH_PICKED("k_csr_boundary", pick_bnd(epi, op->bnd_lanes), dim3((b.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, stream, b);
@@ -1955,11 +1957,11 @@ int apply(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e) {
 }
 
 int ensure_tmp(sgpu_op *op) {
-    if (!op->tmp) HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->tmp), std::max<size_t>(1, op->M) * sizeof(double)));
+    if (!op->tmp) HIPCHK(alloc_vec(op->tmp, op->M));
     return SGPU_OK;
 }
 int ensure_d(sgpu_op *op) {
-    if (!op->dvec) HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->dvec), std::max<size_t>(1, op->M) * sizeof(double)));
+    if (!op->dvec) HIPCHK(alloc_vec(op->dvec, op->M));
     return SGPU_OK;
 }
 
@@ -2109,10 +2111,10 @@ int sgpu_get_unique_id(void *out128) {
 // times a dummy matvec per level for the same decision (saena_matrix::decide_shrinking, src/saena_matrix_shrink.cpp:3-118).
 static int calibrate_chain() {
     const int n = 4096;                                  // doubles: about one face of a 64^3 block
-    double *a = nullptr, *b = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&a), n * sizeof(double)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&b), n * sizeof(double)));
-    struct Free { double *a, *b; hipEvent_t e0 = nullptr, e1 = nullptr; ~Free() { hipFree(a); hipFree(b); if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); } } fr{a, b};
+    DevArr<double> a_, b_;
+    HIPCHK(a_.alloc(n)); HIPCHK(b_.alloc(n));
+    double *a = a_, *b = b_;
+    struct Free { hipEvent_t e0 = nullptr, e1 = nullptr; ~Free() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); } } fr;
     HIPCHK(hipMemsetAsync(a, 0, n * sizeof(double), g.cs));
     HIPCHK(hipEventCreate(&fr.e0)); HIPCHK(hipEventCreate(&fr.e1));
     int peer = g.rank ^ 1;
@@ -2389,7 +2391,7 @@ int sgpu_op_create(const sgpu_op_desc *d, sgpu_op **out) {
         std::vector<unsigned> mask(((size_t)d->M + 31) / 32, 0u);
         long len = d->nnz_l_remote;
         for (int r : rows) { mask[(size_t)r >> 5] |= 1u << (r & 31); len += d->nnzPerRow_local[r]; }
-        CHK(dev_upload(&op->skip, mask.data(), mask.size()));
+        CHK(dev_upload(op->skip, mask.data(), mask.size()));
         // lanes per boundary row: about one lane per entry (a G-lane group then reads its row as one coalesced
         // segment; one lane per 7-entry row made the launch 2.5x slower).  SAENA_BOUNDARY_LANES=1 restores the
         // reference's sequential per-row sum on these rows.
@@ -2399,7 +2401,7 @@ int sgpu_op_create(const sgpu_op_desc *d, sgpu_op **out) {
         if (const char *bl = std::getenv("SAENA_BOUNDARY_LANES")) gl = std::max(1, std::min(64, pow2floor(std::atoi(bl))));
         op->bnd_lanes = gl;
     }
-    if (d->inv_diag) CHK(dev_upload(&op->inv_diag, d->inv_diag, (size_t)d->M));
+    if (d->inv_diag) CHK(dev_upload(op->inv_diag, d->inv_diag, (size_t)d->M));
 
     // halo plan
     op->vIndexSize = d->vIndexSize;
@@ -2426,16 +2428,16 @@ int sgpu_op_create(const sgpu_op_desc *d, sgpu_op **out) {
     if (d->vIndexSize) {
         for (index_t i = 0; i < d->vIndexSize; ++i)
             if (d->vIndex[i] < 0 || d->vIndex[i] >= d->N_local) return fail(SGPU_ERR_ARG, "vIndex out of range");
-        CHK(dev_upload(&op->vIndex, d->vIndex, (size_t)d->vIndexSize));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->send_buf), (size_t)d->vIndexSize * sizeof(double)));
+        CHK(dev_upload(op->vIndex, d->vIndex, (size_t)d->vIndexSize));
+        HIPCHK(op->send_buf.alloc((size_t)d->vIndexSize));
     }
     if (op->recvSize) {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->recv_buf), (size_t)op->recvSize * sizeof(double)));
+        HIPCHK(op->recv_buf.alloc((size_t)op->recvSize));
         HIPCHK(hipMemsetAsync(op->recv_buf, 0, (size_t)op->recvSize * sizeof(double), g.cs));
     }
     if (op->halo_fp32 && g.multi()) {
-        if (op->vIndexSize) HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->send_f), (size_t)op->vIndexSize * sizeof(float)));
-        if (op->recvSize) HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->recv_f), (size_t)op->recvSize * sizeof(float)));
+        if (op->vIndexSize) HIPCHK(op->send_f.alloc((size_t)op->vIndexSize));
+        if (op->recvSize) HIPCHK(op->recv_f.alloc((size_t)op->recvSize));
     }
     {   // Two streams pay when the interior kernel is long enough to hide part of the exchange chain behind.
         // SAENA_SINGLE_STREAM_NNZ overrides the nnz threshold (0: never).
@@ -2507,7 +2509,7 @@ int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_nam
             const_cast<sgpu_op *>(op)->vname = buf;
             *kernel_name = op->vname.c_str();
         } else {
-            *kernel_name = (v == 17 && op->loc.sp_rbase) ? "k_vidx<rowbase>" : (v == 11 && op->loc.sp_rbase) ? (op->loc.sp_wide ? "k_sellp<wide,rowbase>" : "k_sellp<rowbase>") : (v == 11 && op->loc.sp_wide) ? "k_sellp<wide>" : (v == 14 && op->loc.sp_wide) ? "k_sellp2<wide>" : (v == 9 && op->loc.sl_sorted) ? "k_sell<sorted>" : VARIANT_NAMES[v];      // the compact table around 1024 threads
+            *kernel_name = (v == 17 && op->loc.sp.sp_rbase) ? "k_vidx<rowbase>" : (v == 11 && op->loc.sp.sp_rbase) ? (op->loc.sp.sp_wide ? "k_sellp<wide,rowbase>" : "k_sellp<rowbase>") : (v == 11 && op->loc.sp.sp_wide) ? "k_sellp<wide>" : (v == 14 && op->loc.sp.sp_wide) ? "k_sellp2<wide>" : (v == 9 && op->loc.sv.sl_sorted) ? "k_sell<sorted>" : VARIANT_NAMES[v];      // the compact table around 1024 threads
         }
     }
     return SGPU_OK;
@@ -2520,7 +2522,7 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
         CHK(build_sell_values(op->loc));
         CHK(build_sellp(op->loc));
         CHK(build_vidx(op->loc));
-        if (!op->loc.vi_ok)
+        if (!op->loc.vi.vi_ok)
             return fail(SGPU_ERR_ARG, "the value-indexed row-pattern form needs what the row-pattern form needs (k_sellp) with ONE pattern table, and at most %d "
                                       "distinct values (as bit patterns) in every group of %d rows", sk::VI_MAX, sk::BLOCK);
     }
@@ -2528,7 +2530,7 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
         CHK(build_sell_values(op->loc));
         CHK(build_sellp(op->loc));
         CHK(build_sellpx(op->loc));
-        if (!op->loc.spx_ok)
+        if (!op->loc.spx.spx_ok)
             return fail(SGPU_ERR_ARG, "the row-pattern form with x in LDS needs what the row-pattern form needs (k_sellp) and pattern offsets that fall into at most %d "
                                       "windows of x which fit %d KiB of LDS together with the table", sk::SPX_MAXWIN, sk::SPX_LDS_BYTES / 1024);
     }
@@ -2536,32 +2538,32 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
         CHK(build_sell_values(op->loc));
         CHK(build_sellp(op->loc));
         CHK(build_sellp2(op->loc, op->h_val_all));
-        if (!op->loc.sp2_ok)
+        if (!op->loc.sp2.sp2_ok)
             return fail(SGPU_ERR_ARG, "the row-paired row-pattern form needs what the row-pattern form needs (k_sellp) and the host copy of the values");
     }
     if (variant == 13) {
         CHK(build_rowt(op->loc, op->h_val_all));
-        if (!op->loc.rt_ok)
+        if (!op->loc.rt.rt_ok)
             return fail(SGPU_ERR_ARG, "the row-template form needs rows that repeat at most %d bytes' worth of (length, relative columns, values) templates "
                                       "and the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)", RT_MAX_BYTES);
     }
     if (variant == 12) {
         CHK(build_xlds(op->loc));
         CHK(build_sellx(op->loc, op->h_val_all));
-        if (!op->loc.sx_ok)
+        if (!op->loc.sx.sx_ok)
             return fail(SGPU_ERR_ARG, "the sliced-ELLPACK-in-LDS form needs the x-in-LDS plan (row chunks over at most %d column windows), at most 25 %% padding "
                                       "and the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)", sk::XL_MAXT);
     }
     if (variant == 11) {
         CHK(build_sell_values(op->loc));
         CHK(build_sellp(op->loc));
-        if (!op->loc.sp_ok)
+        if (!op->loc.sp.sp_ok)
             return fail(SGPU_ERR_ARG, "the row-pattern form needs what the sliced-ELLPACK form needs and rows that follow at most %d-int's worth of "
                                       "(length, relative columns) patterns per group of %d rows", sk::SPW_MAX_TABLE, sk::SPW_BLOCK);
     }
     if (variant == 10 || variant == 16) {
         CHK(build_xlds(op->loc));
-        if (!op->loc.xl_ok)
+        if (!op->loc.xlp.xl_ok)
             return fail(SGPU_ERR_ARG, "the x-in-LDS form needs row chunks (one per CU) that reach over at most %d columns",
                         sk::XL_MAXT * sk::XL_MAX);
     }
@@ -2575,12 +2577,12 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
         CHK(build_dense_rem(op));
     } else if (variant == 7 || variant == 8) {
         CHK(build_cm(op->loc, variant - 7, op->h_val_all));
-        if (!op->loc.cm_ok[variant - 7])
+        if (!op->loc.cm[variant - 7].ok)
             return fail(SGPU_ERR_ARG, "the column-major form needs compressed columns, no row longer than the tile and the host copy of the values "
                                       "(kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)");
     } else if (variant == 3 || variant == 4) {
         CHK(build_cc16(op->loc, variant - 3));
-        if (!op->loc.cc_ok[variant - 3]) return fail(SGPU_ERR_ARG, "a row block of this operator touches more than 256 column segments of 256 columns");
+        if (!op->loc.cc[variant - 3].ok) return fail(SGPU_ERR_ARG, "a row block of this operator touches more than 256 column segments of 256 columns");
     }
     op->loc.variant = variant;
     op->loc.vw_rows = 0;                                 // variant 17 alone gathers directly; sgpu_op_set_x_windows turns the windows on
@@ -2696,48 +2698,43 @@ void plan_cache_store(uint64_t key, const sgpu_op *op, int v, int lanes, int xw,
     if (::write(fd, line, (size_t)n) != n) { /* a cache: best effort */ }
     ::close(fd);
 }
-// drop what the chosen plan does not need: alternative forms on the device, the host copy of the values
+// drop what the chosen plan does not need: alternative forms on the device (every group plan_keeps() does not name), the host copy
+// of the values
 void finish_plan(sgpu_op *op, int bv) {
-    if (bv != 5 && op->loc.dense) { hipFree(op->loc.dense); op->loc.dense = nullptr; }
-    const bool keep = std::getenv("SAENA_KEEP_HOST_VALUES") != nullptr;   // development sweeps switch variants after the autotune
-    for (int k = 0; k < 2 && !keep; ++k)              // the column-major copies of the plans that lost
-        if (op->loc.cm_ok[k] && bv != 7 + k) {
-            hipFree(op->loc.cm_val[k]); hipFree(op->loc.cm_col[k]); hipFree(op->loc.cm_dst[k]); hipFree(op->loc.cm_ptr[k]);
-            op->loc.cm_val[k] = nullptr; op->loc.cm_col[k] = op->loc.cm_dst[k] = nullptr; op->loc.cm_ptr[k] = nullptr;
-            op->loc.cm_ok[k] = false; op->loc.cm_tried[k] = 0;
-        }
-    if (bv != 14 && !keep) op->loc.free_sellp2();
-    if (bv != 17 && !keep) op->loc.free_vidx();                   // (the x-window tables go with the codes ...)
-    else if (!keep) op->loc.free_xwin(op->loc.vw_rows);           // (... or stay with them: the workgroup size in use only)
-    if ((bv == 14 || bv == 17) && !keep) {                        // k_sellp2 / k_vidx keep the pattern ids and the table; k_sell's / k_sellp's arrays go
-        CsrPart &L = op->loc;
-        L.free_sell_columns();
-        hipFree(L.sl_val); hipFree(L.sl_ptr); hipFree(L.sl_perm); L.sl_val = nullptr; L.sl_ptr = nullptr; L.sl_perm = nullptr;
-        L.sl_vals = false; L.sl_vals_tried = 0; L.sl_sorted = false;                       // (a later set_variant(11) re-orders the values again, from the device's CSR copy)
-    } else if (bv != 9 && bv != 11 && bv != 15 && !keep) op->loc.free_sell();        // (with the pattern ids, the table and k_vidx's codes)
-    else if ((bv == 11 || bv == 15) && !keep) op->loc.free_sell_columns();    // k_sellp / k_sellpx keep the values and the slice pointers only
-    else if (bv == 9 && !keep) op->loc.free_sellp();
-    if (bv != 15 && !keep) op->loc.free_sellpx();
-    if (!keep) { std::vector<int>().swap(op->loc.h_pstart); std::vector<int>().swap(op->loc.h_ptab); std::vector<unsigned short>().swap(op->loc.h_pat); }
-    if (bv != 13 && !keep) op->loc.free_rowt();
-    if (bv != 12 && !keep) op->loc.free_sellx();
-    if (bv != 10 && bv != 12 && bv != 16 && !keep) op->loc.free_xlds();
-    else if (bv == 12 && !keep) { hipFree(op->loc.xl_col); hipFree(op->loc.xl_tab); op->loc.xl_col = nullptr; op->loc.xl_tab = nullptr; }      // k_sellx keeps the chunk plan only
+    CsrPart &L = op->loc;
+    if (!plan_keeps(G_DENSE, bv, 0)) L.dn = {};
+    if (std::getenv("SAENA_KEEP_HOST_VALUES")) return;             // development sweeps switch variants after the autotune
+    auto drop = [&](int grp) { return !plan_keeps(grp, bv, L.vw_rows); };
+    for (int k = 0; k < 2; ++k) {                                  // (a plan whose build was refused keeps its `tried` mark)
+        if (L.cm[k].ok && drop(G_CM0 + k)) L.cm[k] = {};
+        if (L.cc[k].ok && drop(G_CC0 + k)) L.cc[k] = {};
+    }
+    if (drop(G_SELL_VALUES)) L.sv = {};                            // (a later set_variant(11) re-orders the values again, from the device's CSR copy)
+    if (drop(G_SELL_COLUMNS)) {
+        L.sc = {};
+        L.sl_ok = false;                                           // variant 9 is gone for good (sl_tried stays set) while a row-pattern form
+        if (drop(G_SELLP)) L.sl_tried = 0;                         // lives on; with the whole family gone it may be built again
+    }
+    if (drop(G_SELLP)) L.sp = {};
+    for (int k = 0; k < 3; ++k) if (drop(G_XWIN0 + k)) L.vw[k] = {};      // (variant 17 keeps the tables of the workgroup size in use only)
+    if (drop(G_VIDX)) { L.vi = {}; L.vw_rows = 0; }
+    if (drop(G_SELLP2)) L.sp2 = {};
+    if (drop(G_SELLPX)) L.spx = {};
+    if (drop(G_ROWT)) L.rt = {};
+    if (drop(G_SELLX)) L.sx = {};
+    if (drop(G_XLDS_PLAN)) L.xlp = {};
+    if (drop(G_XLDS_COLUMNS)) L.xlc = {};                          // (k_sellx keeps the chunk plan only: xl_ok stays, launch_part refuses 10 / 16 on the missing columns)
+    std::vector<int>().swap(L.h_pstart); std::vector<int>().swap(L.h_ptab); std::vector<unsigned short>().swap(L.h_pat);
     // the host copy of the values goes (the forms that still need it -- k_sellx, k_rowt -- are refused from here on).  Unmapping 4.5 GB
     // of resident host memory takes 0.25 s (the 558 M-entry level: most of what the autotune's log called "freeing"): a detached
     // thread does it, like the host setup's own large temporaries
-    if (!keep && !op->h_val_all.empty()) {
+    if (!op->h_val_all.empty()) {
         if (op->h_val_all.size() >= ((size_t)1 << 22) && !std::getenv("SAENA_NO_ASYNC_FREE")) {
             auto *junk = new std::vector<double>(std::move(op->h_val_all));
             try { std::thread([junk] { delete junk; }).detach(); } catch (...) { delete junk; }       // (no thread to be had: free it here)
         }
         std::vector<double>().swap(op->h_val_all);
     }
-    for (int k = 0; k < 2 && !keep; ++k)              // free the compressed arrays of the plans that lost
-        if (op->loc.cc_ok[k] && bv != 3 + k && bv != 7 + k) {
-            hipFree(op->loc.segtab[k]); hipFree(op->loc.segptr[k]); hipFree(op->loc.ccol[k]);
-            op->loc.segtab[k] = op->loc.segptr[k] = nullptr; op->loc.ccol[k] = nullptr; op->loc.cc_ok[k] = false; op->loc.cc_tried[k] = 0;
-        }
 }
 // does the form add a row's products one after the other in column order (the reference's sum, whatever else is tuned)?
 bool sequential_sum(int v, int lanes) { return v == 9 || v == 11 || v == 13 || v == 14 || v == 15 || v == 17 || (lanes == 1 && (v == 0 || v == 1 || v == 3 || v == 4 || v == 7 || v == 8)); }
@@ -2773,9 +2770,9 @@ int sgpu_op_autotune(sgpu_op *op) {
     const int g0 = auto_lanes(op->loc.nrows, op->loc.nblk);
     std::vector<int> lanes;
     for (int g : {g0 / 2, g0, g0 * 2}) if (g >= 1 && g <= 64) lanes.push_back(g);
-    DevBuf x, y, r;
-    CHK(x.alloc(op->N_local)); CHK(y.alloc(op->M)); CHK(r.alloc(op->M));
-    CHK(sgpu_vec_fill(x.p, 1.0, op->N_local)); CHK(sgpu_vec_fill(r.p, 1.0, op->M));
+    DevArr<double> x, y, r;
+    CHK(dev_alloc(x, op->N_local)); CHK(dev_alloc(y, op->M)); CHK(dev_alloc(r, op->M));
+    CHK(sgpu_vec_fill(x, 1.0, op->N_local)); CHK(sgpu_vec_fill(r, 1.0, op->M));
     const int kind = op->inv_diag ? 1 : 0;
     const double avg_row = (double)op->loc.nnz / std::max(1, op->loc.nrows);
     const bool all = std::getenv("SAENA_AUTOTUNE_ALL") != nullptr;     // every form that applies, as before round 3 (development)
@@ -2787,19 +2784,19 @@ int sgpu_op_autotune(sgpu_op *op) {
     bool sell_like = false;
     if (!std::getenv("SAENA_NO_SELL") && (all || avg_row <= 160.0)) {                                 // even rows: a lane per row
         CHK(build_sell_values(op->loc));                                                             // (on the device, from the CSR values: round 4)
-        if (op->loc.sl_vals) {
+        if (op->loc.sv.sl_vals) {
             if (!std::getenv("SAENA_NO_SELLP")) {                                                    // rows that repeat a few patterns: no column stream
                 CHK(build_sellp(op->loc));
-                if (op->loc.sp_ok) variants.push_back(11);
+                if (op->loc.sp.sp_ok) variants.push_back(11);
                 // ... and the values as 8-bit codes into a dictionary per workgroup (operators of at most VI_MAX distinct values per
                 // 256 rows: the constant-coefficient stencil levels and their transfers): 1 B per entry instead of 8.  Offered where the
                 // values are more than the eight XCDs' L2 (32 MiB) hold from one launch to the next -- the bytes it saves come from the
                 // Infinity Cache or HBM; below that it was not measured and the plan stays as it was (128^3 fine level: 111 MB)
-                if (op->loc.sp_ok && !op->loc.sp_wide && 8 * op->loc.nnz > ((int64_t)32 << 20) && !std::getenv("SAENA_NO_VALUE_INDEX")) {
+                if (op->loc.sp.sp_ok && !op->loc.sp.sp_wide && 8 * op->loc.nnz > ((int64_t)32 << 20) && !std::getenv("SAENA_NO_VALUE_INDEX")) {
                     CHK(build_vidx(op->loc));
-                    if (op->loc.vi_ok) variants.push_back(17);
+                    if (op->loc.vi.vi_ok) variants.push_back(17);
                     // ... and the same form with x in LDS windows (k_vidxw), a candidate of its own per workgroup size kept
-                    if (op->loc.vi_ok && !std::getenv("SAENA_NO_X_WINDOWS"))
+                    if (op->loc.vi.vi_ok && !std::getenv("SAENA_NO_X_WINDOWS"))
                         for (int k : XWIN_CANDIDATES) { CHK(build_xwin(op->loc, k)); if (op->loc.vw[k].ok) xwin_rows.push_back(256 << k); }
                 }
                 // ... and a lane per two rows: half the gathers.  With a table per workgroup (sp_wide: the 68-entry level) it wins on the
@@ -2807,27 +2804,27 @@ int sgpu_op_autotune(sgpu_op *op) {
                 // copy is 4.5 GB: tried up to 1 GB (profiles/r03_sellp_pergroup_tables.log).  (Round 4: the device makes the copy in
                 // milliseconds, but allocating and FREEING 4.5 GB costs 0.2 s of the plan and the form lost again on 256^3 -- 942 against
                 // k_sellpx's 888 us: the limit stays)
-                if (op->loc.sp_ok && (!op->loc.sp_wide || op->loc.sp_bytes <= ((int64_t)1 << 30)) && !std::getenv("SAENA_NO_SELLP2")) {
+                if (op->loc.sp.sp_ok && (!op->loc.sp.sp_wide || op->loc.sp_bytes <= ((int64_t)1 << 30)) && !std::getenv("SAENA_NO_SELLP2")) {
                     CHK(build_sellp2(op->loc, op->h_val_all));
-                    if (op->loc.sp2_ok) variants.push_back(14);
+                    if (op->loc.sp2.sp2_ok) variants.push_back(14);
                 }
-                if (op->loc.sp_ok && avg_row >= 16.0 && !std::getenv("SAENA_NO_SELLPX")) {                 // ... with x in LDS windows: where a row gathers dozens of entries
+                if (op->loc.sp.sp_ok && avg_row >= 16.0 && !std::getenv("SAENA_NO_SELLPX")) {                 // ... with x in LDS windows: where a row gathers dozens of entries
                     CHK(build_sellpx(op->loc));
-                    if (op->loc.spx_ok) variants.push_back(15);
+                    if (op->loc.spx.spx_ok) variants.push_back(15);
                 }
-                if (op->loc.sp_ok && std::getenv("SAENA_ROW_TEMPLATES") && !op->h_val_all.empty()) {     // OPT-IN: rows that also repeat their values
+                if (op->loc.sp.sp_ok && std::getenv("SAENA_ROW_TEMPLATES") && !op->h_val_all.empty()) {     // OPT-IN: rows that also repeat their values
                     CHK(build_rowt(op->loc, op->h_val_all));
-                    if (op->loc.rt_ok) variants.push_back(13);
+                    if (op->loc.rt.rt_ok) variants.push_back(13);
                 }
             }
             // k_sell itself (10 B per entry: the same values + 16-bit column codes, which cost a host pass over the entries and 2 B per
             // entry of upload) only where the rows follow no patterns -- it never beat k_sellp on an operator that has them (8 B per
             // entry, the same structure: 128^3 level 1 137.8 against 119.3 us, profiles/r03_sellp_wide_l1_128.log)
-            if (!op->loc.sp_ok || op->loc.sp_rbase || all) {             // (... and next to a rowbase table: the 4 B per row it adds are a fifth of what the codes cost on 6-entry rows)
+            if (!op->loc.sp.sp_ok || op->loc.sp.sp_rbase || all) {             // (... and next to a rowbase table: the 4 B per row it adds are a fifth of what the codes cost on 6-entry rows)
                 CHK(build_sell(op->loc, op->h_val_all));
                 if (op->loc.sl_ok) variants.push_back(9);
             }
-            sell_like = op->loc.sp_ok || (op->loc.sl_ok && !op->loc.sl_sorted);         // (sorted slices: one more candidate next to the tile kernels)
+            sell_like = op->loc.sp.sp_ok || (op->loc.sl_ok && !op->loc.sv.sl_sorted);         // (sorted slices: one more candidate next to the tile kernels)
         }
     }
     const double t_sell = now_s();
@@ -2835,16 +2832,16 @@ int sgpu_op_autotune(sgpu_op *op) {
     for (int k = 0; k < 2; ++k) {
         // (round 4) an operator whose rows follow patterns runs at 8 B per entry; the tile kernels' 10 B per entry never came within 15 % of
         // it (256^3 L0 343 against 277 us, L1 1 190-1 270 against 890): not built, not timed, not freed
-        if (op->loc.sp_ok && !all) continue;
+        if (op->loc.sp.sp_ok && !all) continue;
         if (k == 1 && (short_rows || avg_row < 16.0) && !all) continue;                              // 32 KiB tiles never won on the shortest rows (at 18 entries per
                                                                                                      // row -- P1 of 256^3 -- they do: 361 against 385 us, profiles/r03_transfers_sell_padding.log)
         CHK(build_cc16(op->loc, k));
-        if (op->loc.cc_ok[k]) variants.push_back(3 + k);
+        if (op->loc.cc[k].ok) variants.push_back(3 + k);
     }
     const double t_cc = now_s();
     if (!short_rows) {
-        if (!op->loc.cc_ok[0] || avg_row >= 256.0 || all) variants.push_back(0);                     // 32-bit columns: where 16-bit ones do not apply, and on long rows
-        if (!op->loc.cc_ok[1] || avg_row >= 256.0 || all) variants.push_back(1);
+        if (!op->loc.cc[0].ok || avg_row >= 256.0 || all) variants.push_back(0);                     // 32-bit columns: where 16-bit ones do not apply, and on long rows
+        if (!op->loc.cc[1].ok || avg_row >= 256.0 || all) variants.push_back(1);
     }
     variants.push_back(2);                                                                           // vector CSR: no build
     if (op->loc.nnz >= 256 * (int64_t)std::max(1, op->loc.nrows)) variants.push_back(6);             // long rows: the wave-streamed kernel
@@ -2854,14 +2851,14 @@ int sgpu_op_autotune(sgpu_op *op) {
     const bool irregular_short = !sell_like && avg_row >= 12.0;
     if ((op->loc.nnz >= 48 * (int64_t)std::max(1, op->loc.nrows) || irregular_short) && !std::getenv("SAENA_NO_XLDS") && (!short_rows)) {
         CHK(build_xlds(op->loc));
-        if (op->loc.xl_ok && op->loc.xl_piece >= 24.0) variants.push_back(10);
-        if (op->loc.xl_ok && op->loc.xl_piece >= 8.0 && op->loc.xl_piece < 160.0 && !std::getenv("SAENA_NO_XLDSR")) variants.push_back(16);   // short pieces: four rows per group step
+        if (op->loc.xlp.xl_ok && op->loc.xl_piece >= 24.0) variants.push_back(10);
+        if (op->loc.xlp.xl_ok && op->loc.xl_piece >= 8.0 && op->loc.xl_piece < 160.0 && !std::getenv("SAENA_NO_XLDSR")) variants.push_back(16);   // short pieces: four rows per group step
     }
     // (on the transfers it does not pay: P1 of 256^3, 18 entries per row, 504 us against 350; P2 ties; R2 165 against 156 us,
     //  profiles/r03_sellx_steps.log)
-    if (op->loc.xl_ok && !op->h_val_all.empty() && avg_row >= 96.0 && avg_row <= 1024.0 && !std::getenv("SAENA_NO_SELLX")) {
+    if (op->loc.xlp.xl_ok && !op->h_val_all.empty() && avg_row >= 96.0 && avg_row <= 1024.0 && !std::getenv("SAENA_NO_SELLX")) {
         CHK(build_sellx(op->loc, op->h_val_all));                                                    // a few hundred entries per row: a lane per row piece, x in LDS
-        if (op->loc.sx_ok) variants.push_back(12);
+        if (op->loc.sx.sx_ok) variants.push_back(12);
     }
     const double t_xl = now_s();
     // (k_csr_cm, 12 B per entry, is built further down -- only where the candidates timed so far leave it a chance)
@@ -2870,7 +2867,7 @@ int sgpu_op_autotune(sgpu_op *op) {
         variants.push_back(5);                         // at least half full: the dense form moves fewer bytes
     // Only the LOCAL part is timed, without the halo exchange: ranks may end up with different candidate
     // lists (a rank's blocks may be too scattered for 16-bit columns), so no collective may run in here.
-    EpiArgs e; e.rhs = r.p; e.inv_diag = op->inv_diag; e.u = x.p; e.c0 = JACOBI_OMEGA_REF;
+    EpiArgs e; e.rhs = r; e.inv_diag = op->inv_diag; e.u = x; e.c0 = JACOBI_OMEGA_REF;
     const int epi = kind == 1 ? sk::EPI_JACOBI : sk::EPI_SPMV;
     ++g_plan_generation;                                 // frees/replaces buffers captured graphs may reference
     struct Guard {                                       // an error return inside the sweep leaves the operator as it was
@@ -2897,7 +2894,7 @@ int sgpu_op_autotune(sgpu_op *op) {
         float ms = 0;
         for (int burst = 0; burst < 8 && ms < 2.0f; ++burst) {
             HIPCHK(hipEventRecord(e0, g.cs));
-            for (int i = 0; i < 8; ++i) CHK(launch_part(op->loc, epi, x.p, y.p, e));
+            for (int i = 0; i < 8; ++i) CHK(launch_part(op->loc, epi, x, y, e));
             HIPCHK(hipEventRecord(e1, g.cs));
             HIPCHK(hipEventSynchronize(e1));
             float t = 0;
@@ -2908,7 +2905,7 @@ int sgpu_op_autotune(sgpu_op *op) {
     auto sample = [&](int v, int gl, int reps, float *ms) -> int {
         op->loc.variant = v; op->loc.lanes = gl >= 256 ? lanes.front() : gl; op->loc.vw_rows = gl >= 256 ? gl : 0;
         HIPCHK(hipEventRecord(e0, g.cs));
-        for (int i = 0; i < reps; ++i) CHK(launch_part(op->loc, epi, x.p, y.p, e));
+        for (int i = 0; i < reps; ++i) CHK(launch_part(op->loc, epi, x, y, e));
         HIPCHK(hipEventRecord(e1, g.cs));
         HIPCHK(hipEventSynchronize(e1));
         HIPCHK(hipEventElapsedTime(ms, e0, e1));
@@ -2929,7 +2926,7 @@ int sgpu_op_autotune(sgpu_op *op) {
     if (avg_row >= 96.0 && avg_row <= 768.0 && !std::getenv("SAENA_NO_CM") &&
         (all || (double)best_est > 12.0 * (double)op->loc.nnz / 5.2e9)) {
         CHK(build_cm(op->loc, 1, op->h_val_all));
-        if (op->loc.cm_ok[1])
+        if (op->loc.cm[1].ok)
             for (int gl : lanes) {
                 const std::pair<int, int> c{8, gl};
                 float ms = 0;
@@ -3031,7 +3028,7 @@ int sgpu_residual_negative(sgpu_op *op, const value_t *u, const value_t *rhs, va
     CHK(need_ctx());
     if (!op || !u || !rhs || !res) return fail(SGPU_ERR_ARG, "null argument");
     if (!op->ones && op->M > 0) {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&op->ones), (size_t)op->M * sizeof(double)));
+        HIPCHK(op->ones.alloc((size_t)op->M));
         CHK(sgpu_vec_fill(op->ones, 1.0, (size_t)op->M));
     }
     return sgpu_residual_multiply(op, u, rhs, res, op->ones, 1.0);      // 1 * 1 * (rhs - A u): exact, signs of zeros included
@@ -3084,7 +3081,7 @@ int sgpu_debug_gather_probe(sgpu_op *op, int mode, const value_t *x, int reps, f
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     HIPCHK(hipEventRecord(e0, g.cs));
     for (int i = 0; i < reps; ++i)
-        SGPU_LAUNCH(sk::k_gather_probe, dim3(grid), dim3(sk::BLOCK), 0, g.cs, op->loc.col, x, g.dscalar, nnz, mode);
+        SGPU_LAUNCH(sk::k_gather_probe, dim3(grid), dim3(sk::BLOCK), 0, g.cs, op->loc.csr.col, x, g.dscalar, nnz, mode);
     HIPCHK(hipEventRecord(e1, g.cs));
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(ms, e0, e1));
@@ -3116,10 +3113,11 @@ int sgpu_debug_stream_ceiling(size_t read_bytes, size_t write_bytes, int reps, f
     const size_t n_w = write_bytes / 8;
     const int q = (int)std::max<size_t>(1, (read_bytes + 8 * n_w) / (16 * n_w));       // 16-byte loads per written double, rounded
     const size_t waves = (n_w + 63) / 64, n_r = waves * 64 * (size_t)q;                // (whole waves: every lane of the last wave has its run)
-    void *rd = nullptr; double *wr = nullptr;
-    HIPCHK(hipMalloc(&rd, n_r * 16));
-    if (hipMalloc(reinterpret_cast<void **>(&wr), n_w * 8) != hipSuccess) { hipFree(rd); return fail(SGPU_ERR_HIP, "hipMalloc of the ceiling's output failed"); }
-    struct Free { void *a, *b; hipEvent_t e0 = nullptr, e1 = nullptr; ~Free() { hipFree(a); hipFree(b); if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); } } fr{rd, wr};
+    DevArr<char> rd_; DevArr<double> wr_;
+    HIPCHK(rd_.alloc(n_r * 16));
+    if (wr_.alloc(n_w) != hipSuccess) return fail(SGPU_ERR_HIP, "hipMalloc of the ceiling's output failed");
+    void *rd = rd_.get(); double *wr = wr_;
+    struct Free { hipEvent_t e0 = nullptr, e1 = nullptr; ~Free() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); } } fr;
     HIPCHK(hipMemsetAsync(rd, 0, n_r * 16, g.cs));
     HIPCHK(hipEventCreate(&fr.e0)); HIPCHK(hipEventCreate(&fr.e1));
     const dim3 grid((unsigned)((n_w + sk::BLOCK - 1) / sk::BLOCK)), block(sk::BLOCK);
@@ -3165,105 +3163,89 @@ int sgpu_debug_inject_halo(sgpu_op *op, const value_t *recv_host) {
 int sgpu_spmv_host(sgpu_op *op, const value_t *v_host, value_t *w_host) {
     CHK(need_ctx());
     if (!op || !v_host || !w_host) return fail(SGPU_ERR_ARG, "null argument");
-    DevBuf v, w;
-    CHK(v.alloc(op->N_local)); CHK(w.alloc(op->M));
-    CHK(sgpu_vec_upload(v.p, v_host, op->N_local));
-    CHK(sgpu_spmv(op, v.p, w.p));
-    return sgpu_vec_download(w_host, w.p, op->M);
+    DevArr<double> v, w;
+    CHK(dev_alloc(v, op->N_local)); CHK(dev_alloc(w, op->M));
+    CHK(sgpu_vec_upload(v, v_host, op->N_local));
+    CHK(sgpu_spmv(op, v, w));
+    return sgpu_vec_download(w_host, w, op->M);
 }
 int sgpu_jacobi_host(sgpu_op *op, int iter, value_t omega, value_t *u_host, const value_t *rhs_host) {
     CHK(need_ctx());
     if (!op || !u_host || !rhs_host) return fail(SGPU_ERR_ARG, "null argument");
-    DevBuf u, r;
-    CHK(u.alloc(op->M)); CHK(r.alloc(op->M));
-    CHK(sgpu_vec_upload(u.p, u_host, op->M)); CHK(sgpu_vec_upload(r.p, rhs_host, op->M));
-    CHK(sgpu_jacobi(op, iter, omega, u.p, r.p));
-    return sgpu_vec_download(u_host, u.p, op->M);
+    DevArr<double> u, r;
+    CHK(dev_alloc(u, op->M)); CHK(dev_alloc(r, op->M));
+    CHK(sgpu_vec_upload(u, u_host, op->M)); CHK(sgpu_vec_upload(r, rhs_host, op->M));
+    CHK(sgpu_jacobi(op, iter, omega, u, r));
+    return sgpu_vec_download(u_host, u, op->M);
 }
 int sgpu_chebyshev_host(sgpu_op *op, int iter, value_t eig_max, value_t *u_host, const value_t *rhs_host) {
     CHK(need_ctx());
     if (!op || !u_host || !rhs_host) return fail(SGPU_ERR_ARG, "null argument");
-    DevBuf u, r;
-    CHK(u.alloc(op->M)); CHK(r.alloc(op->M));
-    CHK(sgpu_vec_upload(u.p, u_host, op->M)); CHK(sgpu_vec_upload(r.p, rhs_host, op->M));
-    CHK(sgpu_chebyshev(op, iter, eig_max, u.p, r.p));
-    return sgpu_vec_download(u_host, u.p, op->M);
+    DevArr<double> u, r;
+    CHK(dev_alloc(u, op->M)); CHK(dev_alloc(r, op->M));
+    CHK(sgpu_vec_upload(u, u_host, op->M)); CHK(sgpu_vec_upload(r, rhs_host, op->M));
+    CHK(sgpu_chebyshev(op, iter, eig_max, u, r));
+    return sgpu_vec_download(u_host, u, op->M);
 }
 
 } // extern "C"
 
 // ===========================================================================
 // multigrid
+// a captured graph and its executable instance, destroyed together
+struct CapturedGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    CapturedGraph() = default;
+    CapturedGraph(CapturedGraph &&o) noexcept : graph(o.graph), exec(o.exec) { o.graph = nullptr; o.exec = nullptr; }
+    CapturedGraph &operator=(CapturedGraph &&o) noexcept {
+        if (this != &o) { drop_graph(); graph = o.graph; exec = o.exec; o.graph = nullptr; o.exec = nullptr; }
+        return *this;
+    }
+    ~CapturedGraph() { drop_graph(); }
+    void drop_graph() {
+        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
+        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
+    }
+};
+// a captured V-cycle and the (u, rhs) pointer pair it was captured on
+struct CapturedCycle : CapturedGraph { double *u = nullptr; const double *rhs = nullptr; bool u_zero = false; };
+
 // block V-cycle / pCG state of a hierarchy for ONE K (sgpu_block.hip.inc): made at the first block call with that K
 struct AmgBlock {
     int K = 0;
-    std::vector<double *> res, rhs, u, alt;   // block work vectors per level, as sgpu_amg's scalar ones
-    double *alt0 = nullptr, *r = nullptr, *rho = nullptr, *hh = nullptr, *p = nullptr;
-    double *cm = nullptr;                     // coarsest CG: the K columns unpacked (rhs, then u), 2 * n * K
-    double *S = nullptr, *partials = nullptr; // device scalars [8][K]; dot partial sums [n_partials][K]
-    double *hS = nullptr;                     // pinned mirror of one row of S
-    struct Captured { double *u; const double *rhs; bool u_zero; hipGraph_t graph; hipGraphExec_t exec; };
-    std::vector<Captured> graphs;
+    std::vector<DevArr<double>> res, rhs, u, alt;   // block work vectors per level, as sgpu_amg's scalar ones
+    DevArr<double> alt0, r, rho, hh, p;
+    DevArr<double> cm;                        // coarsest CG: the K columns unpacked (rhs, then u), 2 * n * K
+    DevArr<double> S, partials;               // device scalars [8][K]; dot partial sums [n_partials][K]
+    PinArr<double> hS;                        // pinned mirror of one row of S
+    std::vector<CapturedCycle> graphs;
     uint64_t graph_gen = 0, block_gen = 0;
-    void drop_graphs() {
-        for (auto &c : graphs) { hipGraphExecDestroy(c.exec); hipGraphDestroy(c.graph); }
-        graphs.clear();
-    }
-    ~AmgBlock() {
-        drop_graphs();
-        for (auto q : res) hipFree(q);
-        for (auto q : rhs) hipFree(q);
-        for (auto q : u) hipFree(q);
-        for (auto q : alt) hipFree(q);
-        hipFree(alt0); hipFree(r); hipFree(rho); hipFree(hh); hipFree(p); hipFree(cm); hipFree(S); hipFree(partials);
-        if (hS) hipHostFree(hS);
-    }
+    void drop_graphs() { graphs.clear(); }
 };
 
-// restarted FGMRES state of a hierarchy (sgpu_gmres.hip.inc): made at the first sgpu_solve_FGMRES with a given restart length
-struct AmgGmres {
+// restarted FGMRES state of a hierarchy (sgpu_gmres.hip.inc): made at the first sgpu_solve_FGMRES with a given restart length;
+// its graph: the V-cycle on (pout, pin) from a zero iterate, captured once
+struct AmgGmres : CapturedGraph {
     int restart = 0;
     size_t ld = 0;                                   // leading dimension of V and Z: the rows rounded up to an even number
-    double *V = nullptr, *Z = nullptr;               // Krylov basis (restart + 1 columns), preconditioned vectors (restart columns)
-    double *pin = nullptr, *pout = nullptr;          // the fixed pair the V-cycle preconditions through
-    double *coef = nullptr, *partials = nullptr;     // device coefficients (two Gram-Schmidt sets and ||w||^2); the dots' partial sums
-    double *hcoef = nullptr;                         // pinned mirror of coef
-    hipGraph_t graph = nullptr;                      // the V-cycle on (pout, pin) from a zero iterate, captured once
-    hipGraphExec_t exec = nullptr;
+    DevArr<double> V, Z;                             // Krylov basis (restart + 1 columns), preconditioned vectors (restart columns)
+    DevArr<double> pin, pout;                        // the fixed pair the V-cycle preconditions through
+    DevArr<double> coef, partials;                   // device coefficients (two Gram-Schmidt sets and ||w||^2); the dots' partial sums
+    PinArr<double> hcoef;                            // pinned mirror of coef
     uint64_t graph_gen = 0;
-    void drop_graph() {
-        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
-        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
-    }
-    ~AmgGmres() {
-        drop_graph();
-        hipFree(V); hipFree(Z); hipFree(pin); hipFree(pout); hipFree(coef); hipFree(partials);
-        if (hcoef) hipHostFree(hcoef);
-    }
 };
 
-// LOBPCG state of a hierarchy for ONE K (sgpu_eig.hip.inc): made at the first sgpu_eigs_LOBPCG with that K
-struct AmgEig {
+// LOBPCG state of a hierarchy for ONE K (sgpu_eig.hip.inc): made at the first sgpu_eigs_LOBPCG with that K; its graph: the block
+// V-cycle on (W, R) from a zero iterate, captured once
+struct AmgEig : CapturedGraph {
     int K = 0;
-    double *AX = nullptr, *R = nullptr, *W = nullptr, *AW = nullptr, *P = nullptr, *AP = nullptr;   // block vectors (X is the caller's)
-    double *gpart = nullptr, *rpart = nullptr;       // partial sums: 12 Gram blocks [n_partials][K*K] each; the residual norms [n_partials][K]
-    double *coef = nullptr;                          // device: 3 K*K mix coefficients | K lambda | K ||r_j||^2 | 12 Gram blocks of K*K
-    double *hmix = nullptr, *hlam = nullptr, *hdown = nullptr;   // pinned: what goes up (coefficients, lambda), what comes down (norms, Gram blocks)
-    hipGraph_t graph = nullptr;                      // the block V-cycle on (W, R) from a zero iterate, captured once
-    hipGraphExec_t exec = nullptr;
+    DevArr<double> AX, R, W, AW, P, AP;              // block vectors (X is the caller's)
+    DevArr<double> gpart, rpart;                     // partial sums: 12 Gram blocks [n_partials][K*K] each; the residual norms [n_partials][K]
+    DevArr<double> coef;                             // device: 3 K*K mix coefficients | K lambda | K ||r_j||^2 | 12 Gram blocks of K*K
+    PinArr<double> hmix, hlam, hdown;                // pinned: what goes up (coefficients, lambda), what comes down (norms, Gram blocks)
     uint64_t graph_gen = 0, block_gen = 0;
     int debug_stop = -1;                             // sgpu_debug_eig_stop: the iteration a test wants to look into
-    void drop_graph() {
-        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
-        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
-    }
-    ~AmgEig() {
-        drop_graph();
-        hipFree(AX); hipFree(R); hipFree(W); hipFree(AW); hipFree(P); hipFree(AP); hipFree(gpart); hipFree(rpart); hipFree(coef);
-        if (hmix) hipHostFree(hmix);
-        if (hlam) hipHostFree(hlam);
-        if (hdown) hipHostFree(hdown);
-    }
 };
 
 struct sgpu_amg {
@@ -3272,31 +3254,21 @@ struct sgpu_amg {
     std::vector<double> eig;
     sgpu_amg_params prm;
     // per level l < nlevels-1: res[l] (A[l].M); per level l >= 1: rhs_l / u_l / alt_l (A[l].M)
-    std::vector<double *> res, rhs, u, alt;
-    double *alt0 = nullptr;   // ping-pong partner of the caller's level-0 u
+    std::vector<DevArr<double>> res, rhs, u, alt;
+    DevArr<double> alt0;      // ping-pong partner of the caller's level-0 u
     // solve work vectors (level 0)
-    double *r = nullptr, *rho = nullptr, *hh = nullptr, *p = nullptr;
+    DevArr<double> r, rho, hh, p;
+    DevArr<double> Ainv;      // dense inverse of the coarsest operator (coarse_solver == 1)
+    bool coarse_local = true; // the coarsest operator has no halo on any rank
     // captured V-cycles, one per (u, rhs) pointer pair (single rank): replaying a hipGraph removes
     // the ~70 launch gaps of a V-cycle, which weigh as much as a whole coarse level
-    struct Captured { double *u; const double *rhs; bool u_zero; hipGraph_t graph; hipGraphExec_t exec; };
-    double *Ainv = nullptr;   // dense inverse of the coarsest operator (coarse_solver == 1)
-    bool coarse_local = true; // the coarsest operator has no halo on any rank
-    ~sgpu_amg() {
-        for (auto p_ : res) hipFree(p_);
-        for (auto p_ : rhs) hipFree(p_);
-        for (auto p_ : u) hipFree(p_);
-        for (auto p_ : alt) hipFree(p_);
-        drop_graphs();
-        hipFree(Ainv); hipFree(alt0); hipFree(r); hipFree(rho); hipFree(hh); hipFree(p);
-    }
-    std::vector<Captured> graphs;
+    std::vector<CapturedCycle> graphs;
     // Multi-rank: the levels agglomerated onto this rank (no operator with a halo from level `tail_level` down) form a
     // sub-V-cycle without any communication; it is captured once and replayed as ONE graph launch per V-cycle instead
     // of ~8 launches per level.  Ranks that own no rows of those levels launch nothing at all for them.
     int  tail_level = -1;
     bool tail_capturing = false;
-    hipGraph_t tail_graph = nullptr;
-    hipGraphExec_t tail_exec = nullptr;
+    CapturedGraph tail;
     double *tail_out = nullptr;        // which of u[tail_level] / alt[tail_level] holds the sub-V-cycle's result
     uint64_t graph_gen = 0;            // g_plan_generation the graphs were captured under
     bool coarse_host_driven = false;   // coarsest level too large for the LDS-resident solvers: host-driven CG, no graph capture
@@ -3307,10 +3279,8 @@ struct sgpu_amg {
         for (auto &b : blk) if (b) b->drop_graphs();
         if (gm) gm->drop_graph();
         for (auto &e : eigs) if (e) e->drop_graph();
-        for (auto &c : graphs) { hipGraphExecDestroy(c.exec); hipGraphDestroy(c.graph); }
         graphs.clear();
-        if (tail_exec) { hipGraphExecDestroy(tail_exec); tail_exec = nullptr; }
-        if (tail_graph) { hipGraphDestroy(tail_graph); tail_graph = nullptr; }
+        tail.drop_graph();
     }
 };
 
@@ -3319,7 +3289,7 @@ namespace {
 int coarse_cg_single(sgpu_amg *h, sgpu_op *A, double *u, const double *rhs, int *iters) {
     if (A->M > sk::CG_MAXN) return fail(SGPU_ERR_ARG, "coarsest level has %d rows; the LDS-resident CG supports <= %d", A->M, sk::CG_MAXN);
     sk::CoarseCGArgs a;
-    a.row_ptr = A->loc.row_ptr; a.col = A->loc.col; a.val = A->loc.val; a.n = A->M;
+    a.row_ptr = A->loc.csr.row_ptr; a.col = A->loc.csr.col; a.val = A->loc.csr.val; a.n = A->M;
     a.rhs = rhs; a.u = u; a.max_iter = h->prm.CG_coarsest_max_iter; a.tol = h->prm.CG_coarsest_tol;
     a.iters_out = iters ? g.dint + 1 : nullptr;
     SGPU_LAUNCH(sk::k_coarse_cg, dim3(1), dim3(sk::CG_BLOCK), 0, g.cs, a);
@@ -3336,28 +3306,28 @@ int coarse_cg_single(sgpu_amg *h, sgpu_op *A, double *u, const double *rhs, int 
 // over the distributed kernels (src/saena_object_solve.cpp:14-114).
 int coarse_cg_dist(sgpu_amg *h, sgpu_op *A, double *u, const double *rhs, int *iters) {
     const size_t n = (size_t)A->M;
-    DevBuf res, dir, mt;
-    CHK(res.alloc(n)); CHK(dir.alloc(n)); CHK(mt.alloc(n));
-    CHK(sgpu_vec_copy(res.p, rhs, n)); CHK(sgpu_vec_copy(dir.p, rhs, n));
+    DevArr<double> res, dir, mt;
+    CHK(dev_alloc(res, n)); CHK(dev_alloc(dir, n)); CHK(dev_alloc(mt, n));
+    CHK(sgpu_vec_copy(res, rhs, n)); CHK(sgpu_vec_copy(dir, rhs, n));
     const double tol = h->prm.CG_coarsest_tol;
     double initial_dot = 0, dot = 0, factor = 0, dot_prev = 0;
-    CHK(sgpu_dot(res.p, res.p, n, &initial_dot));
+    CHK(sgpu_dot(res, res, n, &initial_dot));
     const double thres = initial_dot * tol * tol;
     dot = initial_dot;
     int max_iter = h->prm.CG_coarsest_max_iter;
     if (dot < tol * tol) max_iter = 0;
     int i = 1;
     while (i < max_iter) {
-        CHK(sgpu_spmv(A, dir.p, mt.p));
-        CHK(sgpu_dot(dir.p, mt.p, n, &factor));
+        CHK(sgpu_spmv(A, dir, mt));
+        CHK(sgpu_dot(dir, mt, n, &factor));
         factor = dot / factor;
-        CHK(sgpu_vec_axpby(factor, dir.p, 1.0, u, n));
-        CHK(sgpu_vec_axpby(-factor, mt.p, 1.0, res.p, n));
+        CHK(sgpu_vec_axpby(factor, dir, 1.0, u, n));
+        CHK(sgpu_vec_axpby(-factor, mt, 1.0, res, n));
         dot_prev = dot;
-        CHK(sgpu_dot(res.p, res.p, n, &dot));
+        CHK(sgpu_dot(res, res, n, &dot));
         if (dot < thres) break;
         factor = dot / dot_prev;
-        CHK(sgpu_vec_axpby(1.0, res.p, factor, dir.p, n));
+        CHK(sgpu_vec_axpby(1.0, res, factor, dir, n));
         i++;
     }
     if (i == max_iter && max_iter != 0) i--;
@@ -3401,16 +3371,16 @@ int vcycle_level(sgpu_amg *h, int l, double *u, double *alt, const double *rhs, 
 // the communication-free sub-V-cycle from `tail_level` down as one graph launch (captured at its first use)
 int tail_run(sgpu_amg *h, double **out) {
     const int l = h->tail_level;
-    if (h->tail_exec && h->graph_gen != g_plan_generation) { HIPCHK(hipStreamSynchronize(g.cs)); h->drop_graphs(); }
-    if (!h->tail_exec) {
+    if (h->tail.exec && h->graph_gen != g_plan_generation) { HIPCHK(hipStreamSynchronize(g.cs)); h->drop_graphs(); }
+    if (!h->tail.exec) {
         h->graph_gen = g_plan_generation;
         h->tail_capturing = true;
         hipError_t e = hipStreamBeginCapture(g.cs, hipStreamCaptureModeThreadLocal);
         int st = SGPU_OK;
         if (e == hipSuccess) {
             st = vcycle_level(h, l, h->u[l], h->alt[l], h->rhs[l], &h->tail_out, true);
-            e = hipStreamEndCapture(g.cs, &h->tail_graph);
-            if (e == hipSuccess && st == SGPU_OK) e = hipGraphInstantiate(&h->tail_exec, h->tail_graph, nullptr, nullptr, 0);
+            e = hipStreamEndCapture(g.cs, &h->tail.graph);
+            if (e == hipSuccess && st == SGPU_OK) e = hipGraphInstantiate(&h->tail.exec, h->tail.graph, nullptr, nullptr, 0);
         }
         h->tail_capturing = false;
         if (e != hipSuccess || st != SGPU_OK) {          // not capturable here: run these levels eagerly from now on
@@ -3421,7 +3391,7 @@ int tail_run(sgpu_amg *h, double **out) {
         }
     }
     ++g_launches;
-    HIPCHK(hipGraphLaunch(h->tail_exec, g.cs));
+    HIPCHK(hipGraphLaunch(h->tail.exec, g.cs));
     *out = h->tail_out;
     return SGPU_OK;
 }
@@ -3495,19 +3465,17 @@ int vcycle0(sgpu_amg *h, double *u, const double *rhs, bool u_zero = false) {
     h->graph_gen = g_plan_generation;
     for (auto &c : h->graphs)
         if (c.u == u && c.rhs == rhs && c.u_zero == u_zero) { ++g_launches; HIPCHK(hipGraphLaunch(c.exec, g.cs)); return SGPU_OK; }
-    sgpu_amg::Captured c{u, rhs, u_zero, nullptr, nullptr};
+    CapturedCycle c;
+    c.u = u; c.rhs = rhs; c.u_zero = u_zero;
     HIPCHK(hipStreamBeginCapture(g.cs, hipStreamCaptureModeThreadLocal));
     const int st = vcycle0_eager(h, u, rhs, u_zero);
     const hipError_t e = hipStreamEndCapture(g.cs, &c.graph);
-    if (st != SGPU_OK) { if (c.graph) hipGraphDestroy(c.graph); return st; }
+    if (st != SGPU_OK) return st;
     if (e != hipSuccess) return fail(SGPU_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
     HIPCHK(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
-    if (h->graphs.size() >= 8) {                  // bounded cache
-        hipGraphExecDestroy(h->graphs.front().exec); hipGraphDestroy(h->graphs.front().graph);
-        h->graphs.erase(h->graphs.begin());
-    }
-    h->graphs.push_back(c);
-    ++g_launches; HIPCHK(hipGraphLaunch(c.exec, g.cs));
+    if (h->graphs.size() >= 8) h->graphs.erase(h->graphs.begin());                  // bounded cache
+    h->graphs.push_back(std::move(c));
+    ++g_launches; HIPCHK(hipGraphLaunch(h->graphs.back().exec, g.cs));
     return SGPU_OK;
 }
 
@@ -3545,12 +3513,11 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
             if (h->prm.smoother == 1 && !(h->eig[l] > 0.0)) return fail(SGPU_ERR_ARG, "chebyshev needs eig_max[%d] > 0", l);
         }
     }
-    h->res.assign(nlevels, nullptr); h->rhs.assign(nlevels, nullptr); h->u.assign(nlevels, nullptr); h->alt.assign(nlevels, nullptr);
-    auto alloc = [](double **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(1, n) * sizeof(double)); };
+    h->res.resize(nlevels); h->rhs.resize(nlevels); h->u.resize(nlevels); h->alt.resize(nlevels);
     for (int l = 0; l < nlevels; ++l) {
         const size_t n = (size_t)A[l]->M;
-        if (l < nlevels - 1) HIPCHK(alloc(&h->res[l], n));
-        if (l >= 1) { HIPCHK(alloc(&h->rhs[l], n)); HIPCHK(alloc(&h->u[l], n)); HIPCHK(alloc(&h->alt[l], n)); }
+        if (l < nlevels - 1) HIPCHK(alloc_vec(h->res[l], n));
+        if (l >= 1) { HIPCHK(alloc_vec(h->rhs[l], n)); HIPCHK(alloc_vec(h->u[l], n)); HIPCHK(alloc_vec(h->alt[l], n)); }
     }
     // direct coarsest solve: one rank, or a coarsest level that lives whole on one rank (no halo on any rank:
     // the setup shrinks small levels onto rank 0, ranks holding zero rows have nothing to solve)
@@ -3588,7 +3555,7 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
                 for (int j = 0; j < n; ++j) { a[(size_t)r * n + j] -= f * a[(size_t)c * n + j]; inv[(size_t)r * n + j] -= f * inv[(size_t)c * n + j]; }
             }
         }
-        CHK(dev_upload(&h->Ainv, inv.data(), inv.size()));
+        CHK(dev_upload(h->Ainv, inv.data(), inv.size()));
     }
     for (int l = 0; l < nlevels - 1; ++l)          // no allocation may happen inside a graph capture
         if (h->prm.smoother == 1) CHK(ensure_d(A[l]));
@@ -3602,8 +3569,8 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
         if (Lt < nlevels && A[Lt]->M > 0) h->tail_level = Lt;      // (a rank without rows there has nothing to launch anyway)
     }
     const size_t n0 = (size_t)A[0]->M;
-    HIPCHK(alloc(&h->alt0, n0));
-    HIPCHK(alloc(&h->r, n0)); HIPCHK(alloc(&h->rho, n0)); HIPCHK(alloc(&h->hh, n0)); HIPCHK(alloc(&h->p, n0));
+    HIPCHK(alloc_vec(h->alt0, n0));
+    HIPCHK(alloc_vec(h->r, n0)); HIPCHK(alloc_vec(h->rho, n0)); HIPCHK(alloc_vec(h->hh, n0)); HIPCHK(alloc_vec(h->p, n0));
     *out = h.release();
     return SGPU_OK;
 }
@@ -3639,12 +3606,12 @@ int sgpu_amg_profile_matvecs(sgpu_amg *h, int iter, double *us_per_level) {
     if (!h || !us_per_level || iter < 1) return fail(SGPU_ERR_ARG, "bad argument");
     for (int l = 0; l < h->nlevels; ++l) {
         sgpu_op *A = h->A[l];
-        DevBuf v, w;
-        CHK(v.alloc(A->M)); CHK(w.alloc(A->M));
-        CHK(sgpu_vec_fill(v.p, 1.0, A->M));              // saena_object.cpp:625
-        CHK(sgpu_spmv(A, v.p, w.p));                     // warm-up launch (code object load)
+        DevArr<double> v, w;
+        CHK(dev_alloc(v, A->M)); CHK(dev_alloc(w, A->M));
+        CHK(sgpu_vec_fill(v, 1.0, A->M));              // saena_object.cpp:625
+        CHK(sgpu_spmv(A, v, w));                     // warm-up launch (code object load)
         float ms = 0;
-        CHK(sgpu_time_kernel(A, 0, v.p, nullptr, w.p, iter, &ms));
+        CHK(sgpu_time_kernel(A, 0, v, nullptr, w, iter, &ms));
         us_per_level[l] = (double)ms * 1e3;
     }
     return SGPU_OK;
@@ -3844,6 +3811,13 @@ int sgpu_debug_chain_us(double *us) {
     return SGPU_OK;
 }
 
+int sgpu_debug_op_storage(const sgpu_op *op, unsigned *group_mask, long long *live_bytes) {
+    if (!group_mask || !live_bytes) return fail(SGPU_ERR_ARG, "null argument");
+    *group_mask = op ? part_storage_mask(op->loc) : 0;
+    *live_bytes = (long long)devmem::live_bytes.load();
+    return SGPU_OK;
+}
+
 int sgpu_debug_launch_count(long *launches) {
     if (!launches) return fail(SGPU_ERR_ARG, "null argument");
     *launches = g_launches;
@@ -3906,9 +3880,9 @@ namespace {
 struct RcclHostComm : saena_host::Comm {
     static void ok(int s, const char *what) { if (s != SGPU_OK) throw std::runtime_error(std::string(what) + ": " + g_err); }
     struct Buf {
+        DevArr<char> arr;
         void *p = nullptr;
-        explicit Buf(size_t n) { if (hipMalloc(&p, std::max<size_t>(n, 8)) != hipSuccess) throw std::runtime_error("hipMalloc failed in RcclHostComm"); }
-        ~Buf() { hipFree(p); }
+        explicit Buf(size_t n) { if (arr.alloc(std::max<size_t>(n, 8)) != hipSuccess) throw std::runtime_error("hipMalloc failed in RcclHostComm"); p = arr.get(); }
     };
     static int h2d(void *d, const void *h, size_t n) { if (n) HIPCHK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, g.cs)); return SGPU_OK; }
     static int d2h(void *h, const void *d, size_t n) {

@@ -24,6 +24,7 @@
 #include "../../include/saena_gpu.h"
 #include "host/amg_setup.h"
 #include "host/par.h"
+#include "devmem.h"
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -291,14 +292,13 @@ __global__ __launch_bounds__(256) void k_copy_out(const int *__restrict__ ubptr,
     for (int t = lane; t < cnt; t += 64) { ocol[o0 + t] = scol[u0 + t]; oval[o0 + t] = sval[u0 + t]; }
 }
 
-struct Dev {                                    // RAII for the call's device buffers
-    std::vector<void *> p;
-    ~Dev() { for (void *q : p) hipFree(q); }
+struct Dev {                                    // the call's device buffers, freed together when it returns
+    std::vector<devmem::DevArr<char>> p;
     template <class T> T *alloc(size_t n) {
-        void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        p.push_back(q);
-        return static_cast<T *>(q);
+        devmem::DevArr<char> a;
+        if (a.alloc(std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
+        p.push_back(std::move(a));
+        return reinterpret_cast<T *>(p.back().get());
     }
 };
 extern "C" int sgpu_context_device();      // sgpu_runtime.hip: the device of this process's context
@@ -402,9 +402,7 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
     long long *d_bw = nullptr;
     int lds_grid = 256;
     { int dev = 0, ncu = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) lds_grid = ncu; }
-    struct Temp { void *p = nullptr; ~Temp() { if (p) hipFree(p); } } temp;      // the sort's scratch: freed on every return path
-    void *&d_temp = temp.p;
-    size_t temp_bytes = 0;
+    devmem::DevArr<char> temp;                                                  // the sort's scratch: freed on every return path
 
     c_ptr.assign(1, 0);
     c_col.clear(); c_val.clear();
@@ -490,12 +488,11 @@ int gpu_spgemm(int a_rows, int b_rows, int b_cols, const long *a_ptr, const int 
         size_t need = 0;
         SP_CHK(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, need, (const int *)tcol, scol, (const double *)tval, sval, (int)items, n,
                                                            (const int *)d_ubptr, (const int *)d_ends, 0, 32, 0));
-        if (need > temp_bytes) {
-            if (d_temp) { hipFree(d_temp); d_temp = nullptr; }
-            SP_CHK(hipMalloc(&d_temp, need));
-            temp_bytes = need;
+        if (need > temp.bytes()) {
+            temp.reset();
+            SP_CHK(temp.alloc(need));
         }
-        hipError_t se = hipcub::DeviceSegmentedRadixSort::SortPairs(d_temp, need, (const int *)tcol, scol, (const double *)tval, sval, (int)items, n,
+        hipError_t se = hipcub::DeviceSegmentedRadixSort::SortPairs(temp.get(), need, (const int *)tcol, scol, (const double *)tval, sval, (int)items, n,
                                                                     (const int *)d_ubptr, (const int *)d_ends, 0, 32, 0);
         if (se != hipSuccess) return 1;
         h_kept.resize((size_t)n);
