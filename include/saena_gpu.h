@@ -91,12 +91,15 @@ typedef struct {
                                          (saena_matrix_matvec.cpp:56, restrict_matrix.cpp:662, prolong_matrix.cpp:538) */
     nnz_t          nnz_l_local;
     const index_t *nnzPerRow_local;   /* [M]                                            */
-    const index_t *col_local;         /* [nnz_l_local], GLOBAL column ids, row-major    */
+    const index_t *col_local;         /* [nnz_l_local], GLOBAL column ids, row-major; within a row the columns are DISTINCT
+                                         and ASCENDING (the reference's row-major sort).  sgpu_op_create checks it and
+                                         returns SGPU_ERR_ARG naming the row and the position; nothing is built */
     const value_t *val_local;
     nnz_t          nnz_l_remote;
     index_t        col_remote_size;   /* == recvSize                                    */
     const index_t *nnzPerCol_remote;  /* [col_remote_size], in receive-buffer order     */
-    const index_t *row_remote;        /* [nnz_l_remote] local row                       */
+    const index_t *row_remote;        /* [nnz_l_remote] local row; inside one receive column the rows may come in any
+                                         order but each at most once (checked: SGPU_ERR_ARG)                  */
     const value_t *val_remote;
     int            numRecvProc, numSendProc;
     const int     *recvProcRank, *recvProcCount;   /* [numRecvProc], ascending rank     */

@@ -31,7 +31,9 @@ int sgpu_debug_gather_probe(sgpu_op *op, int mode, const value_t *x, int reps, f
 
 /* bench.py (configs[4], "stresses load-balance of wavefront CSR"): the spread of work over the row blocks of the tile kernels' plan
  * (big = 0: 16 KiB tiles of <= 2048 products / 256 rows, 1: 32 KiB tiles).  out[0..7] = blocks, fewest / most entries in a block,
- * entries in all, fewest / most rows in a block, rows longer than the tile (a block of their own: the long-row path), longest row. */
+ * entries in all, fewest / most rows in a block, rows longer than the tile (a block of their own: the long-row path), longest row.
+ * big = 2: the x-in-LDS plan of variants 10 / 12 / 16 once one of them was set: out[0..4] = chunks, most windows of a chunk, columns
+ * per window, 1 where the partial row sums live in LDS behind the window (0: in global memory), most rows in a chunk; the rest 0. */
 int sgpu_debug_block_plan(const sgpu_op *op, int big, long *out);
 
 /* bench.py: the streaming ceiling of a byte mix on this device -- a kernel that reads `read_bytes` with wave-coalesced 16-byte

@@ -390,6 +390,12 @@ class Operator:
         k = ("blocks", "min_nnz_per_block", "max_nnz_per_block", "nnz", "min_rows_per_block", "max_rows_per_block", "long_rows", "longest_row")
         return dict(zip(k, (int(x) for x in o)))
 
+    def xlds_plan(self):
+        """the x-in-LDS plan of variants 10 / 12 / 16 (sgpu_debug_block_plan, big = 2)"""
+        o = (C.c_long * 8)()
+        check(lib().sgpu_debug_block_plan(self.h, 2, o))
+        return dict(zip(("chunks", "windows", "window_columns", "sums_in_lds", "max_rows_per_chunk"), (int(x) for x in o)))
+
     def variant(self):
         v, name = C.c_int(), C.c_char_p()
         check(lib().sgpu_op_get_variant(self.h, C.byref(v), C.byref(name)))

@@ -2338,15 +2338,38 @@ int sgpu_op_create(const sgpu_op_desc *d, sgpu_op **out) {
         }
         if (rp[d->M] != d->nnz_l_local) return fail(SGPU_ERR_ARG, "sum(nnzPerRow_local)=%d != nnz_l_local=%ld", rp[d->M], (long)d->nnz_l_local);
         std::vector<int> col((size_t)d->nnz_l_local);
-        std::atomic<long> bad{-1};
+        // within a row the columns are distinct and ascend: build_xlds / k_xlds_build take a chunk's column range from each row's first
+        // and last entry and cut a row at the windows' edges as it goes, build_dense stores one value per (row, column).  Checked in
+        // the rebasing pass: a thread finds the row its first entry belongs to and walks the row ends from there; the lowest
+        // offending row is named
+        std::atomic<long> bad{-1}, bad_row{-1};
         saena_host::parallel_chunks<long>((long)d->nnz_l_local, 1L << 20, [&](int, long k0, long k1) {      // rebased on threads: 0.6 G entries per level at 16 M rows
+            if (k0 >= k1) return;
+            long r = (long)(std::upper_bound(rp.begin(), rp.end(), (int)k0) - rp.begin()) - 1;              // rp[r] <= k0 < rp[r + 1]
+            long end = rp[(size_t)r + 1];
+            long prev = k0 > rp[(size_t)r] ? (long)d->col_local[k0 - 1] - d->col_offset : -1;
+            bool noted = false;
             for (long k = k0; k < k1; ++k) {
+                if (k == end) { do ++r; while (rp[(size_t)r + 1] <= k); end = rp[(size_t)r + 1]; prev = -1; }
                 const long c = (long)d->col_local[k] - d->col_offset;
                 if (c < 0 || c >= d->N_local) { bad.store(k); return; }
+                if (c <= prev && !noted) {
+                    noted = true;
+                    long seen = bad_row.load();
+                    while ((seen < 0 || r < seen) && !bad_row.compare_exchange_weak(seen, r)) {}
+                }
+                prev = c;
                 col[(size_t)k] = (int)c;
             }
         });
         if (bad.load() >= 0) return fail(SGPU_ERR_ARG, "col_local[%ld]=%d outside this rank's column block", bad.load(), d->col_local[bad.load()]);
+        if (bad_row.load() >= 0) {
+            const long r = bad_row.load();
+            int k = rp[(size_t)r] + 1;
+            while (col[(size_t)k] > col[(size_t)k - 1]) ++k;
+            return fail(SGPU_ERR_ARG, "row %ld of col_local %s column %d at position %d of the row (col_local[%d]): within a row the columns must be distinct and ascending",
+                        r, col[(size_t)k] == col[(size_t)k - 1] ? "repeats" : "steps back to", d->col_local[k], k - rp[(size_t)r], k);
+        }
         const size_t nval = (size_t)d->nnz_l_local;
         auto host_copy = [&](std::vector<double> &dst) { dst.resize(nval); saena_host::parallel_copy(dst.data(), d->val_local, nval); };
         CHK(build_part(op->loc, std::move(rp), std::move(col), d->val_local, nval, nullptr));
@@ -2382,6 +2405,9 @@ int sgpu_op_create(const sgpu_op_desc *d, sgpu_op **out) {
         for (index_t j = 0; j < d->col_remote_size; ++j)
             for (index_t t = 0; t < d->nnzPerCol_remote[j]; ++t, ++k) {
                 const int s = slot[d->row_remote[k]];
+                // (a row twice inside one receive column: the remote CSR would add both, the dense form's remote part keep the last)
+                if (fillp[s] > rp[(size_t)s] && col[fillp[s] - 1] == j)
+                    return fail(SGPU_ERR_ARG, "row_remote[%ld]: row %d appears twice in receive column %d", (long)k, d->row_remote[k], j);
                 col[fillp[s]] = j; val[fillp[s]] = d->val_remote[k]; fillp[s]++;
             }
         if (!op->loc.h_val.empty()) { op->rem.h_val = val; op->rem_rows_h = rows; }      // a dense form is still possible
@@ -3093,6 +3119,13 @@ int sgpu_debug_gather_probe(sgpu_op *op, int mode, const value_t *x, int reps, f
 int sgpu_debug_block_plan(const sgpu_op *op, int big, long *out) {
     if (!op || !out) return fail(SGPU_ERR_ARG, "null argument");
     const CsrPart &P = op->loc;
+    if (big == 2) {                                            // the x-in-LDS plan (variants 10, 12, 16)
+        if (!P.xlp.xl_ok) return fail(SGPU_ERR_STATE, "the x-in-LDS plan was not built");
+        long rmx = 0;
+        for (size_t b = 0; b + 1 < P.xl_blk_h.size(); ++b) rmx = std::max(rmx, (long)(P.xl_blk_h[b + 1] - P.xl_blk_h[b]));
+        out[0] = P.xl_nblk; out[1] = P.xl_maxt; out[2] = P.xl_win; out[3] = P.xl_acc_lds ? 1 : 0; out[4] = rmx; out[5] = out[6] = out[7] = 0;
+        return SGPU_OK;
+    }
     const std::vector<int> &blk = big ? P.h_blk_big : P.h_blk;
     if (blk.size() < 2 || P.h_rp.empty()) return fail(SGPU_ERR_STATE, "the operator keeps no host copy of its row-block plan");
     const int nb = (int)blk.size() - 1, cap = big ? sk::CAP_BIG : sk::CAP;
