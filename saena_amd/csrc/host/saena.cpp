@@ -4,6 +4,7 @@
 #include "../../../include/saena.hpp"
 #include "../../../include/saena_gpu.h"
 #include "../../../include/saena_gpu_debug.h"
+#include "../forms.h"
 #include "comm.h"
 #include "amg_setup.h"
 #include "saena_matrix.h"
@@ -153,7 +154,7 @@ sgpu_op *matrix::device_op() {
         sgpu_op_desc d;
         fill_desc(m_pImpl->L, &m_pImpl->inv_diag, &d);
         gchk(sgpu_op_create(&d, &dev_), "sgpu_op_create");
-        if (use_dense_) gchk(sgpu_op_set_variant(dev_, 5), "saena::matrix::assemble(use_dense = true)");     // dense rows (<= 8192 rows, 64 M entries per rank)
+        if (use_dense_) gchk(sgpu_op_set_variant(dev_, forms::F_DENSE), "saena::matrix::assemble(use_dense = true)");     // dense rows (<= 8192 rows, 64 M entries per rank)
     }
     return dev_;
 }
@@ -298,7 +299,7 @@ int amg::set_matrix(saena::matrix *A, saena::options *opts) {
     if (o.switch_to_dense)                    // saena_object_setup2.cpp:328
         for (int l = 1; l < n; ++l) {
             const double rows = (double)H_->level_rows(l), dens = (double)H_->level_nnzA(l) / (rows * rows);
-            if (dens > o.dense_thre && rows <= o.dense_sz_thre) sgpu_op_set_variant(dA_[(size_t)l], 5);     // refused (halo, size): stays sparse
+            if (dens > o.dense_thre && rows <= o.dense_sz_thre) sgpu_op_set_variant(dA_[(size_t)l], forms::F_DENSE);     // refused (halo, size): stays sparse
         }
     sgpu_amg_params p;
     sgpu_amg_default_params(&p);

@@ -1,5 +1,6 @@
 // saena_c_api.cpp -- flat C view (include/saena_c.h) of the host-side mirror.
 #include "../../../include/saena_c.h"
+#include "../forms.h"
 #include "saena_matrix.h"
 #include "amg_setup.h"
 #include "shm_comm.h"
@@ -384,7 +385,7 @@ int saena_amg_to_device(saena_amg_h *S) {
     if (S->H.opts.switch_to_dense)            // saena_object_setup2.cpp:328: switch_to_dense && density > dense_thre && Mbig <= dense_sz_thre
         for (int l = 1; l < n; ++l) {
             const double rows = (double)S->H.level_rows(l), dens = (double)S->H.level_nnzA(l) / (rows * rows);
-            if (dens > S->H.opts.dense_thre && rows <= S->H.opts.dense_sz_thre) sgpu_op_set_variant(S->dA[(size_t)l], 5);   // refused (halo, size): stays sparse
+            if (dens > S->H.opts.dense_thre && rows <= S->H.opts.dense_sz_thre) sgpu_op_set_variant(S->dA[(size_t)l], forms::F_DENSE);   // refused (halo, size): stays sparse
         }
     sgpu_amg_params p;
     sgpu_amg_default_params(&p);

@@ -13,6 +13,7 @@
 #include "kernels_eig.hip.h"
 #include "dispatch.h"
 #include "devmem.h"
+#include "forms.h"
 #include "host/dense_eig.h"
 #include "host/comm.h"
 #include "host/par.h"
@@ -44,6 +45,7 @@ extern "C" void sgpu_install_spgemm_hook(int on);
 
 using devmem::DevArr;
 using devmem::PinArr;
+using namespace forms;
 
 namespace {
 
@@ -140,7 +142,7 @@ int dev_upload(DevArr<T> &dst, const T *src, size_t n, size_t pad = 0) {
 // Its device arrays live in GROUPS, one per unit of lifetime: a group holds the arrays and the built / tried flags that a free
 // clears with them, and `G = {}` frees it.  The scalars a launch reads (nslices, sl_pair, sl_uw, sp_w, sp_n, sp_bytes, sp2_uw,
 // sp2_nslices, vi_uw8, xl_nblk ...) stay outside: a surviving form may read them after the arrays they were computed with are gone.
-// Which plan keeps which group: plan_keeps() below, the one place a new form registers its storage.
+// Which plan keeps which group: plan_keeps() in forms.h, the one place a new form registers its storage.
 struct CsrPart {
     int     nrows = 0;            // rows covered by row_ptr (M, or number of remote rows)
     int64_t nnz = 0;
@@ -264,30 +266,6 @@ struct CsrPart {
     std::vector<int> h_rp, h_col, h_blk, h_blk_big;   // host copies kept for build_cc16 / the coarsest factorisation
 };
 
-// The storage groups of a part in the order of sgpu_debug_op_storage's bits, and which of them the plan that settles on variant
-// `bv` keeps (finish_plan resets the others).  vw_rows: the x-window workgroup size in use, its tables alone stay with variant 17.
-enum PartGroup { G_CSR, G_DENSE, G_CC0, G_CC1, G_CM0, G_CM1, G_SELL_VALUES, G_SELL_COLUMNS, G_SELLP, G_VIDX, G_XWIN0, G_XWIN1, G_XWIN2,
-                 G_SELLP2, G_SELLPX, G_ROWT, G_XLDS_PLAN, G_XLDS_COLUMNS, G_SELLX, G_COUNT };
-bool plan_keeps(int grp, int bv, int vw_rows) {
-    switch (grp) {
-    case G_CSR:          return true;
-    case G_DENSE:        return bv == 5;
-    case G_CC0: case G_CC1: { const int k = grp - G_CC0; return bv == 3 + k || bv == 7 + k; }
-    case G_CM0: case G_CM1: return bv == 7 + (grp - G_CM0);
-    case G_SELL_VALUES:  return bv == 9 || bv == 11 || bv == 15;
-    case G_SELL_COLUMNS: return bv == 9;
-    case G_SELLP:        return bv == 11 || bv == 14 || bv == 15 || bv == 17;
-    case G_VIDX:         return bv == 17;
-    case G_XWIN0: case G_XWIN1: case G_XWIN2: return bv == 17 && (256 << (grp - G_XWIN0)) == vw_rows;
-    case G_SELLP2:       return bv == 14;
-    case G_SELLPX:       return bv == 15;
-    case G_ROWT:         return bv == 13;
-    case G_XLDS_PLAN:    return bv == 10 || bv == 12 || bv == 16;
-    case G_XLDS_COLUMNS: return bv == 10 || bv == 16;
-    case G_SELLX:        return bv == 12;
-    }
-    return true;
-}
 // does the group hold memory? (sgpu_debug_op_storage)
 unsigned part_storage_mask(const CsrPart &P) {
     const bool held[G_COUNT] = {
@@ -1638,38 +1616,38 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
     a.nt = nt_rt == 1 || (nt_rt == 2 && 12 * P.nnz > (int64_t)256 * 1024 * 1024) ? 1 : 0;
     const bool halo = skip != nullptr || seq != 0;
     switch (P.variant) {
-    default: {                                                    // 0, 1: 32-bit columns, 16 / 32 KiB tiles
-        const bool big = P.variant == 1;
+    default: {                                                    // F_STREAM16, F_STREAM32: 32-bit columns, 16 / 32 KiB tiles
+        const bool big = P.variant == F_STREAM32;
         a.blk_row = big ? P.csr.blk_row_big : P.csr.blk_row;
         a.nblk = big ? P.nblk_big : P.nblk;
         SGPU_LAUNCH_PICKED("k_csr_stream", pick_tile<0>(epi, P.lanes, big, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     } break;
-    case 2: {                                                     // vector CSR
+    case F_VECTOR: {                                              // vector CSR
         const int rpb = sk::BLOCK / P.lanes;
         a.blk_row = nullptr; a.nblk = 0;
         SGPU_LAUNCH_PICKED("k_csr_vector", pick_vec(epi, P.lanes, halo), dim3((P.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
     } break;
-    case 3: case 4: {                                             // 16-bit compressed columns
-        const int k = P.variant - 3;
+    case F_CC16_16: case F_CC16_32: {                             // 16-bit compressed columns
+        const int k = tile_plan(P.variant);
         if (!P.cc[k].ok) return fail(SGPU_ERR_STATE, "compressed columns of plan %d were not built", k);
         a.blk_row = k ? P.csr.blk_row_big : P.csr.blk_row;
         a.nblk = k ? P.nblk_big : P.nblk;
         a.segtab = P.cc[k].segtab; a.segptr = P.cc[k].segptr; a.ccol = P.cc[k].ccol; a.cc_ob = P.cc_ob[k];
         SGPU_LAUNCH_PICKED("k_csr_cc16", pick_tile<1>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     } break;
-    case 5: {                                                     // dense rows, one wave per row
+    case F_DENSE: {                                               // dense rows, one wave per row
         if (!P.dn.dense) return fail(SGPU_ERR_STATE, "the dense form was not built");
         if (halo) return fail(SGPU_ERR_STATE, "the dense form serves operators without a halo");
         a.blk_row = nullptr; a.nblk = 0;
         SGPU_LAUNCH_PICKED("k_dense_rows", pick_dense(epi), dim3((P.nrows + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, (const double *)P.dn.dense, P.nrows, P.ncols);
     } break;
-    case 6: {                                                     // wave-streamed long rows, 16-byte loads
+    case F_WAVE: {                                                // wave-streamed long rows, 16-byte loads
         const int gl = std::max(8, P.lanes), rpb = sk::BLOCK / gl;
         a.blk_row = nullptr; a.nblk = 0;
         SGPU_LAUNCH_PICKED("k_csr_wave", pick_wave(epi, gl, halo), dim3((P.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
     } break;
-    case 7: case 8: {                                             // compressed columns, entries in column order inside a block
-        const int k = P.variant - 7;
+    case F_CM16: case F_CM32: {                                   // compressed columns, entries in column order inside a block
+        const int k = tile_plan(P.variant);
         if (!P.cm[k].ok) return fail(SGPU_ERR_STATE, "the column-major form of plan %d was not built", k);
         a.blk_row = k ? P.csr.blk_row_big : P.csr.blk_row;
         a.nblk = k ? P.nblk_big : P.nblk;
@@ -1677,7 +1655,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         a.val = P.cm[k].val; a.ccol = P.cm[k].col; a.dst = P.cm[k].dst; a.cmptr = P.cm[k].ptr;
         SGPU_LAUNCH_PICKED("k_csr_cm", pick_tile<2>(epi, P.lanes, k == 1, halo), dim3(a.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     } break;
-    case 9: {                                                     // sliced ELLPACK, a lane per row
+    case F_SELL: {                                                // sliced ELLPACK, a lane per row
         if (!P.sl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK form was not built");
         a.blk_row = P.sv.sl_sorted ? P.sv.sl_perm : nullptr; a.nblk = P.nslices;
         a.val = P.sv.sl_val; a.ccol = P.sc.sl_col; a.segtab = P.sc.sl_base; a.segptr = P.sc.sl_segptr; a.cc_ob = P.sl_ob; a.cmptr = P.sv.sl_ptr; a.dst = P.sc.sl_len;
@@ -1691,15 +1669,15 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         a.nt_from = nt ? resident_slices(P.nslices, 10.0 * (double)P.nnz / (double)std::max(1, P.nslices)) : 0;
         SGPU_LAUNCH_PICKED("k_sell", pick_sell(epi, halo, P.sl_pair, nt), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), 0, g.cs, a, P.nrows);
     } break;
-    case 10: case 16: {                                           // x in LDS, a workgroup per CU (16: four rows per group step -- short rows)
+    case F_XLDS: case F_XLDSR: {                                  // x in LDS, a workgroup per CU (F_XLDSR: four rows per group step -- short rows)
         if (!P.xlp.xl_ok || !P.xlc.xl_col) return fail(SGPU_ERR_STATE, "the x-in-LDS form was not built");
         a.blk_row = P.xlp.xl_blk; a.nblk = P.xl_nblk; a.ccol = P.xlc.xl_col;
         sk::XldsArgs w;
         w.info = P.xlp.xl_info; w.tab = P.xlc.xl_tab; w.acc = P.xlp.xl_acc; w.ncols = P.ncols;
         w.win = P.xl_win; w.acc_lds = P.xl_acc_lds ? 1 : 0; w.ord = P.xlp.xl_ord;
-        SGPU_LAUNCH_PICKED("k_csr_xlds", P.variant == 16 ? pick_xldsr(epi, P.lanes, halo) : pick_xlds(epi, P.lanes, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
+        SGPU_LAUNCH_PICKED("k_csr_xlds", P.variant == F_XLDSR ? pick_xldsr(epi, P.lanes, halo) : pick_xlds(epi, P.lanes, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
     } break;
-    case 11: {                                                    // sliced ELLPACK values + row patterns, a lane per row
+    case F_SELLP: {                                               // sliced ELLPACK values + row patterns, a lane per row
         if (!P.sp.sp_ok || !P.sv.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form was not built");
         a.blk_row = nullptr; a.nblk = P.nslices;
         a.val = P.sv.sl_val; a.cmptr = P.sv.sl_ptr; a.dst = P.sp.sp_pat; a.ptab = P.sp.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
@@ -1712,7 +1690,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         } else
         SGPU_LAUNCH_PICKED("k_sellp", pick_sellp(epi, halo, P.sl_pair, nt, false), dim3((P.nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
     } break;
-    case 12: {                                                    // sliced ELLPACK in the LDS windows, a workgroup per CU
+    case F_SELLX: {                                               // sliced ELLPACK in the LDS windows, a workgroup per CU
         if (!P.sx.sx_ok || !P.xlp.xl_ok) return fail(SGPU_ERR_STATE, "the sliced-ELLPACK-in-LDS form was not built");
         a.blk_row = P.xlp.xl_blk; a.nblk = P.xl_nblk;
         sk::SellxArgs w;
@@ -1721,7 +1699,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         if (nt_rt == 0 && !std::getenv("SAENA_STREAM_NT")) a.nt = 10 * P.nnz > (int64_t)256 * 1024 * 1024 ? 1 : 0;      // non-temporal streams beyond the Infinity Cache (438 -> 426 us)
         SGPU_LAUNCH_PICKED("k_sellx", pick_sellx(epi, halo), dim3(P.xl_nblk), dim3(sk::XL_BLOCK), 0, g.cs, a, w);
     } break;
-    case 13: {                                                    // row templates: a thread per row, no operator stream at all
+    case F_ROWT: {                                                // row templates: a thread per row, no operator stream at all
         if (!P.rt.rt_ok) return fail(SGPU_ERR_STATE, "the row-template form was not built");
         a.blk_row = nullptr; a.nblk = 0;
         a.val = P.rt.rt_vtab; a.dst = P.rt.rt_pat; a.ptab = P.rt.rt_itab; a.pt_w = P.rt_w; a.pt_n = P.rt_n;
@@ -1729,7 +1707,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         const size_t lds = (size_t)P.rt_n * ((size_t)P.rt_w * 8 + (size_t)(P.rt_w + 1) * 4);
         SGPU_LAUNCH_PICKED("k_rowt", pick_rowt(epi, halo, nt), dim3((P.nrows + sk::BLOCK - 1) / sk::BLOCK), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
     } break;
-    case 14: {                                                    // k_sellp with a lane per two rows
+    case F_SELLP2: {                                              // k_sellp with a lane per two rows
         if (!P.sp2.sp2_ok || !P.sp.sp_ok) return fail(SGPU_ERR_STATE, "the row-paired row-pattern form was not built");
         a.blk_row = nullptr; a.nblk = P.sp2_nslices;
         a.val = P.sp2.sp2_val; a.cmptr = P.sp2.sp2_ptr; a.dst = P.sp.sp_pat; a.ptab = P.sp.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n;
@@ -1744,7 +1722,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         } else
         SGPU_LAUNCH_PICKED("k_sellp2", pick_sellp2<false>(epi, halo, nt, pre), dim3((P.sp2_nslices + 3) / 4), dim3(sk::BLOCK), (size_t)P.sp_n * (P.sp_w + 1) * sizeof(int), g.cs, a, P.nrows);
     } break;
-    case 15: {                                                    // k_sellp with x in LDS windows
+    case F_SELLPX: {                                              // k_sellp with x in LDS windows
         if (!P.spx.spx_ok || !P.sp.sp_ok || !P.sv.sl_val) return fail(SGPU_ERR_STATE, "the row-pattern form with x in LDS was not built");
         a.blk_row = nullptr; a.nblk = P.nslices;
         a.val = P.sv.sl_val; a.cmptr = P.sv.sl_ptr; a.dst = P.spx.spx_pat; a.ptab = reinterpret_cast<const int *>(P.spx.spx_tab.get()); a.pt_w = 0; a.pt_n = P.sp_n;
@@ -1752,7 +1730,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         const bool nt = row_pattern_nt(a, P.sp_bytes, P.nslices, 8.0 * (double)P.nnz / (double)std::max(1, P.nslices));
         SGPU_LAUNCH_PICKED("k_sellpx", pick_sellpx(epi, halo, P.sl_pair, nt), dim3((P.nslices + sk::SPX_ROWS / 64 - 1) / (sk::SPX_ROWS / 64)), dim3(sk::SPX_BLOCK), 0, g.cs, a, P.nrows);
     } break;
-    case 17: {                                                    // row patterns + 8-bit value codes, a lane per row
+    case F_VIDX: {                                                // row patterns + 8-bit value codes, a lane per row
         if (!P.vi.vi_ok || !P.sp.sp_ok) return fail(SGPU_ERR_STATE, "the value-indexed row-pattern form was not built");
         a.blk_row = nullptr; a.nblk = P.nslices ? P.nslices : (P.nrows + 63) / 64;
         a.dst = P.sp.sp_pat; a.ptab = P.sp.sp_tab; a.pt_w = P.sp_w; a.pt_n = P.sp_n; a.rbase = P.sp.sp_rbase;
@@ -1760,7 +1738,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         const bool nt = row_pattern_nt(a, P.vi_bytes, a.nblk, (double)P.nnz / (double)std::max(1, a.nblk));     // (about a byte of codes per entry)
         const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
         if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS positions
-            const int k = P.vw_rows == 256 ? 0 : P.vw_rows == 512 ? 1 : 2, spb = P.vw_rows / 64;
+            const int k = xwin_slot(P.vw_rows), spb = P.vw_rows / 64;
             const CsrPart::XWin &X = P.vw[k];
             if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
             a.ptab = reinterpret_cast<const int *>(X.tab.get()); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
@@ -1819,7 +1797,7 @@ int exchange_group(sgpu_op *op, bool f32, hipStream_t st) {
 }
 
 int launch_rows_after_exchange(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, bool f32, hipStream_t stream) {
-    if (op->loc.variant == 5 && op->has_remote) return launch_dense_halo(op, epi, x, y, e, f32, stream);
+    if (is_dense(op->loc.variant) && op->has_remote) return launch_dense_halo(op, epi, x, y, e, f32, stream);
     CHK(launch_part(op->loc, epi, x, y, e, op->has_remote ? op->skip : nullptr));     // (always on cs: callers pass cs)
     if (op->has_remote) CHK(launch_boundary(op, epi, x, y, e, f32, stream));
     return SGPU_OK;
@@ -1866,13 +1844,13 @@ int apply(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e) {
         if ((op->has_remote || op->recvSize) && !g.multi() && !op->local_only_ok)
             return fail(SGPU_ERR_STATE, "operator has %d halo entries but this context has no communicator (sgpu_init was given nranks=%d, no unique id)",
                         op->recvSize, g.nranks);
-        if (op->loc.variant == 5 && op->halo_fp32)      // matvec_dense_float rounds the rank's own block of x as well
+        if (is_dense(op->loc.variant) && op->halo_fp32)    // matvec_dense_float rounds the rank's own block of x as well
             return launch_dense_halo(op, epi, x, y, e, false, g.cs);
         return launch_part(op->loc, epi, x, y, e);      // no halo: the local part is the whole operator
     }
     const bool f32 = op->halo_fp32 != 0;                 // both ends of a link must agree: the flag alone decides the wire type
     const unsigned *skip = op->has_remote ? op->skip : nullptr;
-    if (op->single_stream || (op->loc.variant == 5 && op->has_remote)) {      // (the dense form has no interior/boundary split)
+    if (op->single_stream || (is_dense(op->loc.variant) && op->has_remote)) {      // (the dense form has no interior/boundary split)
         // S  one stream.  A SHORT local kernel has nothing to hide the exchange behind, and the fork/join between the
         //    two streams then costs more than it overlaps: pack -> send/recv group -> interior rows -> boundary rows,
         //    all on cs, in stream order (4 enqueues instead of 6, no flag, no event; capturable in a hipGraph).
@@ -2516,109 +2494,111 @@ int sgpu_op_set_lanes_per_row(sgpu_op *op, int lanes) {
     return SGPU_OK;
 }
 
-// the kernel forms, by number: ONE table, whose length is what set_variant, the plan cache's lookup and its store accept
-static const char *const VARIANT_NAMES[] = {"k_csr_stream<16KiB>", "k_csr_stream<32KiB>", "k_csr_vector", "k_csr_cc16<16KiB>", "k_csr_cc16<32KiB>", "k_dense_rows", "k_csr_wave", "k_csr_cm<16KiB>", "k_csr_cm<32KiB>", "k_sell", "k_csr_xlds", "k_sellp", "k_sellx", "k_rowt", "k_sellp2", "k_sellpx", "k_csr_xldsr", "k_vidx"};   // (3, 4, 7, 8 are named with their slot/offset split below)
-static constexpr int MAX_VARIANT = (int)(sizeof VARIANT_NAMES / sizeof VARIANT_NAMES[0]) - 1;
-// the workgroup sizes (256 << k rows) at which the autotune times the x-window mode of variant 17: 256 rows win on the cache-resident
+// the workgroup sizes (256 << k rows) at which the autotune times the x-window mode of F_VIDX: 256 rows win on the cache-resident
 // 128^3 fine level, 512 on the HBM-resident 256^3 one; 1024 won on neither and stays a setting of sgpu_op_set_x_windows
 static const int XWIN_CANDIDATES[] = {0, 1};
+
+extern "C++" {
+namespace {
+// the form's base name, decorated from the part's flags: the slot/offset split of the compressed columns ("k_csr_cc16<32KiB,5+11>"),
+// <wide> (a pattern table per workgroup), <rowbase> (patterns relative to the row's first column), <sorted> (slices sorted by length)
+std::string form_name(const CsrPart &P) {
+    const int f = P.variant;
+    std::string n = FORM_NAMES[f];
+    if (is_cc16(f) || is_column_major(f)) {
+        const int ob = P.cc_ob[tile_plan(f)];
+        n.pop_back();
+        n += "," + std::to_string(16 - ob) + "+" + std::to_string(ob) + ">";
+    }
+    const bool wide = (f == F_SELLP || f == F_SELLP2) && P.sp.sp_wide, rbase = (f == F_SELLP || f == F_VIDX) && P.sp.sp_rbase;
+    if (wide || rbase) n += std::string("<") + (wide ? "wide" : "") + (wide && rbase ? "," : "") + (rbase ? "rowbase" : "") + ">";
+    if (f == F_SELL && P.sv.sl_sorted) n += "<sorted>";
+    return n;
+}
+
+// Build what `form` launches from: its prerequisite builders in order.  Every builder opens with its own tried / ok guard, so a
+// second call builds nothing.  *ok: the form can run on this operator (the dense form reports through the builder's own error).
+int build_form(sgpu_op *op, int form, bool *ok) {
+    CsrPart &L = op->loc;
+    *ok = true;
+    switch (form) {
+    case F_CC16_16: case F_CC16_32: CHK(build_cc16(L, tile_plan(form))); *ok = L.cc[tile_plan(form)].ok; break;
+    case F_DENSE:   CHK(build_dense(L)); CHK(build_dense_rem(op)); break;
+    case F_CM16: case F_CM32: CHK(build_cm(L, tile_plan(form), op->h_val_all)); *ok = L.cm[tile_plan(form)].ok; break;
+    case F_SELL:    CHK(build_sell(L, op->h_val_all)); *ok = L.sl_ok; break;
+    case F_XLDS: case F_XLDSR: CHK(build_xlds(L)); *ok = L.xlp.xl_ok; break;
+    case F_SELLP:   CHK(build_sell_values(L)); CHK(build_sellp(L)); *ok = L.sp.sp_ok; break;
+    case F_SELLX:   CHK(build_xlds(L)); CHK(build_sellx(L, op->h_val_all)); *ok = L.sx.sx_ok; break;
+    case F_ROWT:    CHK(build_rowt(L, op->h_val_all)); *ok = L.rt.rt_ok; break;
+    case F_SELLP2:  CHK(build_sell_values(L)); CHK(build_sellp(L)); CHK(build_sellp2(L, op->h_val_all)); *ok = L.sp2.sp2_ok; break;
+    case F_SELLPX:  CHK(build_sell_values(L)); CHK(build_sellp(L)); CHK(build_sellpx(L)); *ok = L.spx.spx_ok; break;
+    case F_VIDX:    CHK(build_sell_values(L)); CHK(build_sellp(L)); CHK(build_vidx(L)); *ok = L.vi.vi_ok; break;
+    default: break;                                      // F_STREAM16, F_STREAM32, F_VECTOR, F_WAVE: the CSR arrays as they are
+    }
+    return SGPU_OK;
+}
+
+// why build_form left `form` without its ok
+int refuse_form(int form) {
+    switch (form) {
+    case F_CC16_16: case F_CC16_32:
+        return fail(SGPU_ERR_ARG, "a row block of this operator touches more than 256 column segments of 256 columns");
+    case F_CM16: case F_CM32:
+        return fail(SGPU_ERR_ARG, "the column-major form needs compressed columns, no row longer than the tile and the host copy of the values "
+                                  "(kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)");
+    case F_SELL:
+        return fail(SGPU_ERR_ARG, "the sliced-ELLPACK form needs even rows (padding <= 12 %%), 16-bit column codes (<= 256 segments per 256 rows) and "
+                                  "the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)");
+    case F_XLDS: case F_XLDSR:
+        return fail(SGPU_ERR_ARG, "the x-in-LDS form needs row chunks (one per CU) that reach over at most %d columns", sk::XL_MAXT * sk::XL_MAX);
+    case F_SELLP:
+        return fail(SGPU_ERR_ARG, "the row-pattern form needs what the sliced-ELLPACK form needs and rows that follow at most %d-int's worth of "
+                                  "(length, relative columns) patterns per group of %d rows", sk::SPW_MAX_TABLE, sk::SPW_BLOCK);
+    case F_SELLX:
+        return fail(SGPU_ERR_ARG, "the sliced-ELLPACK-in-LDS form needs the x-in-LDS plan (row chunks over at most %d column windows), at most 25 %% padding "
+                                  "and the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)", sk::XL_MAXT);
+    case F_ROWT:
+        return fail(SGPU_ERR_ARG, "the row-template form needs rows that repeat at most %d bytes' worth of (length, relative columns, values) templates "
+                                  "and the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)", RT_MAX_BYTES);
+    case F_SELLP2:
+        return fail(SGPU_ERR_ARG, "the row-paired row-pattern form needs what the row-pattern form needs (k_sellp) and the host copy of the values");
+    case F_SELLPX:
+        return fail(SGPU_ERR_ARG, "the row-pattern form with x in LDS needs what the row-pattern form needs (k_sellp) and pattern offsets that fall into at most %d "
+                                  "windows of x which fit %d KiB of LDS together with the table", sk::SPX_MAXWIN, sk::SPX_LDS_BYTES / 1024);
+    case F_VIDX:
+        return fail(SGPU_ERR_ARG, "the value-indexed row-pattern form needs what the row-pattern form needs (k_sellp) with ONE pattern table, and at most %d "
+                                  "distinct values (as bit patterns) in every group of %d rows", sk::VI_MAX, sk::BLOCK);
+    }
+    return fail(SGPU_ERR_STATE, "form %d was not built", form);
+}
+} // namespace
+} // extern "C++"
 
 int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_name) {
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     if (variant) *variant = op->loc.variant;
     if (kernel_name) {
-        const int v = op->loc.variant;
-        if (v == 3 || v == 4 || v == 7 || v == 8) {      // name the slot/offset split of the compressed columns: "k_csr_cc16<32KiB,5+11>"
-            char buf[64];
-            const int k = (v == 3 || v == 7) ? 0 : 1;
-            snprintf(buf, sizeof buf, "%s<%s,%d+%d>", v >= 7 ? "k_csr_cm" : "k_csr_cc16", k == 0 ? "16KiB" : "32KiB", 16 - op->loc.cc_ob[k], op->loc.cc_ob[k]);
-            const_cast<sgpu_op *>(op)->vname = buf;
-            *kernel_name = op->vname.c_str();
-        } else {
-            *kernel_name = (v == 17 && op->loc.sp.sp_rbase) ? "k_vidx<rowbase>" : (v == 11 && op->loc.sp.sp_rbase) ? (op->loc.sp.sp_wide ? "k_sellp<wide,rowbase>" : "k_sellp<rowbase>") : (v == 11 && op->loc.sp.sp_wide) ? "k_sellp<wide>" : (v == 14 && op->loc.sp.sp_wide) ? "k_sellp2<wide>" : (v == 9 && op->loc.sv.sl_sorted) ? "k_sell<sorted>" : VARIANT_NAMES[v];      // the compact table around 1024 threads
-        }
+        const_cast<sgpu_op *>(op)->vname = form_name(op->loc);
+        *kernel_name = op->vname.c_str();
     }
     return SGPU_OK;
 }
 
 int sgpu_op_set_variant(sgpu_op *op, int variant) {
     if (!op) return fail(SGPU_ERR_ARG, "null op");
-    if (variant < 0 || variant > MAX_VARIANT) return fail(SGPU_ERR_ARG, "variant must be 0..%d", MAX_VARIANT);
-    if (variant == 17) {
-        CHK(build_sell_values(op->loc));
-        CHK(build_sellp(op->loc));
-        CHK(build_vidx(op->loc));
-        if (!op->loc.vi.vi_ok)
-            return fail(SGPU_ERR_ARG, "the value-indexed row-pattern form needs what the row-pattern form needs (k_sellp) with ONE pattern table, and at most %d "
-                                      "distinct values (as bit patterns) in every group of %d rows", sk::VI_MAX, sk::BLOCK);
-    }
-    if (variant == 15) {
-        CHK(build_sell_values(op->loc));
-        CHK(build_sellp(op->loc));
-        CHK(build_sellpx(op->loc));
-        if (!op->loc.spx.spx_ok)
-            return fail(SGPU_ERR_ARG, "the row-pattern form with x in LDS needs what the row-pattern form needs (k_sellp) and pattern offsets that fall into at most %d "
-                                      "windows of x which fit %d KiB of LDS together with the table", sk::SPX_MAXWIN, sk::SPX_LDS_BYTES / 1024);
-    }
-    if (variant == 14) {
-        CHK(build_sell_values(op->loc));
-        CHK(build_sellp(op->loc));
-        CHK(build_sellp2(op->loc, op->h_val_all));
-        if (!op->loc.sp2.sp2_ok)
-            return fail(SGPU_ERR_ARG, "the row-paired row-pattern form needs what the row-pattern form needs (k_sellp) and the host copy of the values");
-    }
-    if (variant == 13) {
-        CHK(build_rowt(op->loc, op->h_val_all));
-        if (!op->loc.rt.rt_ok)
-            return fail(SGPU_ERR_ARG, "the row-template form needs rows that repeat at most %d bytes' worth of (length, relative columns, values) templates "
-                                      "and the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)", RT_MAX_BYTES);
-    }
-    if (variant == 12) {
-        CHK(build_xlds(op->loc));
-        CHK(build_sellx(op->loc, op->h_val_all));
-        if (!op->loc.sx.sx_ok)
-            return fail(SGPU_ERR_ARG, "the sliced-ELLPACK-in-LDS form needs the x-in-LDS plan (row chunks over at most %d column windows), at most 25 %% padding "
-                                      "and the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)", sk::XL_MAXT);
-    }
-    if (variant == 11) {
-        CHK(build_sell_values(op->loc));
-        CHK(build_sellp(op->loc));
-        if (!op->loc.sp.sp_ok)
-            return fail(SGPU_ERR_ARG, "the row-pattern form needs what the sliced-ELLPACK form needs and rows that follow at most %d-int's worth of "
-                                      "(length, relative columns) patterns per group of %d rows", sk::SPW_MAX_TABLE, sk::SPW_BLOCK);
-    }
-    if (variant == 10 || variant == 16) {
-        CHK(build_xlds(op->loc));
-        if (!op->loc.xlp.xl_ok)
-            return fail(SGPU_ERR_ARG, "the x-in-LDS form needs row chunks (one per CU) that reach over at most %d columns",
-                        sk::XL_MAXT * sk::XL_MAX);
-    }
-    if (variant == 9) {
-        CHK(build_sell(op->loc, op->h_val_all));
-        if (!op->loc.sl_ok)
-            return fail(SGPU_ERR_ARG, "the sliced-ELLPACK form needs even rows (padding <= 12 %%), 16-bit column codes (<= 256 segments per 256 rows) and "
-                                      "the host copy of the values (kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)");
-    } else if (variant == 5) {
-        CHK(build_dense(op->loc));
-        CHK(build_dense_rem(op));
-    } else if (variant == 7 || variant == 8) {
-        CHK(build_cm(op->loc, variant - 7, op->h_val_all));
-        if (!op->loc.cm[variant - 7].ok)
-            return fail(SGPU_ERR_ARG, "the column-major form needs compressed columns, no row longer than the tile and the host copy of the values "
-                                      "(kept until the plan-time autotune, or with SAENA_KEEP_HOST_VALUES=1)");
-    } else if (variant == 3 || variant == 4) {
-        CHK(build_cc16(op->loc, variant - 3));
-        if (!op->loc.cc[variant - 3].ok) return fail(SGPU_ERR_ARG, "a row block of this operator touches more than 256 column segments of 256 columns");
-    }
+    if (variant < 0 || variant >= F_COUNT) return fail(SGPU_ERR_ARG, "variant must be 0..%d", F_COUNT - 1);
+    bool ok = false;
+    CHK(build_form(op, variant, &ok));
+    if (!ok) return refuse_form(variant);
     op->loc.variant = variant;
-    op->loc.vw_rows = 0;                                 // variant 17 alone gathers directly; sgpu_op_set_x_windows turns the windows on
+    op->loc.vw_rows = 0;                                 // F_VIDX alone gathers directly; sgpu_op_set_x_windows turns the windows on
     ++g_plan_generation;
-    if (variant == 17)
+    if (variant == F_VIDX)
         if (const char *e = std::getenv("SAENA_X_WINDOWS")) {     // development: pin the mode where only the variant can be pinned (counter passes); refused -> direct
-            const int rows = std::atoi(e);
-            if (rows == 256 || rows == 512 || rows == 1024) {
-                CHK(build_xwin(op->loc, rows == 256 ? 0 : rows == 512 ? 1 : 2));
-                if (op->loc.vw[rows == 256 ? 0 : rows == 512 ? 1 : 2].ok) op->loc.vw_rows = rows;
+            const int rows = std::atoi(e), k = xwin_slot(rows);
+            if (k >= 0) {
+                CHK(build_xwin(op->loc, k));
+                if (op->loc.vw[k].ok) op->loc.vw_rows = rows;
             }
         }
     return SGPU_OK;
@@ -2629,9 +2609,9 @@ int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     const int R = rows_per_workgroup;
     if (R == 0) { op->loc.vw_rows = 0; ++g_plan_generation; return SGPU_OK; }
-    if (R != 256 && R != 512 && R != 1024) return fail(SGPU_ERR_ARG, "x windows: rows per workgroup must be 0 (off), 256, 512 or 1024");
-    if (op->loc.variant != 17) return fail(SGPU_ERR_ARG, "x windows are a launch mode of the value-indexed form: set variant 17 first");
-    const int k = R == 256 ? 0 : R == 512 ? 1 : 2;
+    const int k = xwin_slot(R);
+    if (k < 0) return fail(SGPU_ERR_ARG, "x windows: rows per workgroup must be 0 (off), 256, 512 or 1024");
+    if (op->loc.variant != F_VIDX) return fail(SGPU_ERR_ARG, "x windows are a launch mode of the value-indexed form: set variant 17 first");
     std::string why;
     CHK(build_xwin(op->loc, k, &why));
     if (!op->loc.vw[k].ok)
@@ -2645,7 +2625,7 @@ int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
 
 int sgpu_op_get_x_windows(const sgpu_op *op, int *rows_per_workgroup) {
     if (!op || !rows_per_workgroup) return fail(SGPU_ERR_ARG, "null argument");
-    *rows_per_workgroup = op->loc.variant == 17 ? op->loc.vw_rows : 0;
+    *rows_per_workgroup = op->loc.variant == F_VIDX ? op->loc.vw_rows : 0;
     return SGPU_OK;
 }
 
@@ -2706,18 +2686,19 @@ bool plan_cache_lookup(uint64_t key, int *v, int *lanes, int *xw) {
     bool hit = false;
     while (fgets(line, sizeof line, f)) {               // the last line of a key wins
         unsigned long long k; int vv, ll, xx;
-        if (sscanf(line, "%llx %d %d %d", &k, &vv, &ll, &xx) == 4 && k == key && vv >= 0 && vv <= MAX_VARIANT && ll >= 1 && ll <= 64 &&
-            (xx == 0 || (vv == 17 && (xx == 256 || xx == 512 || xx == 1024)))) { *v = vv; *lanes = ll; *xw = xx; hit = true; }
+        if (sscanf(line, "%llx %d %d %d", &k, &vv, &ll, &xx) == 4 && k == key && plan_line_valid(vv, ll, xx)) { *v = vv; *lanes = ll; *xw = xx; hit = true; }
     }
     fclose(f);
     return hit;
 }
-void plan_cache_store(uint64_t key, const sgpu_op *op, int v, int lanes, int xw, float ms, int rv = -1, int rlanes = 0, float rms = 0) {
+// the runner-up as the log and the cache line's comment show it: "lanes" of an x-window candidate are its rows per workgroup
+int shown_lanes(const Candidate &c) { return c.xwin_rows ? c.xwin_rows : c.lanes; }
+void plan_cache_store(uint64_t key, const sgpu_op *op, const Candidate &c, float ms, const Candidate &ru, float rms) {     // (ru.form < 0: no runner-up)
     const std::string path = plan_cache_path();
     if (path.empty()) return;
     char line[256];
-    int n = snprintf(line, sizeof line, "%016llx\t%d\t%d\t%d\t%.4f\t# %d rows %lld nnz", (unsigned long long)key, v, lanes, xw, ms, op->M, (long long)op->loc.nnz);
-    if (rv >= 0) n += snprintf(line + n, sizeof line - (size_t)n, "; %s %.4f ms; runner-up %s with %d lanes %.4f ms", VARIANT_NAMES[v], ms, VARIANT_NAMES[rv], rlanes, rms);   // (the lookup reads the first four fields: variant, lanes, x-window rows)
+    int n = snprintf(line, sizeof line, "%016llx\t%d\t%d\t%d\t%.4f\t# %d rows %lld nnz", (unsigned long long)key, c.form, c.lanes, c.xwin_rows, ms, op->M, (long long)op->loc.nnz);
+    if (ru.form >= 0) n += snprintf(line + n, sizeof line - (size_t)n, "; %s %.4f ms; runner-up %s with %d lanes %.4f ms", FORM_NAMES[c.form], ms, FORM_NAMES[ru.form], shown_lanes(ru), rms);   // (the lookup reads the first four fields: variant, lanes, x-window rows)
     n += snprintf(line + n, sizeof line - (size_t)n, "\n");
     const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0644);    // one write() of one short line: appends of concurrent ranks do not interleave
     if (fd < 0) return;
@@ -2762,8 +2743,6 @@ void finish_plan(sgpu_op *op, int bv) {
         std::vector<double>().swap(op->h_val_all);
     }
 }
-// does the form add a row's products one after the other in column order (the reference's sum, whatever else is tuned)?
-bool sequential_sum(int v, int lanes) { return v == 9 || v == 11 || v == 13 || v == 14 || v == 15 || v == 17 || (lanes == 1 && (v == 0 || v == 1 || v == 3 || v == 4 || v == 7 || v == 8)); }
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 } // namespace
 } // extern "C++"
@@ -2807,22 +2786,22 @@ int sgpu_op_autotune(sgpu_op *op) {
     //   16 KiB tiles; a few hundred entries -- column order inside 32 KiB tiles, 16-bit columns on either tile; a thousand and
     //   more -- x in LDS, the wave-streamed kernel, 16-bit or 32-bit columns on tiles
     std::vector<int> variants, xwin_rows;
-    bool sell_like = false;
+    bool sell_like = false, ok = false;
     if (!std::getenv("SAENA_NO_SELL") && (all || avg_row <= 160.0)) {                                 // even rows: a lane per row
         CHK(build_sell_values(op->loc));                                                             // (on the device, from the CSR values: round 4)
         if (op->loc.sv.sl_vals) {
             if (!std::getenv("SAENA_NO_SELLP")) {                                                    // rows that repeat a few patterns: no column stream
-                CHK(build_sellp(op->loc));
-                if (op->loc.sp.sp_ok) variants.push_back(11);
+                CHK(build_form(op, F_SELLP, &ok));
+                if (ok) variants.push_back(F_SELLP);
                 // ... and the values as 8-bit codes into a dictionary per workgroup (operators of at most VI_MAX distinct values per
                 // 256 rows: the constant-coefficient stencil levels and their transfers): 1 B per entry instead of 8.  Offered where the
                 // values are more than the eight XCDs' L2 (32 MiB) hold from one launch to the next -- the bytes it saves come from the
                 // Infinity Cache or HBM; below that it was not measured and the plan stays as it was (128^3 fine level: 111 MB)
                 if (op->loc.sp.sp_ok && !op->loc.sp.sp_wide && 8 * op->loc.nnz > ((int64_t)32 << 20) && !std::getenv("SAENA_NO_VALUE_INDEX")) {
-                    CHK(build_vidx(op->loc));
-                    if (op->loc.vi.vi_ok) variants.push_back(17);
+                    CHK(build_form(op, F_VIDX, &ok));
+                    if (ok) variants.push_back(F_VIDX);
                     // ... and the same form with x in LDS windows (k_vidxw), a candidate of its own per workgroup size kept
-                    if (op->loc.vi.vi_ok && !std::getenv("SAENA_NO_X_WINDOWS"))
+                    if (ok && !std::getenv("SAENA_NO_X_WINDOWS"))
                         for (int k : XWIN_CANDIDATES) { CHK(build_xwin(op->loc, k)); if (op->loc.vw[k].ok) xwin_rows.push_back(256 << k); }
                 }
                 // ... and a lane per two rows: half the gathers.  With a table per workgroup (sp_wide: the 68-entry level) it wins on the
@@ -2831,66 +2810,66 @@ int sgpu_op_autotune(sgpu_op *op) {
                 // milliseconds, but allocating and FREEING 4.5 GB costs 0.2 s of the plan and the form lost again on 256^3 -- 942 against
                 // k_sellpx's 888 us: the limit stays)
                 if (op->loc.sp.sp_ok && (!op->loc.sp.sp_wide || op->loc.sp_bytes <= ((int64_t)1 << 30)) && !std::getenv("SAENA_NO_SELLP2")) {
-                    CHK(build_sellp2(op->loc, op->h_val_all));
-                    if (op->loc.sp2.sp2_ok) variants.push_back(14);
+                    CHK(build_form(op, F_SELLP2, &ok));
+                    if (ok) variants.push_back(F_SELLP2);
                 }
                 if (op->loc.sp.sp_ok && avg_row >= 16.0 && !std::getenv("SAENA_NO_SELLPX")) {                 // ... with x in LDS windows: where a row gathers dozens of entries
-                    CHK(build_sellpx(op->loc));
-                    if (op->loc.spx.spx_ok) variants.push_back(15);
+                    CHK(build_form(op, F_SELLPX, &ok));
+                    if (ok) variants.push_back(F_SELLPX);
                 }
                 if (op->loc.sp.sp_ok && std::getenv("SAENA_ROW_TEMPLATES") && !op->h_val_all.empty()) {     // OPT-IN: rows that also repeat their values
-                    CHK(build_rowt(op->loc, op->h_val_all));
-                    if (op->loc.rt.rt_ok) variants.push_back(13);
+                    CHK(build_form(op, F_ROWT, &ok));
+                    if (ok) variants.push_back(F_ROWT);
                 }
             }
             // k_sell itself (10 B per entry: the same values + 16-bit column codes, which cost a host pass over the entries and 2 B per
             // entry of upload) only where the rows follow no patterns -- it never beat k_sellp on an operator that has them (8 B per
             // entry, the same structure: 128^3 level 1 137.8 against 119.3 us, profiles/r03_sellp_wide_l1_128.log)
             if (!op->loc.sp.sp_ok || op->loc.sp.sp_rbase || all) {             // (... and next to a rowbase table: the 4 B per row it adds are a fifth of what the codes cost on 6-entry rows)
-                CHK(build_sell(op->loc, op->h_val_all));
-                if (op->loc.sl_ok) variants.push_back(9);
+                CHK(build_form(op, F_SELL, &ok));
+                if (ok) variants.push_back(F_SELL);
             }
             sell_like = op->loc.sp.sp_ok || (op->loc.sl_ok && !op->loc.sv.sl_sorted);         // (sorted slices: one more candidate next to the tile kernels)
         }
     }
     const double t_sell = now_s();
     const bool short_rows = sell_like && avg_row <= 128.0 && !all;
-    for (int k = 0; k < 2; ++k) {
+    for (int f : {F_CC16_16, F_CC16_32}) {
         // (round 4) an operator whose rows follow patterns runs at 8 B per entry; the tile kernels' 10 B per entry never came within 15 % of
         // it (256^3 L0 343 against 277 us, L1 1 190-1 270 against 890): not built, not timed, not freed
         if (op->loc.sp.sp_ok && !all) continue;
-        if (k == 1 && (short_rows || avg_row < 16.0) && !all) continue;                              // 32 KiB tiles never won on the shortest rows (at 18 entries per
+        if (f == F_CC16_32 && (short_rows || avg_row < 16.0) && !all) continue;                              // 32 KiB tiles never won on the shortest rows (at 18 entries per
                                                                                                      // row -- P1 of 256^3 -- they do: 361 against 385 us, profiles/r03_transfers_sell_padding.log)
-        CHK(build_cc16(op->loc, k));
-        if (op->loc.cc[k].ok) variants.push_back(3 + k);
+        CHK(build_form(op, f, &ok));
+        if (ok) variants.push_back(f);
     }
     const double t_cc = now_s();
     if (!short_rows) {
-        if (!op->loc.cc[0].ok || avg_row >= 256.0 || all) variants.push_back(0);                     // 32-bit columns: where 16-bit ones do not apply, and on long rows
-        if (!op->loc.cc[1].ok || avg_row >= 256.0 || all) variants.push_back(1);
+        if (!op->loc.cc[0].ok || avg_row >= 256.0 || all) variants.push_back(F_STREAM16);                   // 32-bit columns: where 16-bit ones do not apply, and on long rows
+        if (!op->loc.cc[1].ok || avg_row >= 256.0 || all) variants.push_back(F_STREAM32);
     }
-    variants.push_back(2);                                                                           // vector CSR: no build
-    if (op->loc.nnz >= 256 * (int64_t)std::max(1, op->loc.nrows)) variants.push_back(6);             // long rows: the wave-streamed kernel
+    variants.push_back(F_VECTOR);                                                                // vector CSR: no build
+    if (op->loc.nnz >= 256 * (int64_t)std::max(1, op->loc.nrows)) variants.push_back(F_WAVE);        // long rows: the wave-streamed kernel
     // x in LDS: long rows over few columns; and (round 4) IRREGULAR operators of a few dozen entries per row -- no sliced-ELLPACK form
     // (uneven rows), random columns inside a window: the tile kernels' gathers are what bounds them (configs[4] at 1 M rows: 134 us
     // against 111 us with x in LDS, 4 rows per group step below that)
     const bool irregular_short = !sell_like && avg_row >= 12.0;
     if ((op->loc.nnz >= 48 * (int64_t)std::max(1, op->loc.nrows) || irregular_short) && !std::getenv("SAENA_NO_XLDS") && (!short_rows)) {
-        CHK(build_xlds(op->loc));
-        if (op->loc.xlp.xl_ok && op->loc.xl_piece >= 24.0) variants.push_back(10);
-        if (op->loc.xlp.xl_ok && op->loc.xl_piece >= 8.0 && op->loc.xl_piece < 160.0 && !std::getenv("SAENA_NO_XLDSR")) variants.push_back(16);   // short pieces: four rows per group step
+        CHK(build_form(op, F_XLDS, &ok));
+        if (ok && op->loc.xl_piece >= 24.0) variants.push_back(F_XLDS);
+        if (ok && op->loc.xl_piece >= 8.0 && op->loc.xl_piece < 160.0 && !std::getenv("SAENA_NO_XLDSR")) variants.push_back(F_XLDSR);   // short pieces: four rows per group step
     }
     // (on the transfers it does not pay: P1 of 256^3, 18 entries per row, 504 us against 350; P2 ties; R2 165 against 156 us,
     //  profiles/r03_sellx_steps.log)
     if (op->loc.xlp.xl_ok && !op->h_val_all.empty() && avg_row >= 96.0 && avg_row <= 1024.0 && !std::getenv("SAENA_NO_SELLX")) {
-        CHK(build_sellx(op->loc, op->h_val_all));                                                    // a few hundred entries per row: a lane per row piece, x in LDS
-        if (op->loc.sx.sx_ok) variants.push_back(12);
+        CHK(build_form(op, F_SELLX, &ok));                                                           // a few hundred entries per row: a lane per row piece, x in LDS
+        if (ok) variants.push_back(F_SELLX);
     }
     const double t_xl = now_s();
     // (k_csr_cm, 12 B per entry, is built further down -- only where the candidates timed so far leave it a chance)
     const double t_cm = now_s();      // (the builds end here; k_csr_cm's is timed separately below)
-    if (!op->has_remote && !op->loc.h_val.empty() && (double)op->loc.nnz >= 0.5 * (double)op->loc.nrows * op->loc.ncols && build_dense(op->loc) == SGPU_OK)
-        variants.push_back(5);                         // at least half full: the dense form moves fewer bytes
+    if (!op->has_remote && !op->loc.h_val.empty() && (double)op->loc.nnz >= 0.5 * (double)op->loc.nrows * op->loc.ncols && build_form(op, F_DENSE, &ok) == SGPU_OK)
+        variants.push_back(F_DENSE);                        // at least half full: the dense form moves fewer bytes
     // Only the LOCAL part is timed, without the halo exchange: ranks may end up with different candidate
     // lists (a rank's blocks may be too scattered for 16-bit columns), so no collective may run in here.
     EpiArgs e; e.rhs = r; e.inv_diag = op->inv_diag; e.u = x; e.c0 = JACOBI_OMEGA_REF;
@@ -2908,14 +2887,13 @@ int sgpu_op_autotune(sgpu_op *op) {
         for (int g : {gx / 2, gx, gx * 2}) if (g >= 4 && g <= 64) lanes_x.push_back(g);
     }
     const std::vector<int> lanes_r = {8, 16, 32};         // k_csr_xldsr: lanes per group of four rows
-    std::vector<std::pair<int, int>> cands;
+    std::vector<Candidate> cands;
     for (int v : variants)
-        for (int gl : (v == 10 ? lanes_x : v == 16 ? lanes_r : lanes)) {
-            if ((v == 9 || v == 11 || v == 12 || v == 13 || v == 14 || v == 15 || v == 17) && gl != lanes.front()) continue;      // a lane per row (piece) whatever the setting
-            if (v == 5 && gl != lanes.front()) continue;                   // one wave per dense row likewise
-            cands.push_back({v, gl});
+        for (int gl : (v == F_XLDS ? lanes_x : v == F_XLDSR ? lanes_r : lanes)) {
+            if (one_candidate(v) && gl != lanes.front()) continue;         // a lane per row (piece), a wave per dense row: whatever the setting
+            cands.push_back({v, gl, 0});
         }
-    for (int rows : xwin_rows) cands.push_back({17, rows});      // (variant 17, "lanes" >= 256: the x-window mode at that many rows per workgroup)
+    for (int rows : xwin_rows) cands.push_back({F_VIDX, lanes.front(), rows});
     {                                                    // a few milliseconds of the current plan first: a process's first kernels run at ramping clocks
         float ms = 0;
         for (int burst = 0; burst < 8 && ms < 2.0f; ++burst) {
@@ -2928,8 +2906,8 @@ int sgpu_op_autotune(sgpu_op *op) {
             ms += t;
         }
     }
-    auto sample = [&](int v, int gl, int reps, float *ms) -> int {
-        op->loc.variant = v; op->loc.lanes = gl >= 256 ? lanes.front() : gl; op->loc.vw_rows = gl >= 256 ? gl : 0;
+    auto sample = [&](const Candidate &c, int reps, float *ms) -> int {
+        op->loc.variant = c.form; op->loc.lanes = c.lanes; op->loc.vw_rows = c.xwin_rows;
         HIPCHK(hipEventRecord(e0, g.cs));
         for (int i = 0; i < reps; ++i) CHK(launch_part(op->loc, epi, x, y, e));
         HIPCHK(hipEventRecord(e1, g.cs));
@@ -2941,9 +2919,9 @@ int sgpu_op_autotune(sgpu_op *op) {
     // round 0 warms up (clocks, caches, code objects) and estimates; round 1 measures the candidates within 30 % of the best
     // estimate (>= 1 ms each); the deciding rounds then time the ones within 8 % of the fastest three more times, interleaved, >= 2 ms
     // each, every candidate keeping its best time: single 1 ms samples picked losers now and then
-    std::map<std::pair<int, int>, float> est, seen;
+    std::map<Candidate, float> est, seen;
     float best_est = 1e30f;
-    for (const auto &c : cands) { float ms = 0; CHK(sample(c.first, c.second, 2, &ms)); est[c] = ms; best_est = std::min(best_est, ms); }
+    for (const auto &c : cands) { float ms = 0; CHK(sample(c, 2, &ms)); est[c] = ms; best_est = std::min(best_est, ms); }
     // rows of a few hundred entries: column order inside the block (k_csr_cm) -- a host pass over the entries and a 12 B per entry upload
     // (0.6-0.9 s on the 150-200 M entry operators of 256^3).  Its best rate anywhere was 5.0 TB/s of stored bytes (256^3 L2), so it is
     // built only where the forms timed so far are slower than its bytes at 5.2 TB/s (R1 of 256^3: 438 us against a bound of 351 -> built,
@@ -2951,12 +2929,12 @@ int sgpu_op_autotune(sgpu_op *op) {
     const double t_cm0 = now_s();
     if (avg_row >= 96.0 && avg_row <= 768.0 && !std::getenv("SAENA_NO_CM") &&
         (all || (double)best_est > 12.0 * (double)op->loc.nnz / 5.2e9)) {
-        CHK(build_cm(op->loc, 1, op->h_val_all));
-        if (op->loc.cm[1].ok)
+        CHK(build_form(op, F_CM32, &ok));
+        if (ok)
             for (int gl : lanes) {
-                const std::pair<int, int> c{8, gl};
+                const Candidate c{F_CM32, gl, 0};
                 float ms = 0;
-                CHK(sample(c.first, c.second, 3, &ms));
+                CHK(sample(c, 3, &ms));
                 cands.push_back(c); est[c] = ms; best_est = std::min(best_est, ms);
             }
     }
@@ -2966,7 +2944,7 @@ int sgpu_op_autotune(sgpu_op *op) {
             if (est[c] > 1.3f * best_est && !all) continue;
             const int reps = std::min(48, std::max(3, (int)(1.0f / std::max(est[c], 1e-3f)) + 1));   // a measuring sample lasts >= 1 ms
             float ms = 0;
-            CHK(sample(c.first, c.second, reps, &ms));
+            CHK(sample(c, reps, &ms));
             auto it = seen.find(c);
             if (it == seen.end()) seen[c] = ms; else it->second = std::min(it->second, ms);
         }
@@ -2976,53 +2954,28 @@ int sgpu_op_autotune(sgpu_op *op) {
     {
         float lead = 1e30f;
         for (const auto &kv : seen) lead = std::min(lead, kv.second);
-        std::vector<std::pair<int, int>> close;
+        std::vector<Candidate> close;
         for (const auto &kv : seen) if (kv.second <= 1.08f * lead) close.push_back(kv.first);
         if (close.size() > 1)
             for (int trial = 0; trial < 3; ++trial)
                 for (const auto &c : close) {
                     const int reps = std::min(64, std::max(3, (int)(2.0f / std::max(seen[c], 1e-3f)) + 1));
                     float ms = 0;
-                    CHK(sample(c.first, c.second, reps, &ms));
+                    CHK(sample(c, reps, &ms));
                     seen[c] = std::min(seen[c], ms);
                 }
     }
-    float best = 1e30f;
-    for (const auto &kv : seen) if (kv.first.first != 7 && kv.first.first != 8) best = std::min(best, kv.second);
-    float best_cm = 1e30f;
-    for (const auto &kv : seen) if (kv.first.first == 7 || kv.first.first == 8) best_cm = std::min(best_cm, kv.second);
-    const bool cm_wins = best_cm < 0.95f * best;          // the column-major copy costs 2 B/nnz more: it has to win clearly
-    const float bar = 1.03f * (cm_wins ? best_cm : best);
-    // Inside the 3 % band: forms with the reference's sequential row sum first.  They are bit-identical to ONE ANOTHER (k_sell, k_sellp,
-    // k_sellp2, k_sellpx, the tile kernels at one lane per row), so among them the choice cannot move a result and simply goes to the
-    // fastest; between forms whose sums differ it goes by the fixed (variant, lanes) order, so that noise does not move a result.
-    int bv = guard.v, bg = guard.l, brank = 1 << 30;
-    float bms = 0;
-    int rv = -1, rg = 0; float rms = 0;                   // runner-up (what the cache line records next to the choice)
-    for (const auto &kv : seen) {                         // std::map: ascending (variant, lanes)
-        const int v = kv.first.first, gl = kv.first.second;
-        if ((v == 7 || v == 8) != cm_wins || kv.second > bar) continue;
-        const int rank = sequential_sum(v, gl) ? 0 : 1;
-        if (rank < brank || (rank == 0 && brank == 0 && kv.second < bms)) { brank = rank; bv = v; bg = gl; bms = kv.second; }
-    }
-    if (bv == 17 && bg >= 256) {                          // the x-window mode has to win clearly: direct gathers inside the band come first
-        const auto it = seen.find({17, lanes.front()});
-        if (it != seen.end() && it->second <= bar) { bg = it->first.second; bms = it->second; }
-    }
-    for (const auto &kv : seen)
-        if ((kv.first.first != bv || kv.first.second != bg) && (rv < 0 || kv.second < rms)) { rv = kv.first.first; rg = kv.first.second; rms = kv.second; }
+    const PlanChoice c = choose_plan(seen, Candidate{guard.v, guard.l, guard.xw}, lanes.front());
     guard.armed = false;
-    const int bxw = bg >= 256 ? bg : 0;
-    if (bxw) bg = lanes.front();
-    op->loc.variant = bv; op->loc.lanes = bg; op->loc.vw_rows = bxw;
+    op->loc.variant = c.best.form; op->loc.lanes = c.best.lanes; op->loc.vw_rows = c.best.xwin_rows;
     const double t_fin0 = now_s();
-    finish_plan(op, bv);
+    finish_plan(op, c.best.form);
     const double t_fin1 = now_s();
-    plan_cache_store(key, op, bv, bg, bxw, bms, rv, rg, rms);
+    plan_cache_store(key, op, c.best, c.ms, c.runner_up, c.runner_up_ms);
     if (verbose)
         fprintf(stderr, "[sgpu] autotune of %d rows x %lld nnz (%.1f per row): %zu candidates, variant %d with %d lanes (x windows: %d rows per workgroup) at %.1f us (fastest %.1f us; runner-up variant %d with %d lanes at %.1f us); sliced ELLPACK %.2f s, "
-                        "16-bit columns %.2f s, x in LDS %.2f s, column order %.2f s, timing %.2f s (of which freeing the forms that lost %.2f s)\n", op->M, (long long)op->loc.nnz, avg_row, cands.size(), bv, bg, bxw, bms * 1e3,
-                (cm_wins ? best_cm : best) * 1e3, rv, rg, rms * 1e3, t_sell - t_begin, t_cc - t_sell, t_xl - t_cc, t_cm1 - t_cm0, now_s() - t_cm - (t_cm1 - t_cm0), t_fin1 - t_fin0);
+                        "16-bit columns %.2f s, x in LDS %.2f s, column order %.2f s, timing %.2f s (of which freeing the forms that lost %.2f s)\n", op->M, (long long)op->loc.nnz, avg_row, cands.size(), c.best.form, c.best.lanes, c.best.xwin_rows, c.ms * 1e3,
+                c.fastest * 1e3, c.runner_up.form, shown_lanes(c.runner_up), c.runner_up_ms * 1e3, t_sell - t_begin, t_cc - t_sell, t_xl - t_cc, t_cm1 - t_cm0, now_s() - t_cm - (t_cm1 - t_cm0), t_fin1 - t_fin0);
     return SGPU_OK;
 }
 
@@ -3119,7 +3072,7 @@ int sgpu_debug_gather_probe(sgpu_op *op, int mode, const value_t *x, int reps, f
 int sgpu_debug_block_plan(const sgpu_op *op, int big, long *out) {
     if (!op || !out) return fail(SGPU_ERR_ARG, "null argument");
     const CsrPart &P = op->loc;
-    if (big == 2) {                                            // the x-in-LDS plan (variants 10, 12, 16)
+    if (big == 2) {                                            // the x-in-LDS plan (is_xlds_chunk)
         if (!P.xlp.xl_ok) return fail(SGPU_ERR_STATE, "the x-in-LDS plan was not built");
         long rmx = 0;
         for (size_t b = 0; b + 1 < P.xl_blk_h.size(); ++b) rmx = std::max(rmx, (long)(P.xl_blk_h[b + 1] - P.xl_blk_h[b]));
@@ -3457,7 +3410,7 @@ int vcycle_level(sgpu_amg *h, int l, double *u, double *alt, const double *rhs, 
     const bool no_rsweep = std::getenv("SAENA_NO_RSWEEP") != nullptr;       // (read per call: a captured graph keeps what it was captured with)
     sgpu_op *An = h->A[l + 1];
     const bool fuse = !no_rsweep && !g.multi() && h->prm.preSmooth > 0 && l + 1 < h->nlevels - 1 && An->inv_diag && An->M > 0 &&
-                      !h->R[l]->has_remote && h->R[l]->loc.variant != 5;
+                      !h->R[l]->has_remote && !is_dense(h->R[l]->loc.variant);
     if (fuse) {
         EpiArgs e; e.inv_diag = An->inv_diag; e.y2 = h->alt[l + 1];
         if (h->prm.smoother == 0) { e.c0 = h->prm.jacobi_omega != 0.0 ? h->prm.jacobi_omega : JACOBI_OMEGA_REF; e.c1 = 0.0; }

@@ -1278,7 +1278,7 @@ def test_plan_time_builds_on_the_device_equal_the_host_builds(capi, name, monkey
 def test_plan_cache_honours_every_variant_the_autotune_can_store(capi, tmp_path, monkeypatch):
     """Round-3 advisor finding: the lookup accepted variants 0..14 while the autotune can pick and store 15 (k_sellpx), so a cached
     k_sellpx line was never honoured and every process tuned again and appended another line.  Lookup, store and set_variant
-    now share one bound (MAX_VARIANT): a cached line naming the highest variant is taken without a sweep and without a new line."""
+    now share one bound (F_COUNT in forms.h): a cached line naming the highest variant is taken without a sweep and without a new line."""
     cache = tmp_path / "plans.tsv"
     monkeypatch.setenv("SAENA_PLAN_CACHE", str(cache))
     M = 16384

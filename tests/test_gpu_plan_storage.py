@@ -2,7 +2,8 @@
 
 The local part of an operator stores its kernel forms in groups of device arrays (sgpu_debug_op_storage names them, one bit each);
 when the plan settles on a variant (sgpu_op_autotune), every group outside that variant's keep-set is freed.  The sets below restate,
-by variant, the table the library keeps in ONE place (plan_keeps in sgpu_runtime.hip).  The operators are those of test_gpu_forms.py
+by variant, the table the library keeps in ONE place (plan_keeps in forms.h; the sets live in tests/form_table.py, which
+tests/test_forms_header.py holds the header to on the host).  The operators are those of test_gpu_forms.py
 with fewer than 200 000 entries: their autotune goes straight to the clean-up for the variant in use.
 
 The library counts the bytes of every device and pinned array it owns (vectors from sgpu_vec_alloc are the caller's and are not
@@ -12,27 +13,13 @@ import numpy as np
 import pytest
 
 from tests import inputs, util
+from tests.form_table import KEEPS, XWIN
 from tests.test_gpu_forms import BY_KEY, FORMS, OPERATORS, _hier, bits, make_gpu, name_matches, oracle_op, problem
 from tests.test_gpu_vcycle import build
 
 pytestmark = pytest.mark.gpu
 
 AUTOTUNE_SWEEPS_FROM = 200000                # entries from which sgpu_op_autotune times candidates instead of keeping the variant in use
-XWIN = {256: "xwin256", 512: "xwin512", 1024: "xwin1024"}
-# what the plan that settles on a variant keeps (csr: always)
-KEEPS = {
-    0: set(), 1: set(), 2: set(), 6: set(),
-    3: {"cc0"}, 4: {"cc1"}, 5: {"dense"},
-    7: {"cc0", "cm0"}, 8: {"cc1", "cm1"},
-    9: {"sell_values", "sell_columns"},
-    10: {"xlds_plan", "xlds_columns"}, 16: {"xlds_plan", "xlds_columns"},
-    11: {"sell_values", "sellp"},
-    12: {"xlds_plan", "sellx"},
-    13: {"rowt"},
-    14: {"sellp", "sellp2"},
-    15: {"sell_values", "sellp", "sellpx"},
-    17: {"sellp", "vidx"},
-}
 SGPU_ERR_STATE = -4
 
 
