@@ -243,7 +243,8 @@ public:
     int solve(value_t *&u, saena::options *opts);
     int solve_pCG(value_t *&u, saena::options *opts, bool print_info = true);
     int solve_CG(value_t *&u, saena::options *opts);          // CG without the multigrid preconditioner
-    // nrhs = 2, 4 or 8 right-hand sides through one pass over every operator (one rank): rhs_local and u are column-major,
+    // nrhs = 2, 4 or 8 right-hand sides through one pass over every operator (any number of ranks: the K columns of a
+    // halo cross in one exchange): rhs_local and u are column-major,
     // size x nrhs (column j at [j * size]), partitioned like A; u is allocated (size * nrhs) when null.  Every column is solved
     // as solve_pCG solves it alone, with its own iteration count and history; returns 1 if any column did not converge
     int set_rhs_block(const value_t *rhs_local, index_t size, int nrhs);

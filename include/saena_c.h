@@ -171,7 +171,8 @@ sgpu_op  *saena_amg_device_op(saena_amg_h *S, int level, int which);      /* [GP
 /* [GPU] saena::amg::solve / solve_pCG (saena.hpp:220,224) on HOST slices of this rank: rhs in, u out */
 int   saena_amg_solve(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int *iters, value_t *res_hist, int hist_cap);
 int   saena_amg_solve_pCG(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int *iters, value_t *res_hist, int hist_cap);
-/* [GPU] solve_pCG for K = 2, 4 or 8 right-hand sides through one pass over every operator (sgpu_solve_pCG_block; one rank):
+/* [GPU] solve_pCG for K = 2, 4 or 8 right-hand sides through one pass over every operator (sgpu_solve_pCG_block; any number of ranks:
+ * the K columns of every halo cross in one exchange, the dots are summed over the ranks):
  * rhs_host / u_host are column-major n x K (column j at [j*n]), iters[K], res_hist[K][hist_cap] */
 int   saena_amg_solve_pCG_block(saena_amg_h *S, const value_t *rhs_host, value_t *u_host, int K, int *iters, value_t *res_hist, int hist_cap);
 /* [GPU] restarted flexible GMRES for operators that are not symmetric positive definite (sgpu_solve_FGMRES; one rank): restart in

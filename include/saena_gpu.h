@@ -259,7 +259,11 @@ int sgpu_coarsest_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters)
  * A block vector of K columns over n rows is ONE device allocation of n*K doubles (sgpu_vec_alloc) with the columns
  * interleaved, X[i*K + j]; K is 2, 4 or 8, anything else is SGPU_ERR_ARG on every entry point below.  Outside the
  * library blocks travel column-major (n x K, column j at cols[j*n]); pack / unpack convert, device to device.
- * One rank and fp64 only: a context with nranks > 1, or an operator with a remote part, gets SGPU_ERR_ARG.
+ * fp64 only.  The block apply, V-cycle and pCG run on any number of ranks: under a communicator (RCCL) or a host transport
+ * the K columns of an operator's halo travel through ONE exchange (the scalar plan with every segment K times as long, on
+ * the wire type halo_fp32 names), and the dots of the pCG are summed over the ranks.  An operator with a remote part in a
+ * context that has neither is refused with SGPU_ERR_ARG ("remote part"), as is a hierarchy whose coarsest level is
+ * row-partitioned over the ranks.  pack / unpack are local.
  * Every column of a block result is what the scalar entry point computes for that column alone: bit for bit the
  * reference's sequential row sum at one lane per row, within the tile kernels' bounds above that; column j never
  * reads column j'.  None of this touches the scalar path (no plan, autotune choice, plan-cache entry or scalar graph):

@@ -21,6 +21,13 @@ extern "C" {
  * applies use the remote part without any exchange.  Tests route the buffers between operators on the host. */
 int sgpu_debug_pack(sgpu_op *op, const value_t *v, value_t *send_host);
 int sgpu_debug_inject_halo(sgpu_op *op, const value_t *recv_host);
+/* Their block twins (K = 2, 4, 8 columns; X: a device block vector X[i * K + j] over the operator's columns).  The wire layout of
+ * a block halo: segment i of the send buffer is sendCount[i] * K values at sendDispl[i] * K, send[t * K + j] = X[vIndex[t] * K + j];
+ * the receive buffer is a block vector over the halo positions, recv[p * K + j].  pack_block downloads the vIndexSize * K doubles of
+ * the send buffer (rounded through float on an fp32-wire operator, as sgpu_debug_pack's); inject_halo_block uploads recvSize * K
+ * doubles and makes the following block applies WITH THIS K run the interior and boundary kernels on one stream, no exchange. */
+int sgpu_debug_pack_block(sgpu_op *op, const value_t *X, int K, value_t *send_host);
+int sgpu_debug_inject_halo_block(sgpu_op *op, int K, const value_t *recv_host);
 /* An operator with remote entries applied in a context that has neither a communicator nor a host transport nor
  * an injected halo is an error (SGPU_ERR_STATE): the result would silently miss the remote part.  allow != 0
  * lifts that for this operator: only its local part is applied (plan/launch tests whose numbers mean nothing). */

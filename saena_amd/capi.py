@@ -83,6 +83,8 @@ SYMBOLS = {
     "sgpu_debug_block_plan": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_long)]),
     "sgpu_debug_stream_ceiling": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "sgpu_debug_inject_halo": (C.c_int, [_VP, _PD]),
+    "sgpu_debug_pack_block": (C.c_int, [_VP, _VP, C.c_int, _PD]),
+    "sgpu_debug_inject_halo_block": (C.c_int, [_VP, C.c_int, _PD]),
     "sgpu_spmv_host": (C.c_int, [_VP, _PD, _PD]),
     "sgpu_jacobi_host": (C.c_int, [_VP, C.c_int, C.c_double, _PD, _PD]),
     "sgpu_chebyshev_host": (C.c_int, [_VP, C.c_int, C.c_double, _PD, _PD]),
@@ -490,6 +492,17 @@ class Operator:
     def debug_inject_halo(self, recv):
         recv = _ad(recv)
         check(lib().sgpu_debug_inject_halo(self.h, recv.ctypes.data_as(_PD)))
+
+    def debug_pack_block(self, X, n_send):
+        """-> (n_send, K): the block send buffer after the pack kernel, row t = the K columns of X at vIndex[t]"""
+        out = np.empty((n_send, X.K))
+        check(lib().sgpu_debug_pack_block(self.h, X.ptr, X.K, out.ctypes.data_as(_PD)))
+        return out
+
+    def debug_inject_halo_block(self, recv):
+        """recv: (recvSize, K), row p = the K columns at halo position p"""
+        recv = _ad(recv)
+        check(lib().sgpu_debug_inject_halo_block(self.h, recv.shape[1], recv.ctypes.data_as(_PD)))
 
     def spmv_host(self, v):
         v = _ad(v)

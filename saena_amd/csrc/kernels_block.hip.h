@@ -12,6 +12,9 @@
 //     entries l, l + G, ... of the row and combines the lanes with group_sum -- the orders of k_csr_stream;
 //   * column j's arithmetic never reads column j': a NaN in one column stays there, and the K instantiations perform the
 //     same operations per column, so a column's bits do not depend on K or on its position in the block;
+//   * an operator with a remote part: the rows that own remote entries are masked out of this launch (BlockArgs::skip) and
+//     computed whole by k_csr_boundary_block once the block halo -- K columns through one exchange, packed by k_pack_block --
+//     has arrived;
 //   * the epilogues are those of epilogue<> (kernels.hip.h) per column; inv_diag is shared by the columns, rhs / u / d / y
 //     are block vectors read and written 16 B at a time.
 #pragma once
@@ -32,6 +35,7 @@ struct BlockArgs {
     const double *u;         // block (the smoother's input iterate)
     double       *d;         // block (Chebyshev direction)
     double        c0, c1;
+    const unsigned *skip;    // bitmask of rows this launch must NOT write (boundary rows, owned by k_csr_boundary_block), or nullptr
 };
 
 constexpr int BLK_CH = CAP + 8;   // entries staged per pass: a row block's CAP entries plus the alignment slack of its start
@@ -70,11 +74,9 @@ __device__ __forceinline__ void block_epilogue2(const BlockArgs &a, int r, int h
     *reinterpret_cast<sk_d2v *>(a.y + o) = out;
 }
 
-// the G lanes of a row group hold their partial sums: combine them and write the row
+// every lane of a row group holds the row's K sums: the epilogue, a column pair per lane
 template <int K, int EPI, int G>
-__device__ __forceinline__ void block_finish_row(const BlockArgs &a, int r, int l, double (&acc)[K]) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) acc[j] = group_sum<G>(acc[j]);       // (every lane of the group ends with the sum)
+__device__ __forceinline__ void block_write_row(const BlockArgs &a, int r, int l, double (&acc)[K]) {
     if constexpr (G == 1) {
 #pragma unroll
         for (int h = 0; h < K / 2; ++h) block_epilogue2<K, EPI>(a, r, h, acc[2 * h], acc[2 * h + 1]);
@@ -83,6 +85,16 @@ __device__ __forceinline__ void block_finish_row(const BlockArgs &a, int r, int 
         for (int h = 0; h < K / 2; ++h)
             if (l == h) block_epilogue2<K, EPI>(a, r, h, acc[2 * h], acc[2 * h + 1]);
     }
+}
+
+// the G lanes of a row group hold their partial sums: combine them and write the row -- unless the launch's mask names it (a
+// boundary row: summed like any other, so the lanes stay in step, but its epilogue is the halo kernel's: EPI_SUB reads y)
+template <int K, int EPI, int G>
+__device__ __forceinline__ void block_finish_row(const BlockArgs &a, int r, int l, double (&acc)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = group_sum<G>(acc[j]);       // (every lane of the group ends with the sum)
+    if (a.skip && ((a.skip[r >> 5] >> (r & 31)) & 1u)) return;
+    block_write_row<K, EPI, G>(a, r, l, acc);
 }
 
 // entries k0 + m G (< k1) of the staged stream: acc[j] += val * x[col][j]
@@ -157,6 +169,91 @@ __global__ __launch_bounds__(BLOCK) void k_csr_block(const BlockArgs a) {
         }
     }
     if (g == 0) block_finish_row<K, EPI, G>(a, r0, l, acc);
+}
+
+// ---- boundary rows of a block apply: k_csr_boundary (kernels.hip.h) on K columns.  G lanes own one row that has remote entries: lane l
+// adds the local entries l, l + G, ... of the row (x + col * K), then its halo entries l, l + G, ... (halo + h_col * K: the receive
+// buffer is a block vector over the halo positions), into the K register accumulators of k_csr_block -- product rounded, then added;
+// group_sum, one epilogue.  G = 1: the reference's order, the local loop first and the remote contributions after it in ascending
+// receive position.  Rows are walked from global memory whatever their length: no LDS, no long-row path ----
+struct BlockBoundaryArgs {
+    BlockArgs     b;         // the local CSR (row_ptr / col / val), x and the epilogue operands; blk_row and skip unused
+    const int    *rows;      // [nrows] boundary rows, ascending
+    int           nrows;
+    const int    *h_ptr;     // [nrows+1] CSR over the halo positions, one row per boundary row
+    const int    *h_col;     // halo position
+    const double *h_val;
+    const double *halo;      // receive buffer (fp64 wire), [recvSize * K]
+    const float  *halo_f;    // receive buffer of the fp32 wire, or nullptr
+};
+
+typedef float sk_f2v __attribute__((ext_vector_type(2)));
+
+template <int K, int EPI, int G>
+__global__ __launch_bounds__(BLOCK) void k_csr_boundary_block(const BlockBoundaryArgs a) {
+    static_assert(K == 2 || K == 4 || K == 8, "K");
+    static_assert(G == 1 || G == 4 || G == 16 || G == 64, "G");
+    constexpr int RPB = BLOCK / G;
+    const int i = blockIdx.x * RPB + threadIdx.x / G, l = threadIdx.x % G;
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0.0;
+    int r = 0;
+    if (i < a.nrows) {
+        r = a.rows[i];
+        block_walk<K, G>(a.b.val, a.b.col, a.b.x, a.b.row_ptr[r] + l, a.b.row_ptr[r + 1], acc);
+        const int q1 = a.h_ptr[i + 1];
+        if (a.halo_f) {
+            for (int k = a.h_ptr[i] + l; k < q1; k += G) {
+                const double v = a.h_val[k];
+                const sk_f2v *xp = reinterpret_cast<const sk_f2v *>(a.halo_f + (size_t)a.h_col[k] * K);
+#pragma unroll
+                for (int h = 0; h < K / 2; ++h) {
+                    const sk_f2v xv = xp[h];
+                    acc[2 * h]     += v * (double)xv.x;
+                    acc[2 * h + 1] += v * (double)xv.y;
+                }
+            }
+        } else {
+            block_walk<K, G>(a.h_val, a.h_col, a.halo, a.h_ptr[i] + l, q1, acc);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = group_sum<G>(acc[j]);
+    if (i < a.nrows) block_write_row<K, EPI, G>(a.b, r, l, acc);
+}
+
+// ---- halo pack of a block vector: send[t * K + j] = X[vIndex[t] * K + j], one lane per column pair (a 16-byte load; a 16-byte
+// store, 8 bytes on the float wire).  as_float: the doubles rounded through float, as k_pack's (the test hook's send buffer on an
+// fp32-wire operator).  Segment i of the wire is sendCount[i] * K values at sendDispl[i] * K ----
+template <int K>
+__global__ __launch_bounds__(BLOCK) void k_pack_block(const double *__restrict__ X, const int *__restrict__ vIndex, double *__restrict__ send, int n, int as_float) {
+    constexpr int H = K / 2;
+    const size_t np = (size_t)n * H, stride = (size_t)gridDim.x * BLOCK;
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < np; i += stride) {
+        const size_t t = i / H, h = i % H;
+        sk_d2v v = *reinterpret_cast<const sk_d2v *>(X + (size_t)vIndex[t] * K + 2 * h);
+        if (as_float) { v.x = (double)(float)v.x; v.y = (double)(float)v.y; }
+        *reinterpret_cast<sk_d2v *>(send + t * K + 2 * h) = v;
+    }
+}
+template <int K>
+__global__ __launch_bounds__(BLOCK) void k_pack_block_f32(const double *__restrict__ X, const int *__restrict__ vIndex, float *__restrict__ send, int n) {
+    constexpr int H = K / 2;
+    const size_t np = (size_t)n * H, stride = (size_t)gridDim.x * BLOCK;
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < np; i += stride) {
+        const size_t t = i / H, h = i % H;
+        const sk_d2v v = *reinterpret_cast<const sk_d2v *>(X + (size_t)vIndex[t] * K + 2 * h);
+        sk_f2v f; f.x = (float)v.x; f.y = (float)v.y;
+        *reinterpret_cast<sk_f2v *>(send + t * K + 2 * h) = f;
+    }
+}
+
+// ---- the K dots of a block pCG after their sum over the ranks: dst[j] = src[j] on the columns of `active`; a frozen column's
+// scalar keeps its bits (an all-reduce in place would multiply a stale slot by the rank count) ----
+__global__ void k_copy_masked(const double *__restrict__ src, double *__restrict__ dst, int K, unsigned active) {
+    const int j = threadIdx.x;
+    if (j < K && ((active >> j) & 1u)) dst[j] = src[j];
 }
 
 // ---- column-major n x K  <->  block (device to device) ----

@@ -4,15 +4,30 @@
 // Nothing here touches the scalar path: no plan, no autotune choice, no plan-cache entry, no scalar graph.  The block kernel
 // reads the plain CSR arrays every operator keeps for its whole life (CsrPart::row_ptr / col / val and the 16 KiB row-block
 // plan blk_row); its own state is two lane counts and two lazily made buffers per K and operator, and an AmgBlock per (hierarchy, K).
+// Across ranks (a communicator or a host transport) the K columns of an operator's halo cross in ONE exchange: apply_block mirrors
+// apply()'s plain orderings with block halo buffers per K and operator, and the dots of the block pCG are summed over the ranks.
 namespace {
 
 uint64_t g_block_generation = 0;   // bumped by sgpu_op_set_block_lanes: captured BLOCK V-cycles are stale (the scalar ones are not)
 
+int block_slot(int K) { return K == 2 ? 0 : K == 4 ? 1 : 2; }
+
+// K, and -- with an operator -- that its halo can be fetched: through the context's communicator or host transport, or from a block
+// halo a test injected for this K.  The same answer on every rank of a context (a refusal on one rank alone would leave the
+// others waiting in the exchange): K is the caller's on all of them, and a context with a transport refuses no operator here.
 int block_check(const sgpu_op *op, int K, const char *what) {
     if (K != 2 && K != 4 && K != 8) return fail(SGPU_ERR_ARG, "%s: a block holds 2, 4 or 8 columns (K = %d)", what, K);
-    if (g.nranks > 1 || g.multi()) return fail(SGPU_ERR_ARG, "%s: block entry points run on one rank only (this context has %d)", what, g.nranks);
+    if (op && (op->has_remote || op->recvSize) && !g.multi() && !op->injected_blk[block_slot(K)])
+        return fail(SGPU_ERR_ARG, "%s: the operator has a remote part (%d halo entries), and this context has neither a communicator nor a host transport "
+                    "and no block halo was injected for K = %d", what, op->recvSize, K);
+    return SGPU_OK;
+}
+// what stays on one rank (LOBPCG; FGMRES has gmres_check): no communicator, no host transport, no operator with a remote part
+int block_one_rank_check(const sgpu_op *op, int K, const char *what) {
+    CHK(block_check(nullptr, K, what));
+    if (g.nranks > 1 || g.multi()) return fail(SGPU_ERR_ARG, "%s: runs on one rank only (this context has %d)", what, g.nranks);
     if (op && (op->has_remote || op->recvSize))
-        return fail(SGPU_ERR_ARG, "%s: the operator has a remote part (%d halo entries); block entry points take single-rank operators only", what, op->recvSize);
+        return fail(SGPU_ERR_ARG, "%s: the operator has a remote part (%d halo entries); it takes single-rank operators only", what, op->recvSize);
     return SGPU_OK;
 }
 
@@ -31,22 +46,177 @@ BlockFn pick_block(int K, int epi, int G) {
         return sk::k_csr_block<KK(), E(), GG()>; }); }); });
 }
 
-// Y = epilogue(A X): one launch of k_csr_block over the operator's 16 KiB row-block plan
-int apply_block(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, int K) {
-    if (op->M == 0 || op->loc.nblk == 0) return SGPU_OK;
+using BlockBndFn = void (*)(const sk::BlockBoundaryArgs);
+BlockBndFn pick_block_bnd(int K, int epi, int G) {
+    return among<2, 4, 8>(K, [&](auto KK) { return per_epi_no_rsweep(epi, [&](auto E) { return among<1, 4, 16, 64>(G == 1 || G == 4 || G == 16 ? G : 64, [&](auto GG) -> BlockBndFn {
+        return sk::k_csr_boundary_block<KK(), E(), GG()>; }); }); });
+}
+
+int block_lanes_of(sgpu_op *op) {
     if (!op->block_lanes_auto) op->block_lanes_auto = block_auto_lanes(op);
-    const int G = op->block_lanes ? op->block_lanes : op->block_lanes_auto;
-    const BlockFn fn = pick_block(K, epi, G);
-    if (!fn) return fail(SGPU_ERR_ARG, "block apply: no kernel for epilogue %d", epi);   // a missing kernel is an error, never a fall-back
+    return op->block_lanes ? op->block_lanes : op->block_lanes_auto;
+}
+
+sk::BlockArgs block_args(const sgpu_op *op, const double *x, double *y, const EpiArgs &e) {
     sk::BlockArgs a;
     a.row_ptr = op->loc.csr.row_ptr; a.col = op->loc.csr.col; a.val = op->loc.csr.val; a.blk_row = op->loc.csr.blk_row; a.nblk = op->loc.nblk;
     a.x = x; a.y = y; a.rhs = e.rhs; a.inv_diag = e.inv_diag; a.u = e.u; a.d = e.d; a.c0 = e.c0; a.c1 = e.c1;
+    a.skip = nullptr;
+    return a;
+}
+
+// the block halo buffers of an operator for K columns: made once, at the first block apply with that K (never inside a graph
+// capture: amg_block makes those of a hierarchy before its first V-cycle)
+int ensure_blk_halo(sgpu_op *op, int K) {
+    const int s = block_slot(K);
+    if (op->blk_halo_made[s] || !(op->vIndexSize || op->recvSize)) return SGPU_OK;
+    const size_t ns = (size_t)op->vIndexSize * K, nr = (size_t)op->recvSize * K;
+    if (ns && op->send_blk[s].alloc(ns) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block send buffer (%d entries x %d columns) failed", op->vIndexSize, K);
+    if (nr) {
+        if (op->recv_blk[s].alloc(nr) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block receive buffer (%d entries x %d columns) failed", op->recvSize, K);
+        HIPCHK(hipMemset(op->recv_blk[s], 0, nr * sizeof(double)));
+    }
+    if (op->halo_fp32 && g.multi()) {
+        if (ns && op->send_blk_f[s].alloc(ns) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block send buffer (float wire) failed");
+        if (nr && op->recv_blk_f[s].alloc(nr) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block receive buffer (float wire) failed");
+    }
+    op->blk_halo_made[s] = true;
+    return SGPU_OK;
+}
+
+// rows without remote entries (all rows of an operator without a remote part): k_csr_block over the 16 KiB row-block plan on cs
+int launch_block_interior(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, int K) {
+    if (op->M == 0 || op->loc.nblk == 0) return SGPU_OK;
+    const BlockFn fn = pick_block(K, epi, block_lanes_of(op));
+    if (!fn) return fail(SGPU_ERR_ARG, "block apply: no kernel for epilogue %d", epi);   // a missing kernel is an error, never a fall-back
+    sk::BlockArgs a = block_args(op, x, y, e);
+    a.skip = op->has_remote ? (const unsigned *)op->skip : nullptr;
     SGPU_LAUNCH(fn, dim3(op->loc.nblk), dim3(sk::BLOCK), 0, g.cs, a);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
 }
 
-int block_slot(int K) { return K == 2 ? 0 : K == 4 ? 1 : 2; }
+// the rows that own remote entries, whole (local + halo products, one epilogue), once the block halo has arrived
+int launch_block_boundary(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, int K, bool halo_is_f32, hipStream_t stream) {
+    if (!op->has_remote || op->rem.nrows == 0) return SGPU_OK;
+    const int G = block_lanes_of(op), s = block_slot(K);
+    const BlockBndFn fn = pick_block_bnd(K, epi, G);
+    if (!fn) return fail(SGPU_ERR_ARG, "block apply: no boundary kernel for epilogue %d", epi);
+    sk::BlockBoundaryArgs b;
+    b.b = block_args(op, x, y, e);
+    b.rows = op->rem.csr.rows; b.nrows = op->rem.nrows;
+    b.h_ptr = op->rem.csr.row_ptr; b.h_col = op->rem.csr.col; b.h_val = op->rem.csr.val;
+    b.halo = op->recv_blk[s]; b.halo_f = halo_is_f32 ? (const float *)op->recv_blk_f[s] : nullptr;
+    const int eg = G == 1 || G == 4 || G == 16 ? G : 64, rpb = sk::BLOCK / eg;
+    SGPU_LAUNCH(fn, dim3((b.nrows + rpb - 1) / rpb), dim3(sk::BLOCK), 0, stream, b);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+// send[t * K + j] = X[vIndex[t] * K + j] into the operator's block send buffer (the float one on an fp32 wire)
+int pack_block(sgpu_op *op, const double *x, int K, bool f32, int as_float, hipStream_t stream) {
+    if (!op->vIndexSize) return SGPU_OK;
+    const int s = block_slot(K);
+    const size_t pairs = (size_t)op->vIndexSize * (K / 2);
+    const dim3 grid((unsigned)std::min<size_t>(sk::PACK_MAX_BLOCKS, (pairs + sk::BLOCK - 1) / sk::BLOCK));
+    among<2, 4, 8>(K, [&](auto KK) {
+        if (f32) SGPU_LAUNCH(sk::k_pack_block_f32<KK()>, grid, dim3(sk::BLOCK), 0, stream, x, (const int *)op->vIndex, op->send_blk_f[s].get(), op->vIndexSize);
+        else SGPU_LAUNCH(sk::k_pack_block<KK()>, grid, dim3(sk::BLOCK), 0, stream, x, (const int *)op->vIndex, op->send_blk[s].get(), op->vIndexSize, as_float);
+        return 0;
+    });
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+// exchange_group for a block: the same neighbours in the same order, every segment K times as long
+int exchange_group_block(sgpu_op *op, int K, bool f32, hipStream_t st) {
+    const int s = block_slot(K);
+    const size_t k = (size_t)K;
+    NCCLCHK(ncclGroupStart());
+    for (size_t i = 0; i < op->sendRank.size(); ++i) {
+        if (f32) NCCLCHK(ncclSend(op->send_blk_f[s] + op->sendDispl[i] * k, op->sendCount[i] * k, ncclFloat, op->sendRank[i], g.comm, st));
+        else NCCLCHK(ncclSend(op->send_blk[s] + op->sendDispl[i] * k, op->sendCount[i] * k, ncclDouble, op->sendRank[i], g.comm, st));
+    }
+    for (size_t i = 0; i < op->recvRank.size(); ++i) {
+        if (f32) NCCLCHK(ncclRecv(op->recv_blk_f[s] + op->recvDispl[i] * k, op->recvCount[i] * k, ncclFloat, op->recvRank[i], g.comm, st));
+        else NCCLCHK(ncclRecv(op->recv_blk[s] + op->recvDispl[i] * k, op->recvCount[i] * k, ncclDouble, op->recvRank[i], g.comm, st));
+    }
+    NCCLCHK(ncclGroupEnd());
+    ++g_launches;
+    return SGPU_OK;
+}
+
+// apply_host_transport for a block: pack -> host -> callback (its counts x K, the same element size) -> device, then the interior
+// and the boundary rows, all on cs
+int apply_block_host_transport(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, int K) {
+    const bool f32 = op->halo_fp32 != 0;
+    const int s = block_slot(K);
+    const size_t eb = f32 ? sizeof(float) : sizeof(double);
+    std::vector<char> hs((size_t)op->vIndexSize * K * eb), hr((size_t)op->recvSize * K * eb);
+    std::vector<int> sc(op->sendCount), rc(op->recvCount);
+    for (int &c : sc) c *= K;
+    for (int &c : rc) c *= K;
+    if (op->vIndexSize) {
+        CHK(pack_block(op, x, K, f32, 0, g.cs));
+        HIPCHK(hipMemcpyAsync(hs.data(), f32 ? (const void *)op->send_blk_f[s] : (const void *)op->send_blk[s], hs.size(), hipMemcpyDeviceToHost, g.cs));
+    }
+    HIPCHK(hipStreamSynchronize(g.cs));
+    if (g.xchg(g.xuser, hs.data(), op->sendRank.data(), sc.data(), (int)op->sendRank.size(),
+               hr.data(), op->recvRank.data(), rc.data(), (int)op->recvRank.size(), (int)eb) != 0)
+        return fail(SGPU_ERR_RCCL, "host transport: exchange callback failed");
+    if (op->recvSize) HIPCHK(hipMemcpyAsync(f32 ? (void *)op->recv_blk_f[s] : (void *)op->recv_blk[s], hr.data(), hr.size(), hipMemcpyHostToDevice, g.cs));
+    CHK(launch_block_interior(op, epi, x, y, e, K));
+    CHK(launch_block_boundary(op, epi, x, y, e, K, f32, g.cs));
+    HIPCHK(hipStreamSynchronize(g.cs));                  // the staging vectors die with this frame
+    return SGPU_OK;
+}
+
+// Y = epilogue(A X).  Without a halo: one launch of k_csr_block over the operator's 16 KiB row-block plan.  With one, apply()'s
+// plain orderings (sgpu_runtime.hip), the K columns through ONE exchange chain:
+//   host transport   apply_host_transport's sequence;
+//   S (one stream)   pack -> grouped send/recv -> interior rows (k_csr_block with the skip mask) -> boundary rows, all on cs;
+//   E (two streams)  interior rows on cs; pack, send/recv group and boundary rows on hs; ev_x and ev_halo order the two.
+// No flag is polled and no stream value op is used here: nothing this path enqueues waits on a launch the host has yet to make.
+// A rank takes part in the exchange whenever it has a neighbour, whether or not it has rows to launch for.
+int apply_block(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e, int K) {
+    const bool halo = op->vIndexSize || op->recvSize;
+    if (!halo) return launch_block_interior(op, epi, x, y, e, K);
+    const int s = block_slot(K);
+    // the block kernels read the plain CSR of both parts and the boundary mask, whatever form the scalar path is on (the dense
+    // variant included); never the local part alone
+    if (op->has_remote && (!op->loc.csr.row_ptr || !op->rem.csr.row_ptr || !op->rem.csr.rows || !op->skip))
+        return fail(SGPU_ERR_STATE, "block apply: the operator does not hold the CSR arrays of its boundary rows");
+    CHK(ensure_blk_halo(op, K));
+    const bool inj = op->injected_blk[s];
+    if (g.xchg && !inj) return apply_block_host_transport(op, epi, x, y, e, K);
+    if (!g.comm || inj) {
+        if (op->has_remote && !inj)
+            return fail(SGPU_ERR_ARG, "block apply: the operator has a remote part (%d halo entries) and nothing to fetch it with", op->recvSize);
+        CHK(launch_block_interior(op, epi, x, y, e, K));     // halo supplied by the caller (tests): same kernels, one stream
+        return launch_block_boundary(op, epi, x, y, e, K, false, g.cs);
+    }
+    const bool f32 = op->halo_fp32 != 0;                 // both ends of a link must agree: the flag alone decides the wire type
+    if (op->single_stream) {
+        CHK(pack_block(op, x, K, f32, 0, g.cs));
+        CHK(exchange_group_block(op, K, f32, g.cs));
+        CHK(launch_block_interior(op, epi, x, y, e, K));
+        return launch_block_boundary(op, epi, x, y, e, K, f32, g.cs);
+    }
+    // (RCCL connects a peer at the first exchange with it; the scalar path keeps its polling orderings off that one: tell it)
+    if (g.peer_seen.size() != (size_t)g.nranks) g.peer_seen.assign((size_t)g.nranks, 0);
+    for (int r : op->sendRank) g.peer_seen[(size_t)r] |= 1;
+    for (int r : op->recvRank) g.peer_seen[(size_t)r] |= 2;
+    HIPCHK(hipEventRecord(op->ev_x, g.cs));
+    CHK(launch_block_interior(op, epi, x, y, e, K));
+    HIPCHK(hipStreamWaitEvent(g.hs, op->ev_x, 0));
+    CHK(pack_block(op, x, K, f32, 0, g.hs));
+    CHK(exchange_group_block(op, K, f32, g.hs));
+    CHK(launch_block_boundary(op, epi, x, y, e, K, f32, g.hs));
+    // join: nothing later on cs may see y (or overwrite x and the send buffers) before hs is through
+    HIPCHK(hipEventRecord(op->ev_halo, g.hs));
+    HIPCHK(hipStreamWaitEvent(g.cs, op->ev_halo, 0));
+    return SGPU_OK;
+}
 
 // the operator's block ping-pong buffer (the op-level smoother calls; a block V-cycle ping-pongs in its own work vectors) and its
 // Chebyshev direction for K columns: made when first needed, each on its own
@@ -120,11 +290,13 @@ int amg_block(sgpu_amg *h, int K, AmgBlock **out) {
             if (l < L - 1) HIPCHK(alloc_vec(B->res[l], n));
             if (l >= 1) { HIPCHK(alloc_vec(B->rhs[l], n)); HIPCHK(alloc_vec(B->u[l], n)); HIPCHK(alloc_vec(B->alt[l], n)); }
             CHK(ensure_blk_d(h->A[l], K));                     // (Chebyshev direction) no allocation may happen inside a graph capture
+            CHK(ensure_blk_halo(h->A[l], K));                  // nor after the first collective of a solve: the halo buffers of every level
+            if (l < L - 1) { CHK(ensure_blk_halo(h->P[l], K)); CHK(ensure_blk_halo(h->R[l], K)); }
         }
         const size_t n0 = (size_t)h->A[0]->M * K;
         HIPCHK(alloc_vec(B->alt0, n0)); HIPCHK(alloc_vec(B->r, n0)); HIPCHK(alloc_vec(B->rho, n0)); HIPCHK(alloc_vec(B->hh, n0)); HIPCHK(alloc_vec(B->p, n0));
         HIPCHK(alloc_vec(B->cm, 2 * (size_t)h->A[L - 1]->M * K));
-        HIPCHK(alloc_vec(B->S, 8 * (size_t)K));
+        HIPCHK(alloc_vec(B->S, 8 * (size_t)K));              // (rows 0 and 1: where the dots of a multi-rank solve are summed over the ranks)
         HIPCHK(alloc_vec(B->partials, (size_t)g.n_partials * K));
         HIPCHK(B->hS.alloc(K));
         h->blk[slot] = std::move(B);
@@ -136,6 +308,8 @@ int amg_block(sgpu_amg *h, int K, AmgBlock **out) {
 
 int amg_block_check(sgpu_amg *h, int K, const char *what) {
     CHK(block_check(nullptr, K, what));
+    // (both flags are the same on every rank: sgpu_amg_create sums them over the ranks)
+    if (!h->coarse_local) return fail(SGPU_ERR_ARG, "%s: the coarsest level is row-partitioned over the ranks and needs the distributed CG; block solves take hierarchies whose coarsest level lives on one rank", what);
     if (h->coarse_host_driven) return fail(SGPU_ERR_ARG, "%s: the coarsest level has %d rows and needs the host-driven CG; block solves take hierarchies whose coarsest level fits the LDS-resident solvers (<= %d rows)", what, h->A[h->nlevels - 1]->M, sk::CG_MAXN);
     for (int l = 0; l < h->nlevels; ++l) {
         CHK(block_check(h->A[l], K, what));
@@ -208,7 +382,7 @@ int vcycle_block_eager(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, b
 
 // vcycle0 for blocks: captured once per (u, rhs, K) and replayed
 int vcycle_block0(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, bool u_zero = false) {
-    if (!h->prm.use_graph) return vcycle_block_eager(h, B, u, rhs, u_zero);
+    if (!h->prm.use_graph || g.multi()) return vcycle_block_eager(h, B, u, rhs, u_zero);
     if (!B.graphs.empty() && (B.graph_gen != g_plan_generation || B.block_gen != g_block_generation)) {
         HIPCHK(hipStreamSynchronize(g.cs));
         B.drop_graphs();
@@ -230,7 +404,29 @@ int vcycle_block0(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, bool u
     return SGPU_OK;
 }
 
-// out[j] = x_j . y_j on the columns of `active` (the others keep what they hold)
+// out[j] (K device scalars, this rank's share) summed over the ranks on the columns of `active`; the others keep their bits.  Summed
+// into scratch (rows 0 and 1 of S) and copied under the mask: in place, a frozen column's stale slot would be multiplied by the
+// rank count.  Every rank reads the same reduced bits, so the masks, iteration counts and histories agree on all of them.
+int rank_sum_block(AmgBlock &B, double *out, unsigned active) {
+    if (!g.multi()) return SGPU_OK;
+    const int K = B.K;
+    double *sum = B.S + K;
+    if (g.comm) {
+        NCCLCHK(ncclAllReduce(out, sum, (size_t)K, ncclDouble, ncclSum, g.comm, g.cs));
+        ++g_launches;
+    } else {
+        HIPCHK(hipMemcpyAsync(B.hS, out, K * sizeof(double), hipMemcpyDeviceToHost, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
+        CHK(host_allreduce(B.hS, K));
+        HIPCHK(hipMemcpyAsync(sum, B.hS, K * sizeof(double), hipMemcpyHostToDevice, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));               // (hS is the mirror the caller fetches into next)
+    }
+    SGPU_LAUNCH(sk::k_copy_masked, dim3(1), dim3(64), 0, g.cs, (const double *)sum, out, K, active);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
+// out[j] = x_j . y_j on the columns of `active` (the others keep what they hold); this rank's rows
 int dot_block(AmgBlock &B, const double *x, const double *y, size_t n, double *out, unsigned active) {
     const int nb = dot_nblocks(n), K = B.K;
     if (K == 2) SGPU_LAUNCH(sk::k_dot_block_partial<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
@@ -344,6 +540,29 @@ int sgpu_debug_block_pcg_direction(sgpu_amg *h, const value_t *num, const value_
     return pcg_direction_block(*B, num, den, Z, P, n, active);
 }
 
+// ---- tests: the block twins of sgpu_debug_pack / sgpu_debug_inject_halo ----
+int sgpu_debug_pack_block(sgpu_op *op, const value_t *X, int K, value_t *send_host) {
+    CHK(need_ctx());
+    if (!op || !X) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(nullptr, K, "debug_pack_block"));
+    if (op->vIndexSize == 0) return SGPU_OK;
+    if (!send_host) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(ensure_blk_halo(op, K));
+    CHK(pack_block(op, X, K, false, op->halo_fp32, g.cs));
+    return sgpu_vec_download(send_host, op->send_blk[block_slot(K)], (size_t)op->vIndexSize * K);
+}
+
+int sgpu_debug_inject_halo_block(sgpu_op *op, int K, const value_t *recv_host) {
+    CHK(need_ctx());
+    if (!op) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(block_check(nullptr, K, "debug_inject_halo_block"));
+    if (op->recvSize && !recv_host) return fail(SGPU_ERR_ARG, "null argument");
+    CHK(ensure_blk_halo(op, K));
+    if (op->recvSize) CHK(sgpu_vec_upload(op->recv_blk[block_slot(K)], recv_host, (size_t)op->recvSize * K));
+    op->injected_blk[block_slot(K)] = true;
+    return SGPU_OK;
+}
+
 int sgpu_block_pack(const value_t *cols_colmajor, value_t *blk, size_t n, int K) {
     CHK(need_ctx());
     if (!cols_colmajor || !blk) return fail(SGPU_ERR_ARG, "null argument");
@@ -428,9 +647,9 @@ int sgpu_vcycle_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K) {
 }
 
 // sgpu_solve_pCG's recurrence for K columns in lockstep.  Per column: its own rho, alpha, beta (device scalars, rows of S) and
-// threshold; a column is frozen from the iteration at which its ||r||^2 drops below its threshold -- bit j of `active` leaves
+// threshold (with a communicator or a host transport the dots are summed over the ranks, rank_sum_block); a column is frozen from the iteration at which its ||r||^2 drops below its threshold -- bit j of `active` leaves
 // the mask every update kernel takes, and the column's u, r, p and scalars are not written again.  One host synchronisation
-// per iteration: the K current dots.
+// per iteration: the K current dots (two more per dot under the host transport).
 int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int *iters, value_t *hist, int cap) {
     CHK(need_ctx());
     if (!h || !U || !RHS) return fail(SGPU_ERR_ARG, "null argument");
@@ -451,6 +670,7 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
     CHK(sgpu_vec_fill(U, 0.0, szK));
     { EpiArgs e; e.rhs = RHS; CHK(apply_block(A, sk::EPI_RESIDUAL, U, r, e, K)); }
     CHK(dot_block(B, r, r, sz, Srr, all));
+    CHK(rank_sum_block(B, Srr, all));
     CHK(fetch(Srr));
     double thr[8], cur[8];
     int it[8];
@@ -467,10 +687,13 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
         CHK(vcycle_block0(h, B, rho, r, true));
         CHK(sgpu_vec_copy(p, rho, szK));
         CHK(dot_block(B, r, rho, sz, Sa, active));
+        CHK(rank_sum_block(B, Sa, active));
         for (int i = 0; i < h->prm.solver_max_iter && active; ++i) {
             CHK(apply_block(A, sk::EPI_SPMV, p, hh, EpiArgs(), K));
             CHK(dot_block(B, p, hh, sz, Sph, active));
+            CHK(rank_sum_block(B, Sph, active));
             CHK(pcg_update_block(B, Sa, Sph, p, hh, U, r, sz, active, Srr));
+            CHK(rank_sum_block(B, Srr, active));
             CHK(fetch(Srr));
             for (int j = 0; j < K; ++j) {
                 if (!((active >> j) & 1u)) continue;
@@ -482,6 +705,7 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
             if (!active || i + 1 == h->prm.solver_max_iter) break;
             CHK(vcycle_block0(h, B, rho, r, true));
             CHK(dot_block(B, r, rho, sz, Sb, active));
+            CHK(rank_sum_block(B, Sb, active));
             CHK(pcg_direction_block(B, Sb, Sa, rho, p, sz, active));
             std::swap(Sa, Sb);
         }

@@ -101,6 +101,17 @@ int eig_precondition(sgpu_amg *h, AmgBlock &B, AmgEig &E) {
     return SGPU_OK;
 }
 
+// LOBPCG stays on one rank: its Gram blocks and norms are not summed over the ranks.  No communicator, no host transport, no
+// operator with a remote part (an injected block halo does not lift this) -- then what every block solve asks of a hierarchy
+int lobpcg_check(sgpu_amg *h, int K, const char *what) {
+    CHK(block_one_rank_check(nullptr, K, what));
+    for (int l = 0; l < h->nlevels; ++l) {
+        CHK(block_one_rank_check(h->A[l], K, what));
+        if (l < h->nlevels - 1) { CHK(block_one_rank_check(h->P[l], K, what)); CHK(block_one_rank_check(h->R[l], K, what)); }
+    }
+    return amg_block_check(h, K, what);
+}
+
 // what the debug wrappers check: the hierarchy (for its AmgEig) and K
 int eig_debug_args(sgpu_amg *h, int K, const char *what, AmgEig **E) {
     CHK(need_ctx());
@@ -209,7 +220,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
                      value_t *res_hist, int hist_cap) {
     CHK(need_ctx());
     if (!h || !X || !lambda) return fail(SGPU_ERR_ARG, "eigs_LOBPCG: null argument");
-    CHK(amg_block_check(h, K, "eigs_LOBPCG"));
+    CHK(lobpcg_check(h, K, "eigs_LOBPCG"));
     if (nev < 1 || nev > K) return fail(SGPU_ERR_ARG, "eigs_LOBPCG: nev must be in 1..K (nev = %d, K = %d)", nev, K);
     if (precond != 0 && precond != 1) return fail(SGPU_ERR_ARG, "eigs_LOBPCG: precond is 0 (none) or 1 (one V-cycle), got %d", precond);
     if (max_iter < 0 || !(tol >= 0.0)) return fail(SGPU_ERR_ARG, "eigs_LOBPCG: max_iter and tol must not be negative");

@@ -1449,6 +1449,11 @@ struct sgpu_op {
     // (never re-allocated: captured block V-cycles hold the pointers)
     int     block_lanes = 0, block_lanes_auto = 0;
     DevArr<double> tmp_blk[3], dvec_blk[3];
+    // the block halo of an operator with a halo plan, per K = 2, 4, 8: send / receive buffers of vIndexSize * K / recvSize * K doubles
+    // (and the float pair of an fp32 wire), made at the first block apply with that K; injected_blk: sgpu_debug_inject_halo_block
+    DevArr<double> send_blk[3], recv_blk[3];
+    DevArr<float>  send_blk_f[3], recv_blk_f[3];
+    bool    blk_halo_made[3] = {false, false, false}, injected_blk[3] = {false, false, false};
     // halo plan
     int     vIndexSize = 0, recvSize = 0;
     DevArr<int>    vIndex;
