@@ -72,6 +72,12 @@ int sgpu_debug_on_fatal_print(const char *line);
  * on the received data; microseconds, the maximum over the ranks); 0 without a communicator.  The agglomeration of coarse
  * levels and the one- / two-stream thresholds of a multi-rank apply start from it. */
 int sgpu_debug_chain_us(double *us);
+/* tests (tests/rccl_mirror.py): how the next scalar apply of `op` (sgpu_spmv, the residuals, a smoother sweep ...) orders its halo
+ * exchange against its rows, for an apply whose peers are already connected (the first exchange with a peer always takes events).
+ * Computed by the predicate apply() itself branches on, from the operator's current form and the context:
+ *   0 no exchange (no halo, an injected halo, or no transport)   1 host transport   2 one stream (also: the dense form with a halo)
+ *   3 two streams, flags polled by kernels   4 two streams, stream value operations   5 two streams, events */
+int sgpu_debug_exchange_mode(const sgpu_op *op, int *mode);
 /* number of kernel launches + graph launches + RCCL group calls the library has enqueued since sgpu_init
  * (tests: "fewer launches per V-cycle"); counts host-side enqueues, not GPU work */
 int sgpu_debug_launch_count(long *launches);

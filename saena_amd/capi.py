@@ -103,6 +103,7 @@ SYMBOLS = {
     "sgpu_debug_launch_count": (C.c_int, [C.POINTER(C.c_long)]),
     "sgpu_debug_op_storage": (C.c_int, [_VP, C.POINTER(C.c_uint), C.POINTER(C.c_longlong)]),
     "sgpu_debug_chain_us": (C.c_int, [C.POINTER(C.c_double)]),
+    "sgpu_debug_exchange_mode": (C.c_int, [_VP, _PI]),
     "sgpu_debug_device_info": (C.c_int, [C.c_char_p, C.c_int]),
     "sgpu_debug_allow_local_only": (C.c_int, [_VP, C.c_int]),
     "sgpu_debug_init_host_transport": (C.c_int, [C.c_int, C.c_int, C.c_int, _VP, _VP, _VP]),
@@ -336,6 +337,9 @@ def _ad(a):
     return np.ascontiguousarray(a, np.float64)
 
 
+EXCHANGE_MODES = ("none", "host-transport", "one-stream", "kernel-flags", "value-ops", "events")
+
+
 class Operator:
     """sgpu_op built from one rank's arrays in the reference's storage layout."""
 
@@ -418,6 +422,12 @@ class Operator:
         v = C.c_int()
         check(lib().sgpu_op_get_x_windows(self.h, C.byref(v)))
         return v.value
+
+    def exchange_mode(self):
+        """how the next scalar apply orders its exchange (sgpu_debug_exchange_mode): an index into EXCHANGE_MODES"""
+        v = C.c_int()
+        check(lib().sgpu_debug_exchange_mode(self.h, C.byref(v)))
+        return EXCHANGE_MODES[v.value]
 
     def storage_mask(self):
         """bit mask of the local part's storage groups that hold device memory (sgpu_debug_op_storage; bit order: STORAGE_GROUPS)"""

@@ -74,7 +74,10 @@ int ensure_blk_halo(sgpu_op *op, int K) {
     if (ns && op->send_blk[s].alloc(ns) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block send buffer (%d entries x %d columns) failed", op->vIndexSize, K);
     if (nr) {
         if (op->recv_blk[s].alloc(nr) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block receive buffer (%d entries x %d columns) failed", op->recvSize, K);
-        HIPCHK(hipMemset(op->recv_blk[s], 0, nr * sizeof(double)));
+        // on cs and waited for: a memset of device memory on the null stream returns before it has run, and neither cs nor hs (both
+        // non-blocking) waits for that stream -- it could land on top of the first exchange or of an injected halo
+        HIPCHK(hipMemsetAsync(op->recv_blk[s], 0, nr * sizeof(double), g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
     }
     if (op->halo_fp32 && g.multi()) {
         if (ns && op->send_blk_f[s].alloc(ns) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of a block send buffer (float wire) failed");

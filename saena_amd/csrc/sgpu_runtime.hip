@@ -1830,6 +1830,20 @@ int apply_host_transport(sgpu_op *op, int epi, const double *x, double *y, const
     return SGPU_OK;
 }
 
+// How apply() orders the exchange of `op` against its rows (the values of sgpu_debug_exchange_mode).  fresh_peer: this exchange is
+// the first with one of its peers in one direction, which runs in the plainest two-stream mode (see apply()).
+enum { XM_NONE = 0, XM_HOST = 1, XM_ONE_STREAM = 2, XM_KERNEL_FLAGS = 3, XM_VALUE_OPS = 4, XM_EVENTS = 5 };
+int exchange_mode(const sgpu_op *op, bool fresh_peer) {
+    if (op->injected || !(op->vIndexSize || op->recvSize)) return XM_NONE;
+    if (g.xchg) return XM_HOST;
+    if (!g.comm) return XM_NONE;
+    if (op->single_stream || (is_dense(op->loc.variant) && op->has_remote)) return XM_ONE_STREAM;      // (the dense form has no interior/boundary split)
+    const bool plain = fresh_peer || op->events_only;
+    if (g.inkernel_sync && op->loc.nblk > 0 && !plain) return XM_KERNEL_FLAGS;
+    if (g.value_ops && !plain) return XM_VALUE_OPS;
+    return XM_EVENTS;
+}
+
 // y = epi(A x).  With a communicator the two streams split the ROWS, not the phases:
 //   cs (compute): interior rows -- every row without remote entries -- straight away;
 //   hs (halo):    wait for the inputs (ev_x) -> pack -> ncclSend/ncclRecv group -> boundary rows whole;
@@ -1838,9 +1852,9 @@ int apply_host_transport(sgpu_op *op, int epi, const double *x, double *y, const
 // profiles/r01_halo_loopback_trace.md) and the interior launch never waits for it: this is where the
 // reference overlaps MPI_Isend/Irecv with its local loop (src/saena_matrix_matvec.cpp:32-80).
 int apply(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e) {
-    if (g.xchg && !op->injected && (op->vIndexSize || op->recvSize)) return apply_host_transport(op, epi, x, y, e);
-    const bool exchanged = g.comm && !op->injected && (op->vIndexSize || op->recvSize);
-    if (!exchanged) {
+    int mode = exchange_mode(op, false);
+    if (mode == XM_HOST) return apply_host_transport(op, epi, x, y, e);
+    if (mode == XM_NONE) {
         if (op->has_remote && op->injected)             // halo supplied by the caller (tests): same kernels, one stream
             return launch_rows_after_exchange(op, epi, x, y, e, false, g.cs);
         // an operator with remote entries but no way to fetch them (no communicator, no host transport, no injected
@@ -1855,7 +1869,7 @@ int apply(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e) {
     }
     const bool f32 = op->halo_fp32 != 0;                 // both ends of a link must agree: the flag alone decides the wire type
     const unsigned *skip = op->has_remote ? op->skip : nullptr;
-    if (op->single_stream || (is_dense(op->loc.variant) && op->has_remote)) {      // (the dense form has no interior/boundary split)
+    if (mode == XM_ONE_STREAM) {
         // S  one stream.  A SHORT local kernel has nothing to hide the exchange behind, and the fork/join between the
         //    two streams then costs more than it overlaps: pack -> send/recv group -> interior rows -> boundary rows,
         //    all on cs, in stream order (4 enqueues instead of 6, no flag, no event; capturable in a hipGraph).
@@ -1889,9 +1903,8 @@ int apply(sgpu_op *op, int epi, const double *x, double *y, const EpiArgs &e) {
     // A LONG interior kernel hides the whole exchange chain whichever way the streams are ordered (16.6 M rows per GPU,
     // configs[3]: ~290 us of interior work against a 48 us chain in the plainest mode), so such operators take plain
     // events: nothing polls, nothing depends on co-residency.  The polling forms earn their keep in between.
-    const bool plain = fresh_peer || op->events_only;
-    const bool K = g.inkernel_sync && op->loc.nblk > 0 && !plain;
-    const bool V = g.value_ops && !plain;
+    if (fresh_peer) mode = exchange_mode(op, true);
+    const bool K = mode == XM_KERNEL_FLAGS, V = mode == XM_VALUE_OPS;
     if (K) {
         CHK(launch_part(op->loc, epi, x, y, e, skip, n));
     } else {
@@ -2184,7 +2197,8 @@ int sgpu_init(int device_id, int rank, int nranks, const void *uid) {
     if (!std::getenv("SAENA_NO_INKERNEL_SYNC")) {
         char *fl = nullptr;
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&fl), 512));
-        HIPCHK(hipMemset(fl, 0, 512));
+        HIPCHK(hipMemsetAsync(fl, 0, 512, g.cs));        // (on cs and waited for: neither cs nor hs waits for a memset on the null stream)
+        HIPCHK(hipStreamSynchronize(g.cs));
         g.kflag_x = reinterpret_cast<uint64_t *>(fl); g.kflag_h = reinterpret_cast<uint64_t *>(fl + 128);
         g.inkernel_sync = true;
     }
@@ -3799,6 +3813,13 @@ int sgpu_debug_chain_us(double *us) {
     CHK(need_ctx());
     if (!us) return fail(SGPU_ERR_ARG, "null argument");
     *us = g.chain_us;
+    return SGPU_OK;
+}
+
+int sgpu_debug_exchange_mode(const sgpu_op *op, int *mode) {
+    CHK(need_ctx());
+    if (!op || !mode) return fail(SGPU_ERR_ARG, "null argument");
+    *mode = exchange_mode(op, false);
     return SGPU_OK;
 }
 
