@@ -865,41 +865,55 @@ __global__ __launch_bounds__(BLOCK) void k_vidx(const SpmvArgs a, int nrows) {
 // is k_vidx's).  k_vidx requests x seven times per row of the 7-point level although every element is stored once; a workgroup of
 // R consecutive rows reads x only inside a few windows [r0 + omin_c, r0 + R + omax_c) (k_sellpx's clusters, the gap rule at R), which
 // it loads ONCE with coalesced loads and gathers from LDS: 8 (3 R + 2 n) / R bytes of x per row instead of 56.
-// Every global load of a workgroup is issued before its ONE barrier: codes, pattern id, the epilogue's operands (Jacobi / residual,
-// as k_sellp2<PRE>), then windows, dictionaries and table -- k_vidx's chain of three dependent round trips becomes one.
+// The kernel is bound by the lifetime of its waves, so the prologue is ONE block of straight-line code: what it needs to form its
+// addresses arrives in the kernel arguments (VwHead: the first four windows, the table's word counts, the common dictionary length),
+// and then every wave issues all its loads -- codes, pattern id, the epilogue's operands (Jacobi / residual, as k_sellp2<PRE>), a
+// dictionary value, a table chunk, the windows -- before it waits for any of them and meets the workgroup's one barrier.  Where a
+// lane has no dictionary value or table chunk of its own the index is clamped, not branched on.  Beyond that only what is rare
+// keeps a round trip of its own: slices of differing widths (a.vcptr), dictionaries of differing lengths (a.vdptr), a fifth
+// window and later (a.segtab), more than 4 R doubles of x, a table of more than R chunks.  tools/kernel_waits.py lists the loads
+// and waits of the compiled prologue (profiles/r08_vidxw_prologue_isa_*.txt).
 // blockDim.x = R in {256, 512, 1024}, a lane per row; dynamic LDS: [windows of x][R / 256 dictionaries of VI_MAX][table].
-// a.segtab: nwin, S (doubles of x in LDS), then per window (LDS base, omin - base), at least four (unused: base INT32_MAX); a.ptab: the table as 16-bit words -- the patterns'
-// lengths (padded to a multiple of 8), then per pattern pt_w (a multiple of 8) LDS positions for the workgroup's first row, the
-// tail repeating the last one; a.vcode / a.vcptr / a.uw / a.vdict / a.vdptr / a.dst: k_vidx's.
+// h: see VwHead; a.segtab: nwin, S, then per window (LDS base, omin - base), at least four (unused: base INT32_MAX) -- read from the
+// fifth window on; a.ptab: the table as 16-bit words -- the patterns' lengths (padded to a multiple of 8), then per pattern pt_w (a
+// multiple of 8) LDS positions for the workgroup's first row, the tail repeating the last one; a.vcode / a.vcptr / a.uw / a.vdict /
+// a.vdptr / a.dst: k_vidx's.
 // Same products, same sequential row sum: bit-identical to k_vidx and k_sellp.
 constexpr int VW_MAX_LDS = 64 * 1024;          // windows + dictionaries + table: at least two workgroups per CU
 typedef unsigned sk_u4v __attribute__((ext_vector_type(4)));
+// the head of the window table and what else the prologue would fetch from memory before it can form an address: by value, k_vidxw's
+// second parameter (build_xwin fills it)
+struct VwHead {
+    int nwin, S;          // windows; doubles of x in LDS
+    int win[8];           // (LDS base, omin - base) of the first four windows (unused ones: base INT32_MAX)
+    int lp, tn;           // 16-bit words of the table: the patterns' lengths, all of it (multiples of 8)
+    int vd_u;             // every dictionary of the operator holds this many values, or 0: they differ, read a.vdptr
+};
 template <int EPI, bool HALO, bool NT>
-__global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, int nrows) {
+__global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h, int nrows) {
     extern __shared__ __attribute__((aligned(16))) double vw_lds[];
     if constexpr (HALO) fork_signal(a);
-    // (the kernel is bound by instruction issue on the cache-resident level, not by bytes: no division, no branch per position or
-    //  per staged element -- clamped addresses and selects instead)
+    // (no division, no branch per position or per staged element -- clamped addresses and selects instead)
     const int R = (int)blockDim.x, sh = __builtin_ctz((unsigned)R) - 6, D = R >> 8;     // rows, log2(slices) and dictionaries per workgroup
     const int tid = threadIdx.x, lane = tid & 63;
-    const int b = xcd_remap(blockIdx.x, (a.nblk + (1 << sh) - 1) >> sh);
+    const int nblk = a.nblk, uw = a.uw, vd_u = h.vd_u;
+    const int b = xcd_remap(blockIdx.x, (nblk + (1 << sh) - 1) >> sh);
     const int r0 = b * R;
     const int s = __builtin_amdgcn_readfirstlane((b << sh) + (tid >> 6));
-    const bool live = s < a.nblk;                                  // (the last workgroup's spare waves still stage and meet the barrier)
+    const bool live = s < nblk;                                    // (the last workgroup's spare waves still stage and meet the barrier)
+    const int sc = live ? s : 0;                                   // ... reading slice 0's codes, which they never use
     const int r = r0 + tid;
     const bool row = r < nrows;                                    // (only inside live slices)
     const int rc = row ? r : 0;                                    // a valid row for the loads of a lane without one
-    // ---- 1. every global load of the lane
-    int cp = 0, w8 = 0;
-    if (live) {
-        if (a.uw) { w8 = a.uw; cp = s * w8 * 64; }
-        else { cp = a.vcptr[s]; w8 = (a.vcptr[s + 1] - cp) >> 6; }
-    }
+    // ---- 1. every global load of the lane but the windows', at addresses formed from the arguments alone: where the slices have one
+    // width and the dictionaries one length (the 7-point levels) these are the addresses, and no branch stands before the loads
+    int cp = sc * uw * 64, w8 = uw;                                // (uw = 0: slice 0's codes, read again below)
+    const int ngd = (nblk + 3) >> 2;                               // dictionaries of the operator
+    const int g0 = b * D, g1 = g0 + D < ngd ? g0 + D : ngd, gw = live ? s >> 2 : g0;      // the workgroup's first, one past its last, the wave's own
+    int d0 = g0 * vd_u, dn = (g1 - g0) * vd_u, dw0 = (gw - g0) * vd_u;                     // the workgroup's values, contiguous: dn <= D * VI_MAX = R; where the wave's begin
     const bool ntv = NT && s >= a.nt_from;
     const sk_u2v *c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp) + lane;
     auto ld_codes = [&](int j) { sk_u2v v; if (ntv) v = __builtin_nontemporal_load(c8 + (j >> 3) * 64); else v = c8[(j >> 3) * 64]; return v; };
-    sk_u2v cc = {0u, 0u};
-    if (w8 > 0) cc = ld_codes(0);
     int pid;
     if constexpr (NT) pid = __builtin_nontemporal_load(a.dst + rc); else pid = a.dst[rc];
     constexpr bool PREF = !HALO && (EPI == EPI_JACOBI || EPI == EPI_RESIDUAL);
@@ -908,16 +922,29 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, int nrows) {
         pre_b = ld_once<NT>(a.rhs + rc);
         if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(a.inv_diag + rc); pre_u = a.u[rc]; }
     }
-    const sk_i4v w0 = *reinterpret_cast<const sk_i4v *>(a.segtab), w1 = *reinterpret_cast<const sk_i4v *>(a.segtab + 4);
-    const int b3 = a.segtab[8], e3 = a.segtab[9];
-    const int nwin = w0.x, S = w0.y;                               // (w0.z = 0: the first window's base)
-    const int ngd = (a.nblk + 3) >> 2;                             // dictionaries of the operator
-    const int d0 = a.vdptr[b * D], dn = a.vdptr[b * D + D < ngd ? b * D + D : ngd] - d0;      // this workgroup's, contiguous: dn <= D * VI_MAX = R
-    const int dw0 = live ? a.vdptr[s >> 2] - d0 : 0;               // where this wave's own begins
+    const int S = h.S, lp = h.lp, n8 = h.tn >> 3;                  // (n8 >= 1: 16-byte chunks of the table)
     double *xw = vw_lds, *dict = vw_lds + ((S + 2) & ~1);          // (xw[S]: a spare slot for the staging lanes past the windows)
     unsigned short *tab = reinterpret_cast<unsigned short *>(dict + D * VI_MAX);
-    const int lp = (a.pt_n + 7) & ~7, tn = lp + a.pt_n * a.pt_w;   // 16-bit words of the table, a multiple of 8
-    // ---- 2. windows (zero where they leave the vector), dictionaries, table -> LDS
+    const sk_u4v *gt = reinterpret_cast<const sk_u4v *>(a.ptab);
+    sk_u4v *lt = reinterpret_cast<sk_u4v *>(tab);
+    const sk_u4v tc0 = gt[tid < n8 ? tid : 0];
+    sk_u2v cc = ld_codes(0);                                       // (an empty slice reads the next one's, or the 512 bytes vcode is padded by)
+    // a lane beyond the dictionary reads its first value again: with dn = 0 that is the next workgroup's, or -- behind the last one -- the
+    // element build_vidx pads vdict by.  It lands in a slot of dict no code points at (tid < R = D * VI_MAX)
+    double dv0 = a.vdict[d0 + (tid < dn ? tid : 0)];               // (vd_u = 0: vdict[0], read again below)
+    // ---- 2. slices of differing widths, dictionaries of differing lengths: one scalar round trip each, then the load once more
+    if (!uw) {
+        cp = a.vcptr[sc]; w8 = (a.vcptr[sc + 1] - cp) >> 6;
+        c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp) + lane;
+        cc = ld_codes(0);
+    }
+    w8 = live ? w8 : 0;
+    if (!vd_u) {
+        const int p0 = a.vdptr[g0], p1 = a.vdptr[g1], pw = a.vdptr[gw];
+        d0 = p0; dn = p1 - p0; dw0 = pw - p0;
+        dv0 = a.vdict[d0 + (tid < dn ? tid : 0)];
+    }
+    // ---- 3. windows (zero where they leave the vector), dictionaries, table -> LDS
     const int xlast = a.ncols - 1;
     auto stage4 = [&](int i0) {                                    // four elements per lane: all loads, then all LDS writes
         int    ii[4], dd[4];
@@ -925,12 +952,12 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, int nrows) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             ii[u] = i0 + u * R + tid;
-            dd[u] = w0.w;                                          // the last window that begins at or before the element (unused ones: base INT32_MAX)
-            dd[u] = ii[u] >= w1.x ? w1.y : dd[u];
-            dd[u] = ii[u] >= w1.z ? w1.w : dd[u];
-            dd[u] = ii[u] >= b3 ? e3 : dd[u];
+            dd[u] = h.win[1];                                      // the last window that begins at or before the element (unused ones: base INT32_MAX)
+            dd[u] = ii[u] >= h.win[2] ? h.win[3] : dd[u];
+            dd[u] = ii[u] >= h.win[4] ? h.win[5] : dd[u];
+            dd[u] = ii[u] >= h.win[6] ? h.win[7] : dd[u];
         }
-        for (int c = 4; c < nwin; ++c) {
+        for (int c = 4; c < h.nwin; ++c) {
             const int bc = a.segtab[2 + 2 * c], dc = a.segtab[3 + 2 * c];
 #pragma unroll
             for (int u = 0; u < 4; ++u) if (ii[u] >= bc) dd[u] = dc;
@@ -945,16 +972,13 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, int nrows) {
         for (int u = 0; u < 4; ++u) xw[ii[u] < S ? ii[u] : S] = v[u];
     };
     stage4(0);
+    dict[tid] = dv0;
+    if (tid < n8) lt[tid] = tc0;
     for (int i0 = 4 * R; i0 < S; i0 += 4 * R) stage4(i0);
-    if (tid < dn) dict[tid] = a.vdict[d0 + tid];
-    {
-        const sk_u4v *gt = reinterpret_cast<const sk_u4v *>(a.ptab);
-        sk_u4v *lt = reinterpret_cast<sk_u4v *>(tab);
-        for (int i = tid; i < (tn >> 3); i += R) lt[i] = gt[i];
-    }
+    for (int i = tid + R; i < n8; i += R) lt[i] = gt[i];
     __syncthreads();
     if (!live) return;
-    // ---- 3. the row: dictionary value x window entry, in the table's order
+    // ---- 4. the row: dictionary value x window entry, in the table's order
     if (!row) pid = 0;
     const int len = row ? (int)tab[pid] : 0;
     const unsigned short *pos = tab + lp + pid * a.pt_w;

@@ -214,8 +214,8 @@ struct CsrPart {
     int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
     // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
     // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS positions; vw_rows: the R in
-    // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays
-    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
+    // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays; head: what of them (and of vi_dptr) every launch passes by value
+    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; sk::VwHead head{}; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
     XWin            vw[3];
     int             vw_rows = 0;
     // x in LDS (variant 10): absolute 16-bit column ids and nnz-balanced row chunks, one per CU.  The chunk plan (k_sellx is built
@@ -1161,7 +1161,7 @@ int build_vidx(CsrPart &P) {
     int dmax = 0;
     for (int b = 0; b < ngrp; ++b) { dptr[(size_t)b + 1] = dptr[(size_t)b] + cnt[(size_t)b]; dmax = std::max(dmax, cnt[(size_t)b]); }
     CHK(dev_upload(P.vi.vi_dptr, dptr.data(), dptr.size()));
-    CHK(dev_upload(P.vi.vi_dict, (const double *)nullptr, 0, (size_t)dptr[(size_t)ngrp] + 1));
+    CHK(dev_upload(P.vi.vi_dict, (const double *)nullptr, 0, (size_t)dptr[(size_t)ngrp] + 1));      // (one element more: k_vidxw's lanes without a value read vdict[d0], and an empty last dictionary begins at the end)
     SGPU_LAUNCH(sk::k_vi_compact, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)tmp, (const int *)P.vi.vi_dptr, P.vi.vi_dict.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
@@ -1234,8 +1234,18 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     std::vector<int> win(2 + 2 * (size_t)std::max(nwin, 4), INT32_MAX);          // (the kernel reads the first four windows unconditionally: unused ones never match)
     win[0] = nwin; win[1] = (int)S;
     for (int c = 0; c < nwin; ++c) { win[2 + 2 * (size_t)c] = base[(size_t)c]; win[3 + 2 * (size_t)c] = omin[(size_t)c] - base[(size_t)c]; }
+    // the dictionaries' common length, where they have one: the kernel then computes where a workgroup's values begin and reads no vi_dptr
+    const int ngd = ((M + 63) / 64 + 3) / 4;
+    std::vector<int> dptr((size_t)ngd + 1);
+    HIPCHK(hipMemcpyAsync(dptr.data(), P.vi.vi_dptr, dptr.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
+    HIPCHK(hipStreamSynchronize(g.cs));
+    int vd_u = dptr[1] - dptr[0];
+    for (int b = 1; b < ngd; ++b) if (dptr[(size_t)b + 1] - dptr[(size_t)b] != vd_u) vd_u = 0;
     CHK(dev_upload(X.tab, t16.data(), t16.size(), 8));
     CHK(dev_upload(X.win, win.data(), win.size()));
+    X.head.nwin = nwin; X.head.S = (int)S;
+    std::copy(win.begin() + 2, win.begin() + 10, X.head.win);
+    X.head.lp = lp; X.head.tn = (int)words; X.head.vd_u = vd_u;
     X.wp = wp; X.lds = (int)lds; X.ok = true;
     if (std::getenv("SAENA_SETUP_TIMING"))
         fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row)\n",
@@ -1506,6 +1516,7 @@ using dispatch::among;
 using dispatch::with_bool;
 using KernelFn = void (*)(const sk::SpmvArgs);
 using VecKernelFn = void (*)(const sk::SpmvArgs, int);
+using VidxwKernelFn = void (*)(const sk::SpmvArgs, const sk::VwHead, int);      // k_vidxw: the head of its tables by value
 using SellKernelFn = void (*)(const sk::SpmvArgs, int);     // seq != 0: the launch carries the fork (block 0 stores flag_x = seq when it starts)
 using XldsKernelFn = void (*)(const sk::SpmvArgs, const sk::XldsArgs);
 using SellxKernelFn = void (*)(const sk::SpmvArgs, const sk::SellxArgs);
@@ -1559,8 +1570,8 @@ SellKernelFn pick_sellpx(int epi, bool halo, bool pair, bool nt) {
 SellKernelFn pick_vidx(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_vidx<E(), H(), N()>; }); }); });
 }
-SellKernelFn pick_vidxw(int epi, bool halo, bool nt) {
-    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_vidxw<E(), H(), N()>; }); }); });
+VidxwKernelFn pick_vidxw(int epi, bool halo, bool nt) {
+    return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> VidxwKernelFn { return sk::k_vidxw<E(), H(), N()>; }); }); });
 }
 SellKernelFn pick_rowt(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_rowt<E(), H(), N()>; }); }); });
@@ -1747,7 +1758,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
             const CsrPart::XWin &X = P.vw[k];
             if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
             a.ptab = reinterpret_cast<const int *>(X.tab.get()); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
-            SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, P.nrows);
+            SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, X.head, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
     } break;
