@@ -24,6 +24,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include "xwin_stage.h"
 
 namespace sk {
 
@@ -873,10 +875,14 @@ __global__ __launch_bounds__(BLOCK) void k_vidx(const SpmvArgs a, int nrows) {
 // keeps a round trip of its own: slices of differing widths (a.vcptr), dictionaries of differing lengths (a.vdptr), a fifth
 // window and later (a.segtab), more than 4 R doubles of x, a table of more than R chunks.  tools/kernel_waits.py lists the loads
 // and waits of the compiled prologue (profiles/r08_vidxw_prologue_isa_*.txt).
+// The vector unit is the kernel's busiest (0.7-0.8 of its clocks before this form: DESIGN section 4), so what a wave knows as a
+// scalar is not computed per lane: the windows are staged one by one (xwin_stage.h: a trip's window, LDS base and first column are
+// scalars, the zeros outside x come from the buffer load's range check), every per-row address is a scalar base plus a 32-bit lane
+// offset, and the row loop runs one of a few bodies chosen by the longest and the shortest pattern (VwHead::lmax / lmin).
 // blockDim.x = R in {256, 512, 1024}, a lane per row; dynamic LDS: [windows of x][R / 256 dictionaries of VI_MAX][table].
 // h: see VwHead; a.segtab: nwin, S, then per window (LDS base, omin - base), at least four (unused: base INT32_MAX) -- read from the
 // fifth window on; a.ptab: the table as 16-bit words -- the patterns' lengths (padded to a multiple of 8), then per pattern pt_w (a
-// multiple of 8) LDS positions for the workgroup's first row, the tail repeating the last one; a.vcode / a.vcptr / a.uw / a.vdict /
+// multiple of 8) LDS byte offsets (8 x position: below 64 KiB like the LDS) for the workgroup's first row, the tail repeating the last one; a.vcode / a.vcptr / a.uw / a.vdict /
 // a.vdptr / a.dst: k_vidx's.
 // Same products, same sequential row sum: bit-identical to k_vidx and k_sellp.
 constexpr int VW_MAX_LDS = 64 * 1024;          // windows + dictionaries + table: at least two workgroups per CU
@@ -888,7 +894,11 @@ struct VwHead {
     int win[8];           // (LDS base, omin - base) of the first four windows (unused ones: base INT32_MAX)
     int lp, tn;           // 16-bit words of the table: the patterns' lengths, all of it (multiples of 8)
     int vd_u;             // every dictionary of the operator holds this many values, or 0: they differ, read a.vdptr
+    int lmin, lmax;       // the shortest and the longest pattern: positions below lmin are real in every row, none at or beyond lmax in any
+    int ntrip;            // the windows are staged one by one in this many trips (xwin_stage.h), or 0: the flat staging
+    xwstage::Trip trip[xwstage::MAX_TRIPS];      // ... the sizes of the first four windows next to their bases, trip by trip (unused: cnt 0)
 };
+typedef unsigned sk_u2w __attribute__((ext_vector_type(2)));
 template <int EPI, bool HALO, bool NT>
 __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h, int nrows) {
     extern __shared__ __attribute__((aligned(16))) double vw_lds[];
@@ -904,7 +914,9 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
     const int sc = live ? s : 0;                                   // ... reading slice 0's codes, which they never use
     const int r = r0 + tid;
     const bool row = r < nrows;                                    // (only inside live slices)
-    const int rc = row ? r : 0;                                    // a valid row for the loads of a lane without one
+    // a valid row for the loads of a lane without one: the workgroup's last.  Every per-row address below is a scalar base (the
+    // array at the workgroup's first row) plus this 32-bit lane offset
+    const unsigned tc = min((unsigned)tid, (unsigned)(nrows - 1 - r0));
     // ---- 1. every global load of the lane but the windows', at addresses formed from the arguments alone: where the slices have one
     // width and the dictionaries one length (the 7-point levels) these are the addresses, and no branch stands before the loads
     int cp = sc * uw * 64, w8 = uw;                                // (uw = 0: slice 0's codes, read again below)
@@ -912,17 +924,19 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
     const int g0 = b * D, g1 = g0 + D < ngd ? g0 + D : ngd, gw = live ? s >> 2 : g0;      // the workgroup's first, one past its last, the wave's own
     int d0 = g0 * vd_u, dn = (g1 - g0) * vd_u, dw0 = (gw - g0) * vd_u;                     // the workgroup's values, contiguous: dn <= D * VI_MAX = R; where the wave's begin
     const bool ntv = NT && s >= a.nt_from;
-    const sk_u2v *c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp) + lane;
-    auto ld_codes = [&](int j) { sk_u2v v; if (ntv) v = __builtin_nontemporal_load(c8 + (j >> 3) * 64); else v = c8[(j >> 3) * 64]; return v; };
+    const sk_u2v *c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp);
+    auto ld_codes = [&](int j) { const unsigned i = (unsigned)((j >> 3) * 64 + lane); sk_u2v v; if (ntv) v = __builtin_nontemporal_load(c8 + i); else v = c8[i]; return v; };
     int pid;
-    if constexpr (NT) pid = __builtin_nontemporal_load(a.dst + rc); else pid = a.dst[rc];
+    if constexpr (NT) pid = __builtin_nontemporal_load(a.dst + r0 + tc); else pid = (a.dst + r0)[tc];
     constexpr bool PREF = !HALO && (EPI == EPI_JACOBI || EPI == EPI_RESIDUAL);
     double pre_b = 0.0, pre_dg = 0.0, pre_u = 0.0;
     if constexpr (PREF) {
-        pre_b = ld_once<NT>(a.rhs + rc);
-        if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(a.inv_diag + rc); pre_u = a.u[rc]; }
+        pre_b = ld_once<NT>(a.rhs + r0 + tc);
+        if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(a.inv_diag + r0 + tc); pre_u = (a.u + r0)[tc]; }
     }
     const int S = h.S, lp = h.lp, n8 = h.tn >> 3;                  // (n8 >= 1: 16-byte chunks of the table)
+    const int lmin = h.lmin, lmax = h.lmax;
+    asm volatile("" ::"s"(lmin), "s"(lmax));                       // in registers HERE: the compiler would sink their argument load behind the barrier, into every wave's row loop
     double *xw = vw_lds, *dict = vw_lds + ((S + 2) & ~1);          // (xw[S]: a spare slot for the staging lanes past the windows)
     unsigned short *tab = reinterpret_cast<unsigned short *>(dict + D * VI_MAX);
     const sk_u4v *gt = reinterpret_cast<const sk_u4v *>(a.ptab);
@@ -931,18 +945,18 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
     sk_u2v cc = ld_codes(0);                                       // (an empty slice reads the next one's, or the 512 bytes vcode is padded by)
     // a lane beyond the dictionary reads its first value again: with dn = 0 that is the next workgroup's, or -- behind the last one -- the
     // element build_vidx pads vdict by.  It lands in a slot of dict no code points at (tid < R = D * VI_MAX)
-    double dv0 = a.vdict[d0 + (tid < dn ? tid : 0)];               // (vd_u = 0: vdict[0], read again below)
+    double dv0 = (a.vdict + d0)[tid < dn ? (unsigned)tid : 0u];    // (vd_u = 0: vdict[0], read again below)
     // ---- 2. slices of differing widths, dictionaries of differing lengths: one scalar round trip each, then the load once more
     if (!uw) {
         cp = a.vcptr[sc]; w8 = (a.vcptr[sc + 1] - cp) >> 6;
-        c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp) + lane;
+        c8 = reinterpret_cast<const sk_u2v *>(a.vcode + cp);
         cc = ld_codes(0);
     }
     w8 = live ? w8 : 0;
     if (!vd_u) {
         const int p0 = a.vdptr[g0], p1 = a.vdptr[g1], pw = a.vdptr[gw];
         d0 = p0; dn = p1 - p0; dw0 = pw - p0;
-        dv0 = a.vdict[d0 + (tid < dn ? tid : 0)];
+        dv0 = (a.vdict + d0)[tid < dn ? (unsigned)tid : 0u];
     }
     // ---- 3. windows (zero where they leave the vector), dictionaries, table -> LDS
     const int xlast = a.ncols - 1;
@@ -971,10 +985,31 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
 #pragma unroll
         for (int u = 0; u < 4; ++u) xw[ii[u] < S ? ii[u] : S] = v[u];
     };
-    stage4(0);
-    dict[tid] = dv0;
-    if (tid < n8) lt[tid] = tc0;
-    for (int i0 = 4 * R; i0 < S; i0 += 4 * R) stage4(i0);
+    // window by window (xwin_stage.h: at most four windows, S <= 4 R, x within the descriptor's reach): a trip's window and LDS base
+    // are scalars, the range check of the buffer load returns the zeros, the lanes past a window's size write the spare slot
+    auto ldx = [&](const xwstage::Trip &t) {
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.x), 0, 8 * a.ncols, 0x00020000);
+        const sk_u2w q = __builtin_amdgcn_raw_buffer_load_b64(rs, xwstage::byte_offset(r0, t, tid), 0, 0);
+        double d;
+        __builtin_memcpy(&d, &q, sizeof d);
+        return d;
+    };
+    if (h.ntrip) {
+        double v[xwstage::MAX_TRIPS];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ldx(h.trip[u]);          // (the 7-point levels: 1 + 2 + 1; an unused trip loads nothing)
+        if (h.ntrip > 4) { v[4] = ldx(h.trip[4]); v[5] = ldx(h.trip[5]); }
+        dict[tid] = dv0;
+        if (tid < n8) lt[tid] = tc0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) xw[xwstage::slot(h.trip[u], tid, S)] = v[u];
+        if (h.ntrip > 4) { xw[xwstage::slot(h.trip[4], tid, S)] = v[4]; xw[xwstage::slot(h.trip[5], tid, S)] = v[5]; }
+    } else {
+        stage4(0);
+        dict[tid] = dv0;
+        if (tid < n8) lt[tid] = tc0;
+        for (int i0 = 4 * R; i0 < S; i0 += 4 * R) stage4(i0);
+    }
     for (int i = tid + R; i < n8; i += R) lt[i] = gt[i];
     __syncthreads();
     if (!live) return;
@@ -982,33 +1017,52 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
     if (!row) pid = 0;
     const int len = row ? (int)tab[pid] : 0;
     const unsigned short *pos = tab + lp + pid * a.pt_w;
-    const double *xr = xw + tid, *dw = dict + dw0;
+    const char *xr = reinterpret_cast<const char *>(xw + tid);
+    const double *dw = dict + dw0;
     double sum = 0.0;
-    for (int j = 0; j < w8; j += 8) {                              // (w8 <= pt_w: no row is longer than the longest pattern)
+    // N positions of a trip, the first four without a select where every row holds them (FREE4).  A position past the row's length
+    // adds -0.0, which changes no sum (signed zeros and NaNs included): the row sum stays k_vidx's, bit for bit, without a branch
+    auto trip = [&](auto NN, auto FREE4, int j, const sk_u2v cc) {
+        constexpr int N = decltype(NN)::value;
         const sk_u4v pp = *reinterpret_cast<const sk_u4v *>(pos + j);
-        sk_u2v cn = cc;
-        if (j + 8 < w8) cn = ld_codes(j + 8);
-        double xx[8], dv[8];
+        double xx[N], dv[N];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
+        for (int u = 0; u < N; ++u) {
             const unsigned w = u < 2 ? pp.x : u < 4 ? pp.y : u < 6 ? pp.z : pp.w;
-            xx[u] = xr[(u & 1) ? (w >> 16) : (w & 0xffffu)];
+            xx[u] = *reinterpret_cast<const double *>(xr + ((u & 1) ? (w >> 16) : (w & 0xffffu)));
             dv[u] = dw[((u < 4 ? cc.x : cc.y) >> (8 * (u & 3))) & 0xffu];
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {                              // a position past the row's length adds -0.0, which changes no sum (signed zeros
-            const double p = dv[u] * xx[u];                        // and NaNs included): the row sum stays k_vidx's, bit for bit, without a branch
-            sum += j + u < len ? p : -0.0;
+        for (int u = 0; u < N; ++u) {
+            const double p = dv[u] * xx[u];
+            if (decltype(FREE4)::value && u < 4) sum += p;
+            else sum += j + u < len ? p : -0.0;
+        }
+    };
+    for (int j = 0; j < w8; j += 8) {                              // (w8 <= pt_w: no row is longer than the longest pattern)
+        sk_u2v cn = cc;
+        if (j + 8 < w8) cn = ld_codes(j + 8);
+        // both wave-uniform: the positions at or beyond the longest pattern are not computed (never fewer than four, though: the
+        // lengths 1 ... 3 share the body of 4), those below the shortest take no select
+        const int n = lmax - j;
+        const bool f4 = j + 4 <= lmin;
+        auto go = [&](auto NN) { if (f4) trip(NN, std::true_type{}, j, cc); else trip(NN, std::false_type{}, j, cc); };
+        switch (n < 4 ? 4 : n > 8 ? 8 : n) {
+        case 4: go(std::integral_constant<int, 4>{}); break;
+        case 5: go(std::integral_constant<int, 5>{}); break;
+        case 6: go(std::integral_constant<int, 6>{}); break;
+        case 7: go(std::integral_constant<int, 7>{}); break;
+        default: go(std::integral_constant<int, 8>{}); break;
         }
         cc = cn;
     }
     if (row) {
         if constexpr (PREF) {                                      // epilogue<>'s arithmetic on the operands fetched at the top
-            if constexpr (EPI == EPI_RESIDUAL) st_y<NT>(a, a.y + r, sum - pre_b);
+            if constexpr (EPI == EPI_RESIDUAL) st_y<NT>(a, a.y + r0 + (unsigned)tid, sum - pre_b);
             else {
                 double t = sum - pre_b;
                 t *= pre_dg * a.c0;
-                st_y<NT>(a, a.y + r, pre_u - t);
+                st_y<NT>(a, a.y + r0 + (unsigned)tid, pre_u - t);
             }
         } else epilogue<EPI, HALO, NT>(a, r, sum);
     }

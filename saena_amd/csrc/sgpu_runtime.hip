@@ -213,7 +213,7 @@ struct CsrPart {
     int             vi_uw8 = 0;           // every slice has this many code positions (a multiple of 8), or 0: read vi_cptr
     int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
     // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
-    // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS positions; vw_rows: the R in
+    // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS byte offsets; vw_rows: the R in
     // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays; head: what of them (and of vi_dptr) every launch passes by value
     struct XWin { DevArr<unsigned short> tab; DevArr<int> win; sk::VwHead head{}; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
     XWin            vw[3];
@@ -1177,7 +1177,8 @@ int build_vidx(CsrPart &P) {
 // The x-window launch mode of k_vidx for workgroups of R = 256 << k rows: build_sellp's ONE pattern table (read back from the
 // device -- the host copy goes when the plan settles), its offsets clustered as build_sellpx does with the gap rule at R, the
 // windows [r0 + omin_c, r0 + R + omax_c) laid out one after the other, and the table rewritten ONCE for the whole operator as
-// 16-bit LDS positions for a workgroup's first row.  Refused (ok stays false, *why says it): rowbase and per-workgroup tables,
+// 16-bit LDS byte offsets for a workgroup's first row; the head (VwHead) carries the shortest and the longest pattern and, where
+// xwin_stage.h's rule allows it, the trips that stage the windows one by one.  Refused (ok stays false, *why says it): rowbase and per-workgroup tables,
 // more than SPX_MAXWIN windows, positions beyond 16 bits, more LDS than VW_MAX_LDS (two workgroups per CU).
 int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     CsrPart::XWin &X = P.vw[k];
@@ -1226,7 +1227,7 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
         for (int j = 0; j < wp; ++j) {
             if (j < c[0]) {
                 const int w = (int)(std::upper_bound(omin.begin(), omin.end(), c[1 + j]) - omin.begin()) - 1;      // the window that holds the offset
-                last = (unsigned short)(base[(size_t)w] + (c[1 + j] - omin[(size_t)w]));
+                last = (unsigned short)(8 * (base[(size_t)w] + (c[1 + j] - omin[(size_t)w])));      // (a byte offset: S doubles fit the LDS cap, so below 64 KiB)
             }
             t16[(size_t)lp + (size_t)i * wp + j] = last;        // (the tail repeats the last position: read, never added)
         }
@@ -1246,10 +1247,19 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     X.head.nwin = nwin; X.head.S = (int)S;
     std::copy(win.begin() + 2, win.begin() + 10, X.head.win);
     X.head.lp = lp; X.head.tn = (int)words; X.head.vd_u = vd_u;
+    X.head.lmin = X.head.lmax = tab[0];
+    for (int i = 1; i < npat; ++i) { X.head.lmin = std::min(X.head.lmin, tab[(size_t)i * (W + 1)]); X.head.lmax = std::max(X.head.lmax, tab[(size_t)i * (W + 1)]); }
+    // window by window where xwin_stage.h's rule allows it (else ntrip = 0: the flat staging)
+    X.head.ntrip = 0;
+    if (xwstage::per_window(nwin, S, R, P.ncols, M, omin.front(), omax.back())) {
+        std::vector<int> size;
+        for (int c = 0; c < nwin; ++c) size.push_back(R + (omax[(size_t)c] - omin[(size_t)c]));
+        X.head.ntrip = xwstage::trips(nwin, base.data(), omin.data(), size.data(), R, X.head.trip);
+    }
     X.wp = wp; X.lds = (int)lds; X.ok = true;
     if (std::getenv("SAENA_SETUP_TIMING"))
-        fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row)\n",
-                R, nwin, (long long)S, R / sk::BLOCK, (long long)words, (double)lds / 1024.0, 8.0 * (double)S / R);
+        fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row); staged %s (%d trips)\n",
+                R, nwin, (long long)S, R / sk::BLOCK, (long long)words, (double)lds / 1024.0, 8.0 * (double)S / R, X.head.ntrip ? "window by window" : "flat", X.head.ntrip);
     return SGPU_OK;
 }
 
@@ -1753,7 +1763,7 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
         a.vcode = P.vi.vi_code; a.vcptr = P.vi.vi_cptr; a.vdict = P.vi.vi_dict; a.vdptr = P.vi.vi_dptr; a.uw = P.vi_uw8;
         const bool nt = row_pattern_nt(a, P.vi_bytes, a.nblk, (double)P.nnz / (double)std::max(1, a.nblk));     // (about a byte of codes per entry)
         const size_t lds = ((size_t)((P.sp_n * (P.sp_w + 1) + 1) & ~1)) * sizeof(int) + sk::VI_MAX * sizeof(double);
-        if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS positions
+        if (P.vw_rows) {                                          // x in LDS windows: workgroups of vw_rows rows, the table as 16-bit LDS byte offsets
             const int k = xwin_slot(P.vw_rows), spb = P.vw_rows / 64;
             const CsrPart::XWin &X = P.vw[k];
             if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");

@@ -10,6 +10,9 @@ but the compiler), or an assembly file made that way is read with --asm.
     tools/kernel_waits.py 'k_vidxw<0, false, false>'                    # this tree
     tools/kernel_waits.py --tree ../parent 'k_vidxw<1, false, false>'   # another checkout
     tools/kernel_waits.py --asm runtime.s --list k_vidxw                # the kernels of an assembly file whose names hold k_vidxw
+    tools/kernel_waits.py --counts 'k_vidxw<0, false, false>'           # instructions per class and basic block, the whole kernel
+
+--counts is a STATIC count: what a launch executes is the sum over the blocks its waves pass through, once per pass.
 
 A kernel is named as the demangler prints it; blanks are ignored and any unique part of the name will do."""
 import argparse
@@ -121,6 +124,56 @@ def listing(body, argptr=None):
     return out, n, False
 
 
+CLASSES = ("VALU", "SALU", "s_nop", "SMEM", "LDS", "VMEM load", "VMEM store", "wait", "branch", "other")
+
+
+def classify(mnem):
+    if mnem.startswith("v_"):
+        return "VALU"
+    if mnem.startswith("ds_"):
+        return "LDS"
+    if mnem.startswith(("s_load", "s_buffer_load")):
+        return "SMEM"
+    if mnem.startswith(("global_load", "flat_load", "buffer_load", "scratch_load")):
+        return "VMEM load"
+    if mnem.startswith(("global_", "flat_", "buffer_", "scratch_")):
+        return "VMEM store"
+    if mnem.startswith("s_waitcnt"):
+        return "wait"
+    if mnem.startswith("s_nop"):
+        return "s_nop"
+    if mnem.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")):
+        return "branch"
+    if mnem.startswith("s_barrier"):
+        return "other"
+    return "SALU" if mnem.startswith("s_") else "other"
+
+
+def counts(body):
+    """-> [(block label, {class: instructions})] in program order (the entry block is "entry"), over the whole kernel"""
+    blocks = [("entry", dict.fromkeys(CLASSES, 0))]
+    for ln in body:
+        text = ln.split(";")[0].strip()
+        if not text or text.startswith("."):
+            m = re.match(r"^(\.LBB[\w.]*):", text)
+            if m:
+                blocks.append((m.group(1), dict.fromkeys(CLASSES, 0)))
+            continue
+        blocks[-1][1][classify(text.split()[0])] += 1
+    return blocks
+
+
+def counts_table(blocks):
+    out = [f"   {'block':<12s}" + "".join(f"{c:>11s}" for c in CLASSES) + f"{'all':>8s}"]
+    total = dict.fromkeys(CLASSES, 0)
+    for label, n in blocks:
+        out.append(f"   {label:<12s}" + "".join(f"{n[c]:11d}" for c in CLASSES) + f"{sum(n.values()):8d}")
+        for c in CLASSES:
+            total[c] += n[c]
+    out.append(f"   {'all blocks':<12s}" + "".join(f"{total[c]:11d}" for c in CLASSES) + f"{sum(total.values()):8d}")
+    return out
+
+
 def summary(rows):
     """how many of each kind the listing holds -- on every path together: which blocks a launch runs is for the reader to follow"""
     kinds = [r[6:19].strip() for r in rows if not r.endswith(":")]
@@ -133,6 +186,7 @@ def main():
     ap.add_argument("--tree", default=os.path.dirname(HERE), help="the checkout to compile (default: this one)")
     ap.add_argument("--asm", help="read this assembly file instead of compiling")
     ap.add_argument("--keep-asm", help="keep the compiled assembly here")
+    ap.add_argument("--counts", action="store_true", help="print the static instruction counts per class and basic block of the whole kernel instead")
     ap.add_argument("--list", metavar="PART", help="print the demangled names that hold PART and stop")
     a = ap.parse_args()
     hipcc = None
@@ -152,8 +206,12 @@ def main():
             if len(hits) != 1:
                 print(f"{want!r} names {len(hits)} kernels" + "".join("\n  " + names[h] for h in hits), file=sys.stderr)
                 return 1
-            rows, n, found = listing(bodies[hits[0]], argptr.get(hits[0]))
             print(f"== {names[hits[0]]}")
+            if a.counts:
+                print("\n".join(counts_table(counts(bodies[hits[0]]))))
+                print()
+                continue
+            rows, n, found = listing(bodies[hits[0]], argptr.get(hits[0]))
             print(f"   entry to the first s_barrier: {n} instructions" if found else f"   no s_barrier: all {n} instructions")
             print("\n".join(rows))
             print("\n".join("   " + s for s in summary(rows)))
