@@ -166,6 +166,13 @@ int sgpu_op_get_variant(const sgpu_op *op, int *variant, const char **kernel_nam
  * sgpu_op_get_x_windows: the rows per workgroup in use, 0 = direct gathers (or another variant). */
 int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup);
 int sgpu_op_get_x_windows(const sgpu_op *op, int *rows_per_workgroup);
+/* which kernel the x-window mode runs on this operator: 0 the general k_vidxw (or the mode is off), 1 k_vidxw_fast, the common path
+ * as a kernel of its own (workgroups of 256 / 512 rows, one slice width, one dictionary length, at most four trips; launches
+ * without a halo of the product, the residual and the Jacobi sweep; SAENA_VIDXW_FAST=0, read when the windows are built, keeps
+ * the general kernel), 2 k_vidxw_fast with dictionaries of at most two values in scalar registers.  Once the operator was
+ * launched in the mode: what its LAST launch ran (a halo launch or another epilogue of an eligible operator runs k_vidxw).
+ * Results are bit-identical whichever runs. */
+int sgpu_op_get_x_window_kernel(const sgpu_op *op, int *kernel);
 /* time the (variant, lanes) candidates that apply to this operator and keep the fastest (plan-time autotune; no
  * collective).  Call it right after sgpu_op_create: operators of up to 768 entries per row hold a host copy of their
  * values (8 B per entry) for the re-ordered forms from the create until this call -- or until sgpu_op_destroy. */

@@ -71,6 +71,7 @@ SYMBOLS = {
     "sgpu_op_get_variant": (C.c_int, [_VP, _PI, C.POINTER(C.c_char_p)]),
     "sgpu_op_set_x_windows": (C.c_int, [_VP, C.c_int]),
     "sgpu_op_get_x_windows": (C.c_int, [_VP, _PI]),
+    "sgpu_op_get_x_window_kernel": (C.c_int, [_VP, _PI]),
     "sgpu_spmv": (C.c_int, [_VP, _VP, _VP]),
     "sgpu_residual": (C.c_int, [_VP, _VP, _VP, _VP]),
     "sgpu_residual_negative": (C.c_int, [_VP, _VP, _VP, _VP]),
@@ -421,6 +422,13 @@ class Operator:
         """rows per workgroup of the x-window mode in use, 0 = direct gathers"""
         v = C.c_int()
         check(lib().sgpu_op_get_x_windows(self.h, C.byref(v)))
+        return v.value
+
+    def x_window_kernel(self):
+        """which kernel the x-window mode runs (of the last launch in the mode, once there was one): 0 k_vidxw or the mode is off,
+        1 k_vidxw_fast with its dictionaries in LDS, 2 k_vidxw_fast with dictionaries of at most two values in scalar registers"""
+        v = C.c_int()
+        check(lib().sgpu_op_get_x_window_kernel(self.h, C.byref(v)))
         return v.value
 
     def exchange_mode(self):

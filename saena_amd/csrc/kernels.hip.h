@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "xwin_stage.h"
+#include "vw_fast.h"
 
 namespace sk {
 
@@ -899,6 +900,64 @@ struct VwHead {
     xwstage::Trip trip[xwstage::MAX_TRIPS];      // ... the sizes of the first four windows next to their bases, trip by trip (unused: cnt 0)
 };
 typedef unsigned sk_u2w __attribute__((ext_vector_type(2)));
+// One of two wave-uniform 64-bit patterns by bit `bit` of w: a sign-extending bit-field extract makes the mask, two bit-field inserts
+// pick the halves.  No arithmetic touches the value: signed zeros and NaN payloads come through as stored.
+__device__ __forceinline__ double vw_pick(unsigned w, int bit, unsigned long long s0, unsigned long long s1) {
+    const unsigned m = (unsigned)((int)(w << (31 - bit)) >> 31);
+    const unsigned lo = ((unsigned)s0 & ~m) | ((unsigned)s1 & m), hi = ((unsigned)(s0 >> 32) & ~m) | ((unsigned)(s1 >> 32) & m);
+    return __hiloint2double((int)hi, (int)lo);
+}
+// The row of k_vidxw and of k_vidxw_fast: dictionary value x window entry in the table's order, eight positions per turn.
+// pos: the row's pattern (LDS byte offsets for the workgroup's first row), xr: the lane's row in the windows, cc: the codes of the
+// first turn, ld_codes(j): those of positions j ... j + 7; len: the row's length; w8: the slice's positions; lmin / lmax: the shortest
+// and the longest pattern, body0 = vwfast::body(lmin, lmax, 0).  The values: dw[code] (the wave's dictionary in LDS), or with SD one of
+// the two values s0 / s1 of a dictionary that stays in scalar registers, by bit 0 of the code.
+template <bool SD, class LdCodes>
+__device__ __forceinline__ double vw_row_sum(const unsigned short *pos, const char *xr, const double *dw, unsigned long long s0, unsigned long long s1,
+                                             int len, int w8, int lmin, int lmax, int body0, sk_u2v cc, LdCodes ld_codes) {
+    double sum = 0.0;
+    // N positions of a trip, the first four without a select where every row holds them (FREE4).  A position past the row's length
+    // adds -0.0, which changes no sum (signed zeros and NaNs included): the row sum stays k_vidx's, bit for bit, without a branch
+    auto trip = [&](auto NN, auto FREE4, int j, const sk_u2v cc) {
+        constexpr int N = decltype(NN)::value;
+        const sk_u4v pp = *reinterpret_cast<const sk_u4v *>(pos + j);
+        double xx[N], dv[N];
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const unsigned w = u < 2 ? pp.x : u < 4 ? pp.y : u < 6 ? pp.z : pp.w;
+            xx[u] = *reinterpret_cast<const double *>(xr + ((u & 1) ? (w >> 16) : (w & 0xffffu)));
+            if constexpr (SD) dv[u] = vw_pick(u < 4 ? cc.x : cc.y, 8 * (u & 3), s0, s1);
+            else dv[u] = dw[((u < 4 ? cc.x : cc.y) >> (8 * (u & 3))) & 0xffu];
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const double p = dv[u] * xx[u];
+            if (decltype(FREE4)::value && u < 4) sum += p;
+            else sum += j + u < len ? p : -0.0;
+        }
+    };
+    for (int j = 0; j < w8; j += 8) {                              // (w8 <= pt_w: no row is longer than the longest pattern)
+        sk_u2v cn = cc;
+        if (j + 8 < w8) cn = ld_codes(j + 8);
+        // wave-uniform: the positions at or beyond the longest pattern are not computed (never fewer than four, though: the
+        // lengths 1 ... 3 share the body of 4), those below the shortest take no select
+        auto go = [&](auto NN, auto FREE4) { trip(NN, FREE4, j, cc); };
+        switch (j ? vwfast::body(lmin, lmax, j) : body0) {
+        case 0: go(std::integral_constant<int, 4>{}, std::false_type{}); break;
+        case 1: go(std::integral_constant<int, 4>{}, std::true_type{}); break;
+        case 2: go(std::integral_constant<int, 5>{}, std::false_type{}); break;
+        case 3: go(std::integral_constant<int, 5>{}, std::true_type{}); break;
+        case 4: go(std::integral_constant<int, 6>{}, std::false_type{}); break;
+        case 5: go(std::integral_constant<int, 6>{}, std::true_type{}); break;
+        case 6: go(std::integral_constant<int, 7>{}, std::false_type{}); break;
+        case 7: go(std::integral_constant<int, 7>{}, std::true_type{}); break;
+        case 8: go(std::integral_constant<int, 8>{}, std::false_type{}); break;
+        default: go(std::integral_constant<int, 8>{}, std::true_type{}); break;
+        }
+        cc = cn;
+    }
+    return sum;
+}
 template <int EPI, bool HALO, bool NT>
 __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h, int nrows) {
     extern __shared__ __attribute__((aligned(16))) double vw_lds[];
@@ -1013,49 +1072,12 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
     for (int i = tid + R; i < n8; i += R) lt[i] = gt[i];
     __syncthreads();
     if (!live) return;
-    // ---- 4. the row: dictionary value x window entry, in the table's order
+    // ---- 4. the row: dictionary value x window entry, in the table's order (vw_row_sum)
     if (!row) pid = 0;
     const int len = row ? (int)tab[pid] : 0;
     const unsigned short *pos = tab + lp + pid * a.pt_w;
     const char *xr = reinterpret_cast<const char *>(xw + tid);
-    const double *dw = dict + dw0;
-    double sum = 0.0;
-    // N positions of a trip, the first four without a select where every row holds them (FREE4).  A position past the row's length
-    // adds -0.0, which changes no sum (signed zeros and NaNs included): the row sum stays k_vidx's, bit for bit, without a branch
-    auto trip = [&](auto NN, auto FREE4, int j, const sk_u2v cc) {
-        constexpr int N = decltype(NN)::value;
-        const sk_u4v pp = *reinterpret_cast<const sk_u4v *>(pos + j);
-        double xx[N], dv[N];
-#pragma unroll
-        for (int u = 0; u < N; ++u) {
-            const unsigned w = u < 2 ? pp.x : u < 4 ? pp.y : u < 6 ? pp.z : pp.w;
-            xx[u] = *reinterpret_cast<const double *>(xr + ((u & 1) ? (w >> 16) : (w & 0xffffu)));
-            dv[u] = dw[((u < 4 ? cc.x : cc.y) >> (8 * (u & 3))) & 0xffu];
-        }
-#pragma unroll
-        for (int u = 0; u < N; ++u) {
-            const double p = dv[u] * xx[u];
-            if (decltype(FREE4)::value && u < 4) sum += p;
-            else sum += j + u < len ? p : -0.0;
-        }
-    };
-    for (int j = 0; j < w8; j += 8) {                              // (w8 <= pt_w: no row is longer than the longest pattern)
-        sk_u2v cn = cc;
-        if (j + 8 < w8) cn = ld_codes(j + 8);
-        // both wave-uniform: the positions at or beyond the longest pattern are not computed (never fewer than four, though: the
-        // lengths 1 ... 3 share the body of 4), those below the shortest take no select
-        const int n = lmax - j;
-        const bool f4 = j + 4 <= lmin;
-        auto go = [&](auto NN) { if (f4) trip(NN, std::true_type{}, j, cc); else trip(NN, std::false_type{}, j, cc); };
-        switch (n < 4 ? 4 : n > 8 ? 8 : n) {
-        case 4: go(std::integral_constant<int, 4>{}); break;
-        case 5: go(std::integral_constant<int, 5>{}); break;
-        case 6: go(std::integral_constant<int, 6>{}); break;
-        case 7: go(std::integral_constant<int, 7>{}); break;
-        default: go(std::integral_constant<int, 8>{}); break;
-        }
-        cc = cn;
-    }
+    const double sum = vw_row_sum<false>(pos, xr, dict + dw0, 0ull, 0ull, len, w8, lmin, lmax, vwfast::body(lmin, lmax, 0), cc, ld_codes);
     if (row) {
         if constexpr (PREF) {                                      // epilogue<>'s arithmetic on the operands fetched at the top
             if constexpr (EPI == EPI_RESIDUAL) st_y<NT>(a, a.y + r0 + (unsigned)tid, sum - pre_b);
@@ -1065,6 +1087,119 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
                 st_y<NT>(a, a.y + r0 + (unsigned)tid, pre_u - t);
             }
         } else epilogue<EPI, HALO, NT>(a, r, sum);
+    }
+}
+
+// (a double in global memory, for a pointer that reached the kernel as an integer: the store then is a global store, not a flat one)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(1))) double sk_gdouble;
+#else
+typedef double sk_gdouble;
+#endif
+// k_vidxw's common path as a kernel of its own (vw_fast.h has the rule): R in {256, 512} a template parameter, no halo, the plain
+// product / residual / Jacobi sweep, one slice width, one dictionary length, one to four trips, a table of at most R chunks.  What
+// k_vidxw works out in scalar instructions in every wave -- the dictionaries of the workgroup, the LDS carve-up, a trip's offset and
+// slot base, which path and which body of the row loop to take -- arrives in ONE by-value struct in the form it is consumed; the
+// struct passes through asm statements at the top so that its loads form one batch with one wait, and no branch and no further
+// argument wait stands between that wait and the last global load.  The row sum is vw_row_sum, k_vidxw's.
+// SD: the dictionaries hold at most two values; the wave's two are loaded as scalars with the prologue's loads (the wave's dictionary
+// is uniform; vi_dict is padded by one element for the dictionary of ONE value at the end) and a position's value is picked by bit 0
+// of its code: no dictionary in LDS, no LDS read per position for the value.
+// blockDim.x = R; dynamic LDS: [windows of x][R / 256 dictionaries of VI_MAX unless SD][table] (vwfast::plan).
+template <int R, int EPI, bool NT, bool SD>
+__global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
+    static_assert((R == 256 || R == 512) && (EPI == EPI_SPMV || EPI == EPI_RESIDUAL || EPI == EPI_JACOBI), "vw_fast.h: the rule");
+    extern __shared__ __attribute__((aligned(16))) double vw_lds[];
+    constexpr int SH = R == 256 ? 2 : 3, D = R >> 8;                // log2(slices) and dictionaries per workgroup
+    // the argument, whole, in scalar registers HERE: one batch of loads and one wait.  The compiler would sink each field's load to its
+    // first use, behind the barrier and into the row loop; as results of an asm statement they are neither sunk nor loaded again
+    vwfast::VwFast f = arg;
+    if constexpr (EPI == EPI_SPMV) f.rhs = nullptr;                 // (what an instantiation does not read is not loaded)
+    if constexpr (EPI != EPI_JACOBI) { f.inv_diag = nullptr; f.u = nullptr; f.c0 = 0.0; }
+    if constexpr (!NT) { f.nt_from = 0; f.st_plain = 0; }
+    if constexpr (SD) f.ngd = 0;
+    // (the arrays' pointers stay the argument's own, which the compiler knows to point at global memory: they are needed at once; y,
+    // needed last, passes as an integer)
+    unsigned long long y_bits = reinterpret_cast<unsigned long long>(f.y);
+    asm volatile("" : "+s"(f.trip[0].lds8), "+s"(f.trip[0].cnt), "+s"(f.trip[1].lds8), "+s"(f.trip[1].cnt), "+s"(f.trip[2].lds8), "+s"(f.trip[2].cnt),
+                      "+s"(f.trip[3].lds8), "+s"(f.trip[3].cnt), "+s"(f.S8), "+s"(f.dict_off), "+s"(f.tab_off), "+s"(f.pos_off), "+s"(f.pw2), "+s"(f.w8),
+                      "+s"(f.lmin), "+s"(f.lmax), "+s"(f.body0), "+s"(f.st_plain), "+s"(y_bits), "+s"(f.c0)
+                 : "s"(f.nrows), "s"(f.nblk), "s"(f.rq), "s"(f.rr), "s"(f.cbytes), "s"(f.n8), "s"(f.vd_u), "s"(f.ngd), "s"(f.xbytes), "s"(f.nt_from),
+                   "s"(f.trip[0].col), "s"(f.trip[1].col), "s"(f.trip[2].col), "s"(f.trip[3].col));      // (what is needed at once: named, so that it is of the batch)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const unsigned t8 = 8u * (unsigned)tid;
+    const int b = vwfast::remap((int)blockIdx.x, f.rq, f.rr);      // xcd_remap with its quotient and remainder from the plan
+    const int r0 = b * R;
+    const int s = __builtin_amdgcn_readfirstlane((b << SH) + (tid >> 6));
+    const bool live = s < f.nblk;                                  // (the last workgroup's spare waves still stage and meet the barrier)
+    const int sc = live ? s : 0;                                   // ... reading slice 0's codes, which they never use
+    const bool row = r0 + tid < f.nrows;
+    const unsigned tc = min((unsigned)tid, (unsigned)(f.nrows - 1 - r0));      // a valid row for the loads of a lane without one
+    // ---- 1. every global load of the lane: codes, pattern id, the epilogue's operands, the dictionary, a table chunk, the windows
+    const bool ntv = NT && s >= f.nt_from;
+    const sk_u2v *c8 = reinterpret_cast<const sk_u2v *>(f.vcode + sc * f.cbytes);
+    auto ld_codes = [&](int j) { const unsigned i = (unsigned)((j >> 3) * 64 + lane); sk_u2v v; if (ntv) v = __builtin_nontemporal_load(c8 + i); else v = c8[i]; return v; };
+    int pid;
+    if constexpr (NT) pid = __builtin_nontemporal_load(f.dst + r0 + tc); else pid = (f.dst + r0)[tc];
+    double pre_b = 0.0, pre_dg = 0.0, pre_u = 0.0;
+    if constexpr (EPI != EPI_SPMV) {
+        pre_b = ld_once<NT>(f.rhs + r0 + tc);
+        if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(f.inv_diag + r0 + tc); pre_u = (f.u + r0)[tc]; }
+    }
+    const sk_u4v tc0 = reinterpret_cast<const sk_u4v *>(f.ptab)[tid < f.n8 ? tid : 0];
+    sk_u2v cc = ld_codes(0);
+    unsigned long long s0 = 0, s1 = 0, d0v = 0, d1v = 0;
+    double dv0 = 0.0;
+    if constexpr (SD) {                                            // the wave's dictionary (a spare wave: the workgroup's first), as two scalars
+        const unsigned long long *dp = reinterpret_cast<const unsigned long long *>(f.vdict) + (live ? s >> 2 : b * D) * f.vd_u;
+        d0v = dp[0]; d1v = dp[1];                                  // (uniform addresses: scalar loads, or vector loads of one value)
+    } else {
+        // the workgroup's values, contiguous; a lane beyond them reads the first again (k_vidxw: it lands in a slot no code points at)
+        const int g0 = b * D, g1 = g0 + D < f.ngd ? g0 + D : f.ngd, dn = (g1 - g0) * f.vd_u;
+        dv0 = (f.vdict + g0 * f.vd_u)[tid < dn ? (unsigned)tid : 0u];
+    }
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(f.x), 0, (int)f.xbytes, 0x00020000);
+    double v[vwfast::TRIPS];
+#pragma unroll
+    for (int u = 0; u < vwfast::TRIPS; ++u) {                      // xwstage::byte_offset: r0, the window and the lane all in the vector offset
+        const sk_u2w q = __builtin_amdgcn_raw_buffer_load_b64(rs, 8u * (unsigned)(r0 + f.trip[u].col) + t8, 0, 0);
+        __builtin_memcpy(&v[u], &q, sizeof(double));
+    }
+    // every load is issued: the table chunk and the scalar dictionary are pinned HERE, in front of the LDS writes that wait for the
+    // loads anyway (left alone, the chunk's load sinks into the branch around its write and the dictionary's behind the barrier)
+    sk_u4v tcw = tc0;
+    asm volatile("" : "+v"(tcw));
+    if constexpr (SD) {
+        auto uni = [](unsigned long long q) { return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)q) |
+                                                     (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(q >> 32)) << 32; };
+        s0 = uni(d0v); s1 = uni(d1v);
+        asm volatile("" : "+s"(s0), "+s"(s1));
+    }
+    // ---- 2. -> LDS, at the byte offsets of the plan
+    char *lds = reinterpret_cast<char *>(vw_lds);
+    if constexpr (!SD) *reinterpret_cast<double *>(lds + f.dict_off + t8) = dv0;
+    if (tid < f.n8) *reinterpret_cast<sk_u4v *>(lds + f.tab_off + 2 * t8) = tcw;
+#pragma unroll
+    for (int u = 0; u < vwfast::TRIPS; ++u) *reinterpret_cast<double *>(lds + (tid < f.trip[u].cnt ? f.trip[u].lds8 + (int)t8 : f.S8)) = v[u];
+    __syncthreads();
+    if (!live) return;
+    // ---- 3. the row
+    if (!row) pid = 0;
+    const int len = row ? (int)reinterpret_cast<const unsigned short *>(lds + f.tab_off)[pid] : 0;
+    const unsigned short *pos = reinterpret_cast<const unsigned short *>(lds + f.pos_off + pid * f.pw2);
+    const double *dw = reinterpret_cast<const double *>(lds + f.dict_off) + (D > 1 ? __builtin_amdgcn_readfirstlane(tid >> 8) * f.vd_u : 0);
+    const double sum = vw_row_sum<SD>(pos, lds + t8, dw, s0, s1, len, f.w8, f.lmin, f.lmax, f.body0, cc, ld_codes);
+    if (row) {
+        sk_gdouble *yp = reinterpret_cast<sk_gdouble *>(y_bits) + r0 + (unsigned)tid;
+        double out = sum;                                          // epilogue<>'s arithmetic on the operands fetched at the top
+        if constexpr (EPI == EPI_RESIDUAL) out = sum - pre_b;
+        if constexpr (EPI == EPI_JACOBI) {
+            double t = sum - pre_b;
+            t *= pre_dg * f.c0;
+            out = pre_u - t;
+        }
+        if constexpr (NT) { if (f.st_plain) *yp = out; else __builtin_nontemporal_store(out, yp); }
+        else *yp = out;
     }
 }
 

@@ -215,9 +215,13 @@ struct CsrPart {
     // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
     // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS byte offsets; vw_rows: the R in
     // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays; head: what of them (and of vi_dptr) every launch passes by value
-    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; sk::VwHead head{}; int wp = 0, lds = 0; bool ok = false; char tried = 0; };
+    // fast: the operator's part of k_vidxw_fast's argument where vw_fast.h's rule takes the operator at this R (fast_kind 1: dictionaries
+    // in LDS, 2: in scalar registers; 0: the general kernel, fast_clause says which clause refused), fast_lds: its LDS bytes
+    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; sk::VwHead head{}; int wp = 0, lds = 0; bool ok = false; char tried = 0;
+                  vwfast::VwFast fast{}; int fast_kind = 0, fast_clause = 0, fast_lds = 0; };
     XWin            vw[3];
     int             vw_rows = 0;
+    mutable int     vw_last = -1;         // what the last launch in the mode ran (0 k_vidxw, 1 / 2 k_vidxw_fast as fast_kind), -1: none since the mode was set
     // x in LDS (variant 10): absolute 16-bit column ids and nnz-balanced row chunks, one per CU.  The chunk plan (k_sellx is built
     // on top of it) ...
     struct XldsPlan {
@@ -1257,9 +1261,24 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
         X.head.ntrip = xwstage::trips(nwin, base.data(), omin.data(), size.data(), R, X.head.trip);
     }
     X.wp = wp; X.lds = (int)lds; X.ok = true;
-    if (std::getenv("SAENA_SETUP_TIMING"))
+    // the common-path kernel where vw_fast.h's rule takes the operator at this R; the environment is read per operator, so that one
+    // process can build both paths
+    const char *fast_env = std::getenv("SAENA_VIDXW_FAST");
+    X.fast_clause = vwfast::refused(R, P.vi_uw8, vd_u, X.head.ntrip, (int)(words >> 3));
+    if (X.fast_clause == vwfast::TAKEN && fast_env && std::atoi(fast_env) == 0) X.fast_clause = vwfast::SWITCHED_OFF;
+    X.fast_kind = vwfast::kind(X.fast_clause, vd_u);
+    X.fast = vwfast::VwFast{};
+    if (X.fast_kind)
+        X.fast_lds = vwfast::plan(X.fast, R, (M + 63) / 64, P.ncols, (int)S, lp, (int)words, wp, P.vi_uw8, vd_u, X.head.lmin, X.head.lmax, X.head.trip, X.fast_kind == 2);
+    if (std::getenv("SAENA_SETUP_TIMING")) {
         fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row); staged %s (%d trips)\n",
                 R, nwin, (long long)S, R / sk::BLOCK, (long long)words, (double)lds / 1024.0, 8.0 * (double)S / R, X.head.ntrip ? "window by window" : "flat", X.head.ntrip);
+        if (X.fast_kind)
+            fprintf(stderr, "[sgpu] x windows at %d rows: the common-path kernel is taken, dictionaries of %d values in %s, %d bytes of LDS\n", R, vd_u,
+                    X.fast_kind == 2 ? "scalar registers" : "LDS", X.fast_lds);
+        else
+            fprintf(stderr, "[sgpu] x windows at %d rows: the general kernel is kept (%s)\n", R, vwfast::clause_text(X.fast_clause));
+    }
     return SGPU_OK;
 }
 
@@ -1527,6 +1546,7 @@ using dispatch::with_bool;
 using KernelFn = void (*)(const sk::SpmvArgs);
 using VecKernelFn = void (*)(const sk::SpmvArgs, int);
 using VidxwKernelFn = void (*)(const sk::SpmvArgs, const sk::VwHead, int);      // k_vidxw: the head of its tables by value
+using VidxwFastKernelFn = void (*)(const vwfast::VwFast);                        // k_vidxw_fast: its one argument
 using SellKernelFn = void (*)(const sk::SpmvArgs, int);     // seq != 0: the launch carries the fork (block 0 stores flag_x = seq when it starts)
 using XldsKernelFn = void (*)(const sk::SpmvArgs, const sk::XldsArgs);
 using SellxKernelFn = void (*)(const sk::SpmvArgs, const sk::SellxArgs);
@@ -1582,6 +1602,11 @@ SellKernelFn pick_vidx(int epi, bool halo, bool nt) {
 }
 VidxwKernelFn pick_vidxw(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> VidxwKernelFn { return sk::k_vidxw<E(), H(), N()>; }); }); });
+}
+// the common path (vw_fast.h): 256 / 512 rows, the three epilogues with operands fetched up front, dictionaries in LDS / in scalar registers
+VidxwFastKernelFn pick_vidxw_fast(int rows, int epi, bool nt, bool sd) {
+    return among<256, 512>(rows, [&](auto R) { return among<sk::EPI_SPMV, sk::EPI_RESIDUAL, sk::EPI_JACOBI>(epi, [&](auto E) { return with_bool(nt, [&](auto N) { return with_bool(sd, [&](auto S) -> VidxwFastKernelFn {
+        return sk::k_vidxw_fast<R(), E(), N(), S()>; }); }); }); });
 }
 SellKernelFn pick_rowt(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_rowt<E(), H(), N()>; }); }); });
@@ -1768,6 +1793,17 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
             const CsrPart::XWin &X = P.vw[k];
             if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
             a.ptab = reinterpret_cast<const int *>(X.tab.get()); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
+            if (vwfast::launch_takes(X.fast_kind, halo, epi)) {   // the common path: the plan's argument, the launch's vectors and the arrays the plan points at
+                vwfast::VwFast f = X.fast;
+                if (f.nblk != a.nblk) return fail(SGPU_ERR_STATE, "the x windows were planned for %d slices, the launch has %d", f.nblk, a.nblk);
+                f.vcode = a.vcode; f.dst = a.dst; f.ptab = X.tab.get(); f.vdict = a.vdict;
+                f.x = a.x; f.y = a.y; f.rhs = a.rhs; f.inv_diag = a.inv_diag; f.u = a.u; f.c0 = a.c0;
+                f.nt_from = a.nt_from; f.st_plain = a.st_plain; f.nrows = P.nrows;
+                P.vw_last = X.fast_kind;
+                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, nt, X.fast_kind == 2), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.fast_lds, g.cs, f);
+                break;
+            }
+            P.vw_last = 0;
             SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, X.head, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
@@ -2632,6 +2668,7 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
     if (!ok) return refuse_form(variant);
     op->loc.variant = variant;
     op->loc.vw_rows = 0;                                 // F_VIDX alone gathers directly; sgpu_op_set_x_windows turns the windows on
+    op->loc.vw_last = -1;
     ++g_plan_generation;
     if (variant == F_VIDX)
         if (const char *e = std::getenv("SAENA_X_WINDOWS")) {     // development: pin the mode where only the variant can be pinned (counter passes); refused -> direct
@@ -2648,6 +2685,7 @@ int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
     CHK(need_ctx());
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     const int R = rows_per_workgroup;
+    op->loc.vw_last = -1;
     if (R == 0) { op->loc.vw_rows = 0; ++g_plan_generation; return SGPU_OK; }
     const int k = xwin_slot(R);
     if (k < 0) return fail(SGPU_ERR_ARG, "x windows: rows per workgroup must be 0 (off), 256, 512 or 1024");
@@ -2666,6 +2704,14 @@ int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
 int sgpu_op_get_x_windows(const sgpu_op *op, int *rows_per_workgroup) {
     if (!op || !rows_per_workgroup) return fail(SGPU_ERR_ARG, "null argument");
     *rows_per_workgroup = op->loc.variant == F_VIDX ? op->loc.vw_rows : 0;
+    return SGPU_OK;
+}
+
+int sgpu_op_get_x_window_kernel(const sgpu_op *op, int *kernel) {
+    if (!op || !kernel) return fail(SGPU_ERR_ARG, "null argument");
+    const CsrPart &P = op->loc;
+    const int k = P.variant == F_VIDX ? xwin_slot(P.vw_rows) : -1;
+    *kernel = k < 0 ? 0 : P.vw_last >= 0 ? P.vw_last : P.vw[k].fast_kind;
     return SGPU_OK;
 }
 

@@ -1,0 +1,116 @@
+// vw_fast.h -- the common path of k_vidxw as a kernel of its own (k_vidxw_fast): the rule that says which operator x workgroup size and
+// which launch take it, its one argument (VwFast), and how build_xwin fills the part of that argument which is a function of the plan
+// alone.  Plain C++17, no HIP, every function constexpr: build_xwin and launch_part decide through it, the kernels read the row loop's
+// body through it, and a host compiler can test it (tests/test_vw_fast_header.py).
+//
+// k_vidxw serves every geometry the x-window mode accepts, and every wave of every launch works the geometry out again in scalar
+// instructions: log2 of R from blockDim, the dictionaries of the workgroup, the LDS carve-up, per trip its offset and slot base, and
+// the branches that pick the common path.  On the operators the mode is kept for (one slice width, one dictionary length, at most four
+// trips, a table of at most R chunks) all of that is known once build_xwin has run.  The lean kernel takes it as arguments in the form
+// it consumes, with R, the epilogue and the dictionary treatment as template parameters.
+#pragma once
+#include <cstdint>
+#include "xwin_stage.h"
+
+namespace vwfast {
+
+constexpr int TRIPS = 4;                          // trips the lean kernel issues, used or not (the 7-point levels: 1 + 2 + 1)
+constexpr int NXCD = 8;                           // (kernels.hip.h: sk::NXCD)
+constexpr int VI_MAX = 256;                       // values of a dictionary, one per 256 rows (kernels.hip.h: sk::VI_MAX)
+
+// ---- the rule ----
+// which clause refuses an operator x R, in the order the rule is written; TAKEN: eligible
+enum Clause : int { TAKEN = 0, ROWS, WIDTHS, DICT_LENGTHS, TRIP_COUNT, TABLE_CHUNKS, SWITCHED_OFF };
+// R: rows per workgroup; uw: the slices' common width (0: they differ); vd_u: the dictionaries' common length (0: they differ);
+// ntrip: trips of the window-by-window staging (0: flat staging); n8: 16-byte chunks of the pattern table
+constexpr int refused(int R, int uw, int vd_u, int ntrip, int n8) {
+    return !(R == 256 || R == 512) ? ROWS : uw == 0 ? WIDTHS : vd_u == 0 ? DICT_LENGTHS : !(ntrip >= 1 && ntrip <= TRIPS) ? TRIP_COUNT : n8 > R ? TABLE_CHUNKS : TAKEN;
+}
+constexpr const char *clause_text(int c) {
+    return c == ROWS ? "workgroups of neither 256 nor 512 rows" : c == WIDTHS ? "slices of differing widths" : c == DICT_LENGTHS ? "dictionaries of differing lengths"
+         : c == TRIP_COUNT ? "not staged window by window in one to four trips" : c == TABLE_CHUNKS ? "a pattern table of more 16-byte chunks than rows per workgroup"
+         : c == SWITCHED_OFF ? "SAENA_VIDXW_FAST=0" : "taken";
+}
+// dictionaries of at most two values stay in scalar registers: a position's value is a select by bit 0 of its code
+constexpr bool scalar_dict(int vd_u) { return vd_u == 1 || vd_u == 2; }
+// what the operator runs: 0 the general kernel, 1 the lean kernel with its dictionaries in LDS, 2 with scalar dictionaries
+constexpr int kind(int clause, int vd_u) { return clause != TAKEN ? 0 : scalar_dict(vd_u) ? 2 : 1; }
+// a launch of an eligible operator takes the lean kernel without a halo and with the plain product (0), the residual (1) or the
+// Jacobi sweep (2): the epilogues k_vidxw treats with operands fetched up front (kernels.hip.h: sk::Epi)
+constexpr bool launch_takes(int kind_, bool halo, int epi) { return kind_ != 0 && !halo && epi >= 0 && epi <= 2; }
+
+// ---- the row loop's body, for both kernels: positions j ... j + 7 of a row, lmin / lmax the shortest and the longest pattern ----
+// the positions at or beyond the longest pattern are not computed (never fewer than four: the lengths 1 ... 3 share the body of 4),
+// the first four take no select where every row holds them -> 2 (n - 4) + free4, n = 4 ... 8
+constexpr int body(int lmin, int lmax, int j) {
+    const int n = lmax - j;
+    return 2 * ((n < 4 ? 4 : n > 8 ? 8 : n) - 4) + (j + 4 <= lmin ? 1 : 0);
+}
+constexpr int body_positions(int body_) { return 4 + (body_ >> 1); }
+constexpr bool body_free4(int body_) { return (body_ & 1) != 0; }
+
+// ---- the XCD remap (kernels.hip.h: xcd_remap) with its quotient rq = n / NXCD and remainder rr = n % NXCD taken from the plan: the
+// launch's block bx -> the workgroup it computes, so that the blocks that share an XCD take consecutive workgroups ----
+constexpr int remap(int bx, int rq, int rr) {
+    const int xc = (int)((unsigned)bx % (unsigned)NXCD), xk = (int)((unsigned)bx / (unsigned)NXCD);      // (bx >= 0: an and, a shift)
+    return xk < rq + (xc < rr ? 1 : 0) ? xc * rq + (xc < rr ? xc : rr) + xk : bx;
+}
+
+// ---- the argument ----
+struct Trip {
+    int lds8;         // LDS byte offset of lane 0's slot
+    int col;          // lane 0's column - r0; an unused trip: OFF_NONE / 8 -- byte offsets from 2^31 on, which no descriptor reaches, for
+                      // every row below 2^28 (whatever such a trip loads goes to the spare slot: cnt = 0)
+    int cnt;          // lanes that hold an element of the window (the others write the spare slot); 0: an unused trip
+};
+// Everything k_vidxw_fast reads and nothing else, in the order it is needed.  build_xwin fills the operator's part once (plan()
+// below, and the operator's arrays); launch_part copies it and sets x, y, rhs, inv_diag, u, c0, nt_from, st_plain, nrows.
+struct VwFast {
+    // the prologue's loads
+    const unsigned char  *vcode;      // k_vidx's codes
+    const unsigned short *dst;        // pattern ids
+    const void           *ptab;       // the table as 16-bit words (build_xwin's), read in 16-byte chunks
+    const double         *vdict;      // the dictionaries back to back
+    const double         *x;
+    const double         *rhs, *inv_diag, *u;
+    int nrows, nblk;                  // rows; slices of 64 rows
+    int rq, rr;                       // the XCD remap: workgroups / NXCD, workgroups % NXCD
+    int cbytes;                       // bytes of a slice's codes: 64 uw
+    int n8;                           // 16-byte chunks of the table (1 ... R)
+    int vd_u, ngd;                    // values per dictionary; dictionaries of the operator
+    unsigned xbytes;                  // 8 ncols: the buffer descriptor's num_records
+    int nt_from;                      // first slice read with non-temporal loads
+    Trip trip[TRIPS];
+    // behind the loads: the LDS carve-up in bytes
+    int S8;                           // the spare slot behind the windows
+    int dict_off, tab_off, pos_off;   // dictionaries (LDS dictionaries only), table, the table's positions (behind the patterns' lengths)
+    int pw2;                          // bytes of a pattern's positions: 2 pt_w
+    // the row loop and the store
+    int w8;                           // positions of a slice (a multiple of 8)
+    int lmin, lmax, body0;            // the shortest and the longest pattern; body(lmin, lmax, 0)
+    int st_plain;
+    double *y;
+    double  c0;
+};
+
+// The operator's part of VwFast but its four arrays, and the LDS bytes a workgroup needs -> those bytes.
+// R, nslices: rows per workgroup, slices of 64 rows; S: doubles of x in LDS; lp, words: 16-bit words of the patterns' lengths and of
+// the whole table; wp: positions per pattern; uw, vd_u, lmin, lmax: VwHead's; t: xwin_stage.h's trips (at least TRIPS of them);
+// sd: scalar dictionaries.  The layout is k_vidxw's -- [windows, spare slot, rounded to 16 B][R / 256 dictionaries][table] -- without
+// the dictionaries where they stay in scalar registers.
+constexpr int plan(VwFast &f, int R, int nslices, int ncols, int S, int lp, int words, int wp, int uw, int vd_u, int lmin, int lmax, const xwstage::Trip *t, bool sd) {
+    const int spb = R / 64, nwg = (nslices + spb - 1) / spb;
+    f.nblk = nslices; f.rq = nwg / NXCD; f.rr = nwg % NXCD;
+    f.cbytes = 64 * uw; f.n8 = words >> 3; f.vd_u = vd_u; f.ngd = (nslices + 3) >> 2;
+    f.xbytes = 8u * (unsigned)ncols;
+    for (int u = 0; u < TRIPS; ++u) f.trip[u] = Trip{8 * t[u].lds, t[u].cnt > 0 ? t[u].col : (int)(xwstage::OFF_NONE / 8u), t[u].cnt};
+    f.S8 = 8 * S;
+    f.dict_off = 8 * ((S + 2) & ~1);
+    f.tab_off = f.dict_off + (sd ? 0 : (R / 256) * VI_MAX * 8);
+    f.pos_off = f.tab_off + 2 * lp;
+    f.pw2 = 2 * wp;
+    f.w8 = uw; f.lmin = lmin; f.lmax = lmax; f.body0 = body(lmin, lmax, 0);
+    return f.tab_off + 2 * words;
+}
+
+}

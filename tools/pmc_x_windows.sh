@@ -3,7 +3,7 @@
 #   bash tools/pmc_x_windows.sh <rows per workgroup: 0 direct, 256, 512, 1024> <out.txt>
 # One rocprofv3 --pmc pass per counter group over `python bench.py --gpus 1 --steps 20 --warmup 5` with the kernel pinned
 # (SAENA_BENCH_VARIANT=17; SAENA_X_WINDOWS pins the mode), counters only -- no tracing in the same run.  Prints the mean per launch
-# over the launches of the most-launched k_vidx / k_vidxw kernel: texture-addresser busy cycles, L1 accesses and pending-stall
+# over the launches of the most-launched k_vidx / k_vidxw / k_vidxw_fast kernel: texture-addresser busy cycles, L1 accesses and pending-stall
 # cycles (summed over the CUs), FETCH_SIZE (KiB as reported: x 2 on gfx950 for wide coalesced streams, tools/pmc_summarise.py),
 # the waves' instruction counts, and -- of the cycles a wave spends issuing or waiting per instruction class -- whatever the box's
 # counter list offers (asked of rocprofv3 first: a counter it does not name is left out, not tried).  VALU per wave and the share of
