@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "xwin_stage.h"
+#include "xwin_head.h"      // NXCD, VI_MAX, VW_MAX_LDS, SPX_ROWS, SPX_MAXWIN, SPX_LDS_BYTES and VwHead: shared with the host-side plans
 #include "vw_fast.h"
 
 namespace sk {
@@ -34,7 +35,6 @@ constexpr int BLOCK   = 256;    // 4 waves
 constexpr int CAP     = 2048;   // products staged per row block (16 KiB of LDS)
 constexpr int CAP_BIG = 4096;   // alternative plan: 32 KiB of LDS, half the blocks
 constexpr int MAXROWS = 256;    // rows per row block (one pass at 1 lane/row)
-constexpr int NXCD    = 8;
 
 enum Epi : int {
     EPI_SPMV = 0,      // y = s
@@ -809,8 +809,7 @@ __global__ __launch_bounds__(WIDE ? SPW_BLOCK : BLOCK) void k_sellp(const SpmvAr
 // contiguous; a.vcptr / a.uw: slice starts; a.vdict / a.vdptr: the dictionaries, staged in LDS behind the pattern table (<= 2 KiB);
 // a.dst / a.ptab / pt_w / pt_n / a.rbase: k_sellp's pattern ids, table and (rowbase) first columns; a.nblk: slices.
 // One workgroup = 4 slices = 256 rows = one dictionary (k_vi_build below); the operator is refused where any workgroup holds more than
-// VI_MAX distinct values.
-constexpr int VI_MAX = 256;
+// VI_MAX distinct values (xwin_head.h).
 template <int EPI, bool HALO, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_vidx(const SpmvArgs a, int nrows) {
     extern __shared__ int ptab_lds[];
@@ -886,19 +885,9 @@ __global__ __launch_bounds__(BLOCK) void k_vidx(const SpmvArgs a, int nrows) {
 // multiple of 8) LDS byte offsets (8 x position: below 64 KiB like the LDS) for the workgroup's first row, the tail repeating the last one; a.vcode / a.vcptr / a.uw / a.vdict /
 // a.vdptr / a.dst: k_vidx's.
 // Same products, same sequential row sum: bit-identical to k_vidx and k_sellp.
-constexpr int VW_MAX_LDS = 64 * 1024;          // windows + dictionaries + table: at least two workgroups per CU
 typedef unsigned sk_u4v __attribute__((ext_vector_type(4)));
-// the head of the window table and what else the prologue would fetch from memory before it can form an address: by value, k_vidxw's
-// second parameter (build_xwin fills it)
-struct VwHead {
-    int nwin, S;          // windows; doubles of x in LDS
-    int win[8];           // (LDS base, omin - base) of the first four windows (unused ones: base INT32_MAX)
-    int lp, tn;           // 16-bit words of the table: the patterns' lengths, all of it (multiples of 8)
-    int vd_u;             // every dictionary of the operator holds this many values, or 0: they differ, read a.vdptr
-    int lmin, lmax;       // the shortest and the longest pattern: positions below lmin are real in every row, none at or beyond lmax in any
-    int ntrip;            // the windows are staged one by one in this many trips (xwin_stage.h), or 0: the flat staging
-    xwstage::Trip trip[xwstage::MAX_TRIPS];      // ... the sizes of the first four windows next to their bases, trip by trip (unused: cnt 0)
-};
+// h (VwHead, xwin_head.h): the head of the window table and what else the prologue would fetch from memory before it can form an
+// address: by value, k_vidxw's second parameter (build_xwin fills it)
 typedef unsigned sk_u2w __attribute__((ext_vector_type(2)));
 // One of two wave-uniform 64-bit patterns by bit `bit` of w: a sign-extending bit-field extract makes the mask, two bit-field inserts
 // pick the halves.  No arithmetic touches the value: signed zeros and NaN payloads come through as stored.
@@ -1221,9 +1210,7 @@ __global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
 // nwin, then (omin, LDS base, size) per window.
 // Same products, same sequential row sum: bit-identical to k_sellp.
 constexpr int SPX_BLOCK = 512;
-constexpr int SPX_ROWS  = 512;                 // rows per workgroup: 8 slices of 64 (256 rows, 3-4 workgroups per CU: 127.5 against 119.7 us of k_sellp<WIDE>)
-constexpr int SPX_MAXWIN = 16;
-constexpr int SPX_LDS_BYTES = 80 * 1024;       // windows + table: two workgroups per CU
+// (SPX_ROWS, SPX_MAXWIN, SPX_LDS_BYTES: xwin_head.h)
 template <int EPI, bool HALO, bool PAIR, bool NT>
 __global__ __launch_bounds__(SPX_BLOCK) void k_sellpx(const SpmvArgs a, int nrows) {
     __shared__ double spx_lds[SPX_LDS_BYTES / 8];

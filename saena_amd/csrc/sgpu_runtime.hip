@@ -14,6 +14,7 @@
 #include "dispatch.h"
 #include "devmem.h"
 #include "forms.h"
+#include "xwin_plan.h"
 #include "host/dense_eig.h"
 #include "host/comm.h"
 #include "host/par.h"
@@ -213,12 +214,10 @@ struct CsrPart {
     int             vi_uw8 = 0;           // every slice has this many code positions (a multiple of 8), or 0: read vi_cptr
     int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
     // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
-    // windows (count, doubles in all, then LDS base / omin - base each) and the ONE table as 16-bit LDS byte offsets; vw_rows: the R in
-    // use, 0 = direct gathers.  Two small tables next to k_vidx's arrays; head: what of them (and of vi_dptr) every launch passes by value
-    // fast: the operator's part of k_vidxw_fast's argument where vw_fast.h's rule takes the operator at this R (fast_kind 1: dictionaries
-    // in LDS, 2: in scalar registers; 0: the general kernel, fast_clause says which clause refused), fast_lds: its LDS bytes
-    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; sk::VwHead head{}; int wp = 0, lds = 0; bool ok = false; char tried = 0;
-                  vwfast::VwFast fast{}; int fast_kind = 0, fast_clause = 0, fast_lds = 0; };
+    // window list and the ONE table as 16-bit LDS byte offsets -- two small tables next to k_vidx's arrays -- and plan: what of
+    // xwin_plan.h's plan every launch passes by value (the head, the common-path kernel's argument) or sizes its LDS by; vw_rows: the R in
+    // use, 0 = direct gathers
+    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; xwplan::VwScalars plan; bool ok = false; char tried = 0; };
     XWin            vw[3];
     int             vw_rows = 0;
     mutable int     vw_last = -1;         // what the last launch in the mode ran (0 k_vidxw, 1 / 2 k_vidxw_fast as fast_kind), -1: none since the mode was set
@@ -1027,90 +1026,21 @@ int build_sellp_mode(CsrPart &P, bool rowbase) {
     return SGPU_OK;
 }
 
-// k_sellpx on top of build_sellp's patterns: the offsets of all patterns fall into clusters (gaps of more than SPX_ROWS columns
-// separate them); a workgroup of SPX_ROWS rows starting at r0 needs x inside the windows [r0 + omin_c, r0 + SPX_ROWS + omax_c), laid
-// out one after the other in LDS.  A pattern's entry becomes the LDS position of its column for the workgroup's FIRST row: window
-// base + (offset - omin_c).  Every workgroup gets its own small table -- the patterns its rows follow, in order of first
-// appearance -- and its rows' ids count within it.  The form applies when windows and the largest of these tables fit
-// SPX_LDS_BYTES (two workgroups per CU).
+// k_sellpx on top of build_sellp's patterns: xwin_plan.h's plan_sellpx from the host copy of the patterns -- the windows of x per
+// workgroup of SPX_ROWS rows, every workgroup's own small table of 16-bit LDS positions, its rows' ids within it.
 int build_sellpx(CsrPart &P) {
     if (P.spx.spx_ok || P.spx.spx_tried || !P.sp.sp_ok || P.sp.sp_rbase || !P.sv.sl_val || P.h_ptab.empty() || P.h_pat.empty()) return SGPU_OK;
     P.spx.spx_tried = 1;
-    const int npat = (int)P.h_pstart.size(), M = P.nrows;
-    std::vector<int> offs;
-    for (int i = 0; i < npat; ++i) {
-        const int *c = &P.h_ptab[(size_t)P.h_pstart[(size_t)i]];
-        offs.insert(offs.end(), c + 1, c + 1 + c[0]);
-    }
-    std::sort(offs.begin(), offs.end());
-    offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-    if (offs.empty()) return SGPU_OK;
-    std::vector<int> omin, omax, base;
-    for (size_t i = 0; i < offs.size(); ++i) {
-        if (i == 0 || (int64_t)offs[i] - offs[i - 1] > sk::SPX_ROWS) { omin.push_back(offs[i]); omax.push_back(offs[i]); }
-        else omax.back() = offs[i];
-    }
-    const int nwin = (int)omin.size();
-    if (nwin > sk::SPX_MAXWIN) return SGPU_OK;
-    int64_t S = 0;
-    for (int c = 0; c < nwin; ++c) { base.push_back((int)S); S += (int64_t)sk::SPX_ROWS + ((int64_t)omax[(size_t)c] - omin[(size_t)c]); if (S > 65535) return SGPU_OK; }
-    if (S * 8 >= (int64_t)sk::SPX_LDS_BYTES) return SGPU_OK;
-    const int64_t room = ((int64_t)sk::SPX_LDS_BYTES - S * 8) / 2;           // 16-bit words left for a workgroup's table
-    // every pattern once as (length, LDS positions)
-    std::vector<unsigned short> pos16;
-    std::vector<int> pstart16((size_t)npat + 1, 0);
-    for (int i = 0; i < npat; ++i) {
-        const int *c = &P.h_ptab[(size_t)P.h_pstart[(size_t)i]];
-        pstart16[(size_t)i] = (int)pos16.size();
-        pos16.push_back((unsigned short)c[0]);
-        for (int j = 0; j < c[0]; ++j) {
-            const int w = (int)(std::upper_bound(omin.begin(), omin.end(), c[1 + j]) - omin.begin()) - 1;      // the window that holds the offset
-            pos16.push_back((unsigned short)(base[(size_t)w] + (c[1 + j] - omin[(size_t)w])));
-        }
-        if (c[0] == 0) pos16.push_back(0);                        // (an empty row reads position 0 and adds nothing)
-    }
-    pstart16[(size_t)npat] = (int)pos16.size();
-    const int ngrp = (M + sk::SPX_ROWS - 1) / sk::SPX_ROWS;
-    std::vector<int> wgptr((size_t)ngrp + 1, 0);
-    std::vector<unsigned short> tab, lpat(P.h_pat.size(), 0);
-    std::vector<int> local((size_t)npat, -1), used;
-    int64_t max_words = 0;
-    for (int g = 0; g < ngrp; ++g) {
-        used.clear();
-        const int r1 = std::min(M, (g + 1) * sk::SPX_ROWS);
-        for (int r = g * sk::SPX_ROWS; r < r1; ++r) {
-            const int id = P.h_pat[(size_t)r];
-            if (local[(size_t)id] < 0) { local[(size_t)id] = (int)used.size(); used.push_back(id); }
-            lpat[(size_t)r] = (unsigned short)local[(size_t)id];
-        }
-        if (used.empty()) { used.push_back(0); }
-        int64_t words = (int64_t)used.size();
-        for (int id : used) words += pstart16[(size_t)id + 1] - pstart16[(size_t)id];
-        words = (words + 3) / 4 * 4;
-        max_words = std::max(max_words, words);
-        if (words > room || words > 65535 || (int64_t)tab.size() + words > (int64_t)INT32_MAX - 8) { P.h_pat.shrink_to_fit(); return SGPU_OK; }
-        const size_t t0 = tab.size();
-        tab.resize(t0 + (size_t)words, 0);
-        size_t at = t0 + used.size();
-        for (size_t k = 0; k < used.size(); ++k) {
-            const int id = used[k];
-            tab[t0 + k] = (unsigned short)(at - t0);
-            for (int q = pstart16[(size_t)id]; q < pstart16[(size_t)id + 1]; ++q) tab[at++] = pos16[(size_t)q];
-            local[(size_t)id] = -1;
-        }
-        wgptr[(size_t)g + 1] = (int)tab.size();
-    }
+    const xwplan::SpxPlan X = xwplan::plan_sellpx(P.h_pstart, P.h_ptab, P.h_pat, P.nrows);
+    if (X.refusal == xwplan::SPX_TABLE) P.h_pat.shrink_to_fit();
+    if (X.refusal) return SGPU_OK;
     if (std::getenv("SAENA_SETUP_TIMING"))
-        fprintf(stderr, "[sgpu] x in LDS for the row patterns: %d windows, %lld doubles of x + at most %lld table words per workgroup of %d rows (%.1f KiB); tables %.1f MB\n", nwin,
-                (long long)S, (long long)max_words, sk::SPX_ROWS, (double)(S * 8 + max_words * 2) / 1024.0, (double)tab.size() * 2e-6);
-    std::vector<int> win(1 + 3 * (size_t)nwin);
-    win[0] = nwin;
-    for (int c = 0; c < nwin; ++c) { win[1 + 3 * (size_t)c] = omin[(size_t)c]; win[2 + 3 * (size_t)c] = base[(size_t)c]; win[3 + 3 * (size_t)c] = sk::SPX_ROWS + (omax[(size_t)c] - omin[(size_t)c]); }
-    tab.resize(tab.size() + 8, 0);
-    CHK(dev_upload(P.spx.spx_tab, tab.data(), tab.size()));
-    CHK(dev_upload(P.spx.spx_wgptr, wgptr.data(), wgptr.size()));
-    CHK(dev_upload(P.spx.spx_pat, lpat.data(), lpat.size()));
-    CHK(dev_upload(P.spx.spx_win, win.data(), win.size()));
+        fprintf(stderr, "[sgpu] x in LDS for the row patterns: %d windows, %lld doubles of x + at most %lld table words per workgroup of %d rows (%.1f KiB); tables %.1f MB\n", X.nwin,
+                (long long)X.S, (long long)X.max_words, sk::SPX_ROWS, (double)(X.S * 8 + X.max_words * 2) / 1024.0, (double)(X.tab.size() - 8) * 2e-6);
+    CHK(dev_upload(P.spx.spx_tab, X.tab.data(), X.tab.size()));
+    CHK(dev_upload(P.spx.spx_wgptr, X.wgptr.data(), X.wgptr.size()));
+    CHK(dev_upload(P.spx.spx_pat, X.pat.data(), X.pat.size()));
+    CHK(dev_upload(P.spx.spx_win, X.win.data(), X.win.size()));
     P.spx.spx_ok = true;
     return SGPU_OK;
 }
@@ -1124,26 +1054,13 @@ int build_vidx(CsrPart &P) {
     const int M = P.nrows;
     if (M == 0) return SGPU_OK;
     const int ns = (M + 63) / 64, ngrp = (ns + 3) / 4;
-    std::vector<int> ptr((size_t)ns + 1, 0);
-    int64_t tot = 0;
-    bool uniform = true;
-    int w8_0 = 0;
-    for (int s = 0; s < ns; ++s) {
-        int w = 0;
-        for (int r = s * 64; r < std::min(M, s * 64 + 64); ++r) w = std::max(w, P.h_rp[(size_t)r + 1] - P.h_rp[(size_t)r]);
-        const int w8 = (w + 7) & ~7;
-        if (s == 0) w8_0 = w8;
-        else if (w8 != w8_0 && !(s == ns - 1 && w8 < w8_0)) uniform = false;     // (a narrower last slice is padded up)
-        tot += (int64_t)w8 * 64;
-        if (tot > (int64_t)INT32_MAX - 1024) return SGPU_OK;
-        ptr[(size_t)s + 1] = (int)tot;
-    }
-    if (uniform && w8_0 > 0 && (int64_t)ns * w8_0 * 64 <= (int64_t)INT32_MAX - 1024) tot = (int64_t)ns * w8_0 * 64;
-    else uniform = false;
+    const xwplan::SliceWidths sw = xwplan::slice_widths(P.h_rp.data(), M);      // (uw: the slices' common width, or 0: vi_cptr)
+    if (!sw.ok) return SGPU_OK;
+    const int64_t tot = sw.tot;
     const size_t nb = (size_t)tot + 512;
     if (P.vi.vi_code.alloc(nb) != hipSuccess) return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nb);
     HIPCHK(hipMemsetAsync(P.vi.vi_code, 0, nb, g.cs));
-    if (!uniform) CHK(dev_upload(P.vi.vi_cptr, ptr.data(), ptr.size()));
+    if (!sw.uw) CHK(dev_upload(P.vi.vi_cptr, sw.ptr.data(), sw.ptr.size()));
     DevArr<double> tmp;
     DevArr<int> d_cnt;
     CHK(dev_alloc(tmp, (size_t)ngrp * sk::VI_MAX));
@@ -1151,7 +1068,7 @@ int build_vidx(CsrPart &P) {
     int *d_flag = d_cnt + ngrp;
     HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g.cs));
     SGPU_LAUNCH(sk::k_vi_build, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)P.csr.val, (const int *)P.csr.row_ptr, (const int *)P.vi.vi_cptr,
-                uniform ? w8_0 : 0, M, P.vi.vi_code.get(), tmp.get(), d_cnt.get(), d_flag);
+                sw.uw, M, P.vi.vi_code.get(), tmp.get(), d_cnt.get(), d_flag);
     HIPCHK(hipGetLastError());
     std::vector<int> cnt((size_t)ngrp + 1);
     HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
@@ -1169,7 +1086,7 @@ int build_vidx(CsrPart &P) {
     SGPU_LAUNCH(sk::k_vi_compact, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)tmp, (const int *)P.vi.vi_dptr, P.vi.vi_dict.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
-    P.vi_uw8 = uniform ? w8_0 : 0;
+    P.vi_uw8 = sw.uw;
     P.vi_bytes = tot + (P.sp.sp_rbase ? 6 : 2) * (int64_t)M + 8 * (int64_t)P.ncols + 8 * (int64_t)M + 8 * (int64_t)dptr[(size_t)ngrp];
     P.vi.vi_ok = true;
     if (std::getenv("SAENA_SETUP_TIMING"))
@@ -1178,12 +1095,9 @@ int build_vidx(CsrPart &P) {
     return SGPU_OK;
 }
 
-// The x-window launch mode of k_vidx for workgroups of R = 256 << k rows: build_sellp's ONE pattern table (read back from the
-// device -- the host copy goes when the plan settles), its offsets clustered as build_sellpx does with the gap rule at R, the
-// windows [r0 + omin_c, r0 + R + omax_c) laid out one after the other, and the table rewritten ONCE for the whole operator as
-// 16-bit LDS byte offsets for a workgroup's first row; the head (VwHead) carries the shortest and the longest pattern and, where
-// xwin_stage.h's rule allows it, the trips that stage the windows one by one.  Refused (ok stays false, *why says it): rowbase and per-workgroup tables,
-// more than SPX_MAXWIN windows, positions beyond 16 bits, more LDS than VW_MAX_LDS (two workgroups per CU).
+// The x-window launch mode of k_vidx for workgroups of R = 256 << k rows: xwin_plan.h's plan_vidxw from build_sellp's ONE pattern
+// table and the dictionaries' starts (both read back from the device -- the host copies go when the plan settles).  Refused (ok stays
+// false, *why says it): rowbase and per-workgroup tables, and what the plan refuses.
 int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     CsrPart::XWin &X = P.vw[k];
     const int R = 256 << k;
@@ -1196,88 +1110,26 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     X.tried = 1;
     const int npat = P.sp_n, W = P.sp_w, M = P.nrows;
     if (npat <= 0 || W <= 0) return no("no patterns");
-    std::vector<int> tab((size_t)npat * (W + 1));
+    std::vector<int> tab((size_t)npat * (W + 1)), dptr((size_t)((M + 63) / 64 + 3) / 4 + 1);
     HIPCHK(hipMemcpyAsync(tab.data(), P.sp.sp_tab, tab.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
-    HIPCHK(hipStreamSynchronize(g.cs));
-    std::vector<int> offs;
-    for (int i = 0; i < npat; ++i) {
-        const int *c = &tab[(size_t)i * (W + 1)];
-        if (c[0] < 0 || c[0] > W) return no("a pattern longer than the table's width");
-        offs.insert(offs.end(), c + 1, c + 1 + c[0]);
-    }
-    std::sort(offs.begin(), offs.end());
-    offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-    if (offs.empty()) return no("no entries");
-    std::vector<int> omin, omax, base;
-    for (size_t i = 0; i < offs.size(); ++i) {
-        if (i == 0 || (int64_t)offs[i] - offs[i - 1] > R) { omin.push_back(offs[i]); omax.push_back(offs[i]); }
-        else omax.back() = offs[i];
-    }
-    const int nwin = (int)omin.size();
-    if (nwin > sk::SPX_MAXWIN) return no("more windows than SPX_MAXWIN");
-    int64_t S = 0;
-    for (int c = 0; c < nwin; ++c) { base.push_back((int)S); S += (int64_t)R + ((int64_t)omax[(size_t)c] - omin[(size_t)c]); if (S > 65536) return no("LDS positions beyond 16 bits"); }
-    if ((int64_t)M + R + S + std::max<int64_t>(std::abs((int64_t)offs.front()), std::abs((int64_t)offs.back())) > (int64_t)INT32_MAX - 8) return no("column arithmetic beyond 32 bits");
-    const int wp = (W + 7) & ~7, lp = (npat + 7) & ~7;
-    if (P.vi_uw8 > wp) return no("slices wider than the table");
-    const int64_t words = (int64_t)lp + (int64_t)npat * wp;
-    const int64_t lds = ((S + 2) & ~(int64_t)1) * 8 + (int64_t)(R / sk::BLOCK) * sk::VI_MAX * 8 + words * 2;
-    if (lds > (int64_t)sk::VW_MAX_LDS) return no("windows, dictionaries and table exceed the LDS cap");
-    std::vector<unsigned short> t16((size_t)words, 0);
-    for (int i = 0; i < npat; ++i) {
-        const int *c = &tab[(size_t)i * (W + 1)];
-        t16[(size_t)i] = (unsigned short)c[0];
-        unsigned short last = 0;                                  // (an empty row reads position 0 and adds nothing)
-        for (int j = 0; j < wp; ++j) {
-            if (j < c[0]) {
-                const int w = (int)(std::upper_bound(omin.begin(), omin.end(), c[1 + j]) - omin.begin()) - 1;      // the window that holds the offset
-                last = (unsigned short)(8 * (base[(size_t)w] + (c[1 + j] - omin[(size_t)w])));      // (a byte offset: S doubles fit the LDS cap, so below 64 KiB)
-            }
-            t16[(size_t)lp + (size_t)i * wp + j] = last;        // (the tail repeats the last position: read, never added)
-        }
-    }
-    std::vector<int> win(2 + 2 * (size_t)std::max(nwin, 4), INT32_MAX);          // (the kernel reads the first four windows unconditionally: unused ones never match)
-    win[0] = nwin; win[1] = (int)S;
-    for (int c = 0; c < nwin; ++c) { win[2 + 2 * (size_t)c] = base[(size_t)c]; win[3 + 2 * (size_t)c] = omin[(size_t)c] - base[(size_t)c]; }
-    // the dictionaries' common length, where they have one: the kernel then computes where a workgroup's values begin and reads no vi_dptr
-    const int ngd = ((M + 63) / 64 + 3) / 4;
-    std::vector<int> dptr((size_t)ngd + 1);
     HIPCHK(hipMemcpyAsync(dptr.data(), P.vi.vi_dptr, dptr.size() * sizeof(int), hipMemcpyDeviceToHost, g.cs));
     HIPCHK(hipStreamSynchronize(g.cs));
-    int vd_u = dptr[1] - dptr[0];
-    for (int b = 1; b < ngd; ++b) if (dptr[(size_t)b + 1] - dptr[(size_t)b] != vd_u) vd_u = 0;
-    CHK(dev_upload(X.tab, t16.data(), t16.size(), 8));
-    CHK(dev_upload(X.win, win.data(), win.size()));
-    X.head.nwin = nwin; X.head.S = (int)S;
-    std::copy(win.begin() + 2, win.begin() + 10, X.head.win);
-    X.head.lp = lp; X.head.tn = (int)words; X.head.vd_u = vd_u;
-    X.head.lmin = X.head.lmax = tab[0];
-    for (int i = 1; i < npat; ++i) { X.head.lmin = std::min(X.head.lmin, tab[(size_t)i * (W + 1)]); X.head.lmax = std::max(X.head.lmax, tab[(size_t)i * (W + 1)]); }
-    // window by window where xwin_stage.h's rule allows it (else ntrip = 0: the flat staging)
-    X.head.ntrip = 0;
-    if (xwstage::per_window(nwin, S, R, P.ncols, M, omin.front(), omax.back())) {
-        std::vector<int> size;
-        for (int c = 0; c < nwin; ++c) size.push_back(R + (omax[(size_t)c] - omin[(size_t)c]));
-        X.head.ntrip = xwstage::trips(nwin, base.data(), omin.data(), size.data(), R, X.head.trip);
-    }
-    X.wp = wp; X.lds = (int)lds; X.ok = true;
-    // the common-path kernel where vw_fast.h's rule takes the operator at this R; the environment is read per operator, so that one
-    // process can build both paths
+    // (the environment is read per operator, so that one process can build both paths)
     const char *fast_env = std::getenv("SAENA_VIDXW_FAST");
-    X.fast_clause = vwfast::refused(R, P.vi_uw8, vd_u, X.head.ntrip, (int)(words >> 3));
-    if (X.fast_clause == vwfast::TAKEN && fast_env && std::atoi(fast_env) == 0) X.fast_clause = vwfast::SWITCHED_OFF;
-    X.fast_kind = vwfast::kind(X.fast_clause, vd_u);
-    X.fast = vwfast::VwFast{};
-    if (X.fast_kind)
-        X.fast_lds = vwfast::plan(X.fast, R, (M + 63) / 64, P.ncols, (int)S, lp, (int)words, wp, P.vi_uw8, vd_u, X.head.lmin, X.head.lmax, X.head.trip, X.fast_kind == 2);
+    const xwplan::VwPlan plan = xwplan::plan_vidxw(tab.data(), npat, W, M, P.ncols, R, P.vi_uw8, dptr.data(), fast_env && std::atoi(fast_env) == 0);
+    if (plan.refusal) return no(xwplan::refusal_text(plan.refusal));
+    CHK(dev_upload(X.tab, plan.tab.data(), plan.tab.size(), 8));
+    CHK(dev_upload(X.win, plan.win.data(), plan.win.size()));
+    X.plan = plan.s; X.ok = true;
     if (std::getenv("SAENA_SETUP_TIMING")) {
+        const xwplan::VwScalars &s = X.plan;
         fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row); staged %s (%d trips)\n",
-                R, nwin, (long long)S, R / sk::BLOCK, (long long)words, (double)lds / 1024.0, 8.0 * (double)S / R, X.head.ntrip ? "window by window" : "flat", X.head.ntrip);
-        if (X.fast_kind)
-            fprintf(stderr, "[sgpu] x windows at %d rows: the common-path kernel is taken, dictionaries of %d values in %s, %d bytes of LDS\n", R, vd_u,
-                    X.fast_kind == 2 ? "scalar registers" : "LDS", X.fast_lds);
+                R, s.head.nwin, (long long)s.head.S, R / sk::BLOCK, (long long)s.head.tn, (double)s.lds / 1024.0, 8.0 * (double)s.head.S / R, s.head.ntrip ? "window by window" : "flat", s.head.ntrip);
+        if (s.fast_kind)
+            fprintf(stderr, "[sgpu] x windows at %d rows: the common-path kernel is taken, dictionaries of %d values in %s, %d bytes of LDS\n", R, s.head.vd_u,
+                    s.fast_kind == 2 ? "scalar registers" : "LDS", s.fast_lds);
         else
-            fprintf(stderr, "[sgpu] x windows at %d rows: the general kernel is kept (%s)\n", R, vwfast::clause_text(X.fast_clause));
+            fprintf(stderr, "[sgpu] x windows at %d rows: the general kernel is kept (%s)\n", R, vwfast::clause_text(s.fast_clause));
     }
     return SGPU_OK;
 }
@@ -1792,19 +1644,19 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
             const int k = xwin_slot(P.vw_rows), spb = P.vw_rows / 64;
             const CsrPart::XWin &X = P.vw[k];
             if (!X.ok) return fail(SGPU_ERR_STATE, "the x windows of the value-indexed form were not built");
-            a.ptab = reinterpret_cast<const int *>(X.tab.get()); a.pt_w = X.wp; a.segtab = X.win; a.ncols = P.ncols;
-            if (vwfast::launch_takes(X.fast_kind, halo, epi)) {   // the common path: the plan's argument, the launch's vectors and the arrays the plan points at
-                vwfast::VwFast f = X.fast;
+            a.ptab = reinterpret_cast<const int *>(X.tab.get()); a.pt_w = X.plan.wp; a.segtab = X.win; a.ncols = P.ncols;
+            if (vwfast::launch_takes(X.plan.fast_kind, halo, epi)) {   // the common path: the plan's argument, the launch's vectors and the arrays the plan points at
+                vwfast::VwFast f = X.plan.fast;
                 if (f.nblk != a.nblk) return fail(SGPU_ERR_STATE, "the x windows were planned for %d slices, the launch has %d", f.nblk, a.nblk);
                 f.vcode = a.vcode; f.dst = a.dst; f.ptab = X.tab.get(); f.vdict = a.vdict;
                 f.x = a.x; f.y = a.y; f.rhs = a.rhs; f.inv_diag = a.inv_diag; f.u = a.u; f.c0 = a.c0;
                 f.nt_from = a.nt_from; f.st_plain = a.st_plain; f.nrows = P.nrows;
-                P.vw_last = X.fast_kind;
-                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, nt, X.fast_kind == 2), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.fast_lds, g.cs, f);
+                P.vw_last = X.plan.fast_kind;
+                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, nt, X.plan.fast_kind == 2), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.fast_lds, g.cs, f);
                 break;
             }
             P.vw_last = 0;
-            SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.lds, g.cs, a, X.head, P.nrows);
+            SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.lds, g.cs, a, X.plan.head, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
     } break;
@@ -2711,7 +2563,7 @@ int sgpu_op_get_x_window_kernel(const sgpu_op *op, int *kernel) {
     if (!op || !kernel) return fail(SGPU_ERR_ARG, "null argument");
     const CsrPart &P = op->loc;
     const int k = P.variant == F_VIDX ? xwin_slot(P.vw_rows) : -1;
-    *kernel = k < 0 ? 0 : P.vw_last >= 0 ? P.vw_last : P.vw[k].fast_kind;
+    *kernel = k < 0 ? 0 : P.vw_last >= 0 ? P.vw_last : P.vw[k].plan.fast_kind;
     return SGPU_OK;
 }
 

@@ -11,12 +11,13 @@
 #pragma once
 #include <cstdint>
 #include "xwin_stage.h"
+#include "xwin_head.h"
 
 namespace vwfast {
 
 constexpr int TRIPS = 4;                          // trips the lean kernel issues, used or not (the 7-point levels: 1 + 2 + 1)
-constexpr int NXCD = 8;                           // (kernels.hip.h: sk::NXCD)
-constexpr int VI_MAX = 256;                       // values of a dictionary, one per 256 rows (kernels.hip.h: sk::VI_MAX)
+using sk::NXCD;
+using sk::VI_MAX;                                 // values of a dictionary, one per 256 rows
 
 // ---- the rule ----
 // which clause refuses an operator x R, in the order the rule is written; TAKEN: eligible

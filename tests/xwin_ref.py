@@ -85,6 +85,122 @@ def geometry(rows, cols, M, N, R, st=None):
     return g
 
 
+# ---- the plans of saena_amd/csrc/xwin_plan.h, restated: what build_xwin uploads and keeps, what build_sellpx uploads ----
+INT32_MAX = 2 ** 31 - 1
+SPX_ROWS, SPX_LDS_BYTES = 512, 80 * 1024
+DESC_COLS = 1 << 28                     # xwin_stage.h: columns whose byte offsets stay below 2^31
+# build_xwin's refusals, in the order it checks them
+PATTERN_LENGTH, NO_ENTRIES = "a pattern longer than the table's width", "no entries"
+POSITIONS_16, COLUMNS_32, SLICE_WIDTH = "LDS positions beyond 16 bits", "column arithmetic beyond 32 bits", "slices wider than the table"
+LDS_CAP_TEXT = "windows, dictionaries and table exceed the LDS cap"
+# vw_fast.h's clauses
+FAST_TAKEN, FAST_ROWS, FAST_WIDTHS, FAST_DICTS, FAST_TRIPS, FAST_TABLE, FAST_OFF = range(7)
+
+
+def layout(win, R):
+    """windows one after the other -> ([base], [size], S)"""
+    size = [R + hi - lo for lo, hi in win]
+    base = [sum(size[:c]) for c in range(len(win))]
+    return base, size, sum(size)
+
+
+def position(win, base, o):
+    """the LDS position of offset o for a workgroup's first row: inside the one window that holds it"""
+    (c,) = [c for c, (lo, hi) in enumerate(win) if lo <= o <= hi]
+    return base[c] + o - win[c][0]
+
+
+def fast_rule(R, uw, vd_u, ntrip, n8):
+    return (FAST_ROWS if R not in (256, 512) else FAST_WIDTHS if uw == 0 else FAST_DICTS if vd_u == 0 else FAST_TRIPS if not 1 <= ntrip <= 4
+            else FAST_TABLE if n8 > R else FAST_TAKEN)
+
+
+def vidxw_plan(patterns, W, M, N, R, uw, dict_lengths, fast_off=False):
+    """build_xwin's plan for the patterns (offset tuples, in table order) of a table W wide; uw: the slices' common width or 0;
+    dict_lengths: values per dictionary, one per 256 rows -> dict(verdict=...) and, where the verdict is OK,
+      nwin S lp wp words lds lmin lmax vd_u; win: the window list as uploaded; table: the 16-bit words; ntrip, trips (six of them);
+      fast_clause fast_kind fast_lds"""
+    if any(len(p) > W for p in patterns):
+        return dict(verdict=PATTERN_LENGTH)
+    offsets = sorted({o for p in patterns for o in p})
+    if not offsets:
+        return dict(verdict=NO_ENTRIES)
+    win = windows(offsets, R)
+    if len(win) > SPX_MAXWIN:
+        return dict(verdict=TOO_MANY_WINDOWS)
+    base, size, S = layout(win, R)
+    if S > 65536:
+        return dict(verdict=POSITIONS_16)
+    if M + R + S + max(abs(offsets[0]), abs(offsets[-1])) > INT32_MAX - 8:
+        return dict(verdict=COLUMNS_32)
+    npat, wp, lp = len(patterns), (W + 7) & ~7, (len(patterns) + 7) & ~7
+    if uw > wp:
+        return dict(verdict=SLICE_WIDTH)
+    words = lp + npat * wp
+    lds = ((S + 2) & ~1) * 8 + (R // 256) * VI_MAX * 8 + 2 * words
+    if lds > VW_MAX_LDS:
+        return dict(verdict=LDS_CAP_TEXT)
+    table = np.zeros(words, np.int64)
+    for i, p in enumerate(patterns):
+        table[i] = len(p)
+        at = [8 * position(win, base, o) for o in p] or [0]
+        table[lp + i * wp:lp + (i + 1) * wp] = at + [at[-1]] * (wp - len(at))
+    wlist = [len(win), S] + [v for c in range(len(win)) for v in (base[c], win[c][0] - base[c])] + [INT32_MAX] * (2 * max(0, 4 - len(win)))
+    vd_u = dict_lengths[0] if len(set(dict_lengths)) == 1 else 0
+    per_window = 1 <= len(win) <= 4 and S <= 4 * R and N < DESC_COLS and win[0][0] >= -DESC_COLS and M + win[-1][1] + 2 * R <= DESC_COLS
+    trips = [(base[c] + i0, win[c][0] + i0, min(R, size[c] - i0)) for c in range(len(win)) for i0 in range(0, size[c], R)] if per_window else []
+    if len(trips) > 6:
+        trips = []
+    ntrip = len(trips)
+    clause = fast_rule(R, uw, vd_u, ntrip, words // 8)
+    if clause == FAST_TAKEN and fast_off:
+        clause = FAST_OFF
+    kind = 0 if clause != FAST_TAKEN else 2 if vd_u <= 2 else 1
+    return dict(verdict=OK, windows=win, nwin=len(win), S=S, lp=lp, wp=wp, words=words, lds=lds, lmin=min(map(len, patterns)), lmax=max(map(len, patterns)),
+                vd_u=vd_u, win=wlist, table=table, ntrip=ntrip, trips=trips + [(0, 0, 0)] * (6 - ntrip), fast_clause=clause, fast_kind=kind,
+                fast_lds=0 if kind == 0 else 8 * ((S + 2) & ~1) + (0 if kind == 2 else R // 256 * VI_MAX * 8) + 2 * words)
+
+
+# build_sellpx's refusals, in the order it checks them (it reports none: the codes of xwin_plan.h's SpxRefusal)
+SPX_OK, SPX_NO_ENTRIES, SPX_WINDOW_COUNT, SPX_POSITIONS_16, SPX_WINDOWS_LDS, SPX_TABLE = range(6)
+
+
+def sellpx_plan(patterns, ids, M):
+    """build_sellpx's plan: patterns as offset tuples, ids: the rows' pattern ids -> dict(verdict=code) and, where accepted, nwin S
+    max_words, win (count, then omin / base / size each), wgptr, pat (workgroup-local ids), tab (without its 8 words of padding)"""
+    offsets = sorted({o for p in patterns for o in p})
+    if not offsets:
+        return dict(verdict=SPX_NO_ENTRIES)
+    win = windows(offsets, SPX_ROWS)
+    if len(win) > SPX_MAXWIN:
+        return dict(verdict=SPX_WINDOW_COUNT)
+    base, size, S = layout(win, SPX_ROWS)
+    if S > 65535:
+        return dict(verdict=SPX_POSITIONS_16)
+    if 8 * S >= SPX_LDS_BYTES:
+        return dict(verdict=SPX_WINDOWS_LDS)
+    room = (SPX_LDS_BYTES - 8 * S) // 2
+    tab, wgptr, pat, max_words = [], [0], [], 0
+    for r0 in range(0, M, SPX_ROWS):
+        used = []
+        for i in ids[r0:r0 + SPX_ROWS]:
+            if i not in used:
+                used.append(i)
+            pat.append(used.index(i))
+        used = used or [0]
+        body = [[len(patterns[i])] + ([position(win, base, o) for o in patterns[i]] or [0]) for i in used]
+        words = (len(used) + sum(map(len, body)) + 3) // 4 * 4
+        max_words = max(max_words, words)
+        if words > room or words > 65535 or len(tab) + words > INT32_MAX - 8:
+            return dict(verdict=SPX_TABLE)
+        starts = [len(used) + sum(map(len, body[:k])) for k in range(len(used))]
+        flat = starts + [v for b in body for v in b]
+        tab += flat + [0] * (words - len(flat))
+        wgptr.append(len(tab))
+    return dict(verdict=SPX_OK, windows=win, nwin=len(win), S=S, max_words=max_words, win=[len(win)] + [v for c in range(len(win)) for v in (win[c][0], base[c], size[c])],
+                wgptr=wgptr, pat=pat, tab=tab)
+
+
 def setup_line(g):
     """the fields of the library's line "x windows for the value-indexed form: workgroups of R rows, n windows, S doubles of x ... = K
     KiB of LDS" (SAENA_SETUP_TIMING=1) -> (R, n, S, "K")"""
