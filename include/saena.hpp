@@ -6,7 +6,7 @@
 // of include/data_struct.h:36-38, so that a driver such as experiments/Poisson.cpp ports by
 // replacing `MPI_Comm` with `saena::comm` -- or, unchanged, by including include/saena_mpi.hpp instead
 // (MPI_Comm overloads; tests/test_cpp_surface.py compiles the reference's flow against it).  Only the members on (or feeding) the V-cycle hot path
-// are provided; lazy updates, PETSc bridges etc. are out of scope; solve_GMRES / solve_pGMRES mirror the reference's compiled-out bodies.
+// are provided (update1 / update2 of the lazy-update path among them); update3, PETSc bridges etc. are out of scope; solve_GMRES / solve_pGMRES mirror the reference's compiled-out bodies.
 //
 // Differences from the reference, all at the boundary:
 //   * the communicator is the GPU runtime's (one process = one rank = one MI355X, RCCL), wrapped
@@ -235,6 +235,14 @@ public:
 
     void set_dynamic_levels(const bool &dl = true);
     int set_matrix(saena::matrix *A, saena::options *opts);   // smoothed-aggregation setup (host) + upload
+    // A matrix of the same size with other values (its pattern may differ too) through the hierarchy set_matrix built (reference
+    // saena.hpp:236-237; one rank, more throw "one rank").  update1: A_new replaces the finest operator, nothing else changes.
+    // update2: every coarse operator is rebuilt as R A P over the kept aggregates, P and R -- the setup without its strength graph,
+    // aggregation, smoothed P and transpose; the number of levels stays.  The caller keeps A_new alive and may destroy the old
+    // matrix; the right-hand side stays set.  After a throw the hierarchy is as it was.
+    // update3, the reference's local-difference approximation of update2, is not provided.
+    int update1(saena::matrix *A_new);
+    int update2(saena::matrix *A_new);
     int set_rhs(saena::vector &rhs);                          // note: this function copies the rhs
     int set_rhs(const value_t *rhs_local, index_t size);      // already partitioned like A (interior numbering)
 
@@ -317,6 +325,7 @@ private:
     float dense_thre_override_ = 0;
     int max_level_override_ = -1;
     void drop_device();
+    int update(saena::matrix *A_new, int mode);
     // which: 0 solve, 1 solve_pCG, 2 solve_CG, 3 solve_smoother, 4 solve_pFGMRES (the only one that reads restart / precondition)
     int run(value_t *&u, saena::options *opts, int which, bool print_info, int restart = 0, bool precondition = true);
     int gmres_compiled_out(const char *name, value_t *&u, saena::options *opts);

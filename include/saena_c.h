@@ -156,6 +156,16 @@ saena_amg_h *saena_amg_new(void);
 void  saena_amg_free(saena_amg_h *S);
 /* saena::amg::set_matrix (saena.hpp:202): smoothed-aggregation setup on the host */
 int   saena_amg_set_matrix(saena_amg_h *S, saena_matrix_h *A, const saena_options_c *opts);
+/* saena::amg::update1 / update2 (saena.hpp, src/saena_object_lazy.cpp:7-77): A_new -- assembled, as many rows as the matrix of
+ * set_matrix, its values and even its pattern free -- becomes level 0 of the hierarchy S already holds.  One rank.
+ * mode 1: nothing else changes.  mode 2: every coarse operator is rebuilt as R A P over the kept aggregates and transfer
+ * operators (the setup's own products, filter schedule and eig_max estimate); the number of levels stays.  The caller keeps A_new
+ * alive and may free the old matrix.  [GPU] After saena_amg_to_device the refreshed levels (level 0; every level for mode 2)
+ * get new device operators, made as to_device makes them and installed with sgpu_amg_set_operator; saena_amg_device_op(S, l, 0)
+ * returns new handles for them, (S, l, 1 | 2) the same P and R as before.  Refused, with the hierarchy on the host and on the
+ * device exactly as it was: no set_matrix yet, a hierarchy over more than one rank ("one rank"), A_new not assembled or of
+ * another size, another mode, a coarsest operator the direct solve cannot factor. */
+int   saena_amg_update(saena_amg_h *S, saena_matrix_h *A_new, int mode);
 int   saena_amg_num_levels(saena_amg_h *S);                               /* max_level + 1 */
 /* coarse id of every fine row of `level` (the reference's `aggregate` after aggregate_index_update, src/saena_object_setup1.cpp:
  * 2103-2260); one-rank setups keep it, for the pins of the setup (tests/test_sa_pins.py).  out: rows of that level */

@@ -251,6 +251,19 @@ int sgpu_solve_pCG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, valu
  * replaces the iteration limit, tolerance, smoother (0 jacobi, 1 chebyshev) and sweep counts of an existing
  * hierarchy.  Captured V-cycle graphs are dropped when the V-cycle shape changes. */
 int sgpu_amg_set_solve_params(sgpu_amg *h, int solver_max_iter, double solver_tol, int smoother, int preSmooth, int postSmooth);
+/* Replace A of one level by an operator of the same size (saena::amg::update1 / update2, src/saena_object_lazy.cpp:7-77: other
+ * values, possibly another pattern).  One rank; P, R and every other level stay.  In this order: the arguments are checked --
+ * level in 0..nlevels-1, A_new square with the level's M and without a remote part, inv_diag present unless this is the coarsest
+ * level, eig_max > 0 under Chebyshev on a non-coarsest level, a context of one rank: anything else is SGPU_ERR_ARG; both streams are
+ * waited for; EVERY captured graph of the hierarchy is dropped (the scalar cache, the multi-rank tail, the block caches, FGMRES's and
+ * LOBPCG's: they hold raw pointers into the outgoing operator), so the next call of each captures again; on the coarsest level with
+ * coarse_solver 1 the dense inverse is recomputed (a singular operator is SGPU_ERR_ARG); the Chebyshev direction of A_new is
+ * allocated, for the scalar V-cycle and for every block work space the hierarchy already has (a capture must not allocate); then
+ * A[level] and eig_max[level] are swapped.  After any error the hierarchy is as it was: the old operator, the old inverse.  The work
+ * vectors of the hierarchy and the block, FGMRES and LOBPCG work spaces stay (the sizes are equal); only their graphs go.  The old
+ * operator is neither destroyed nor touched: as with sgpu_amg_create the caller owns the operators, and destroys the old one after
+ * this call returns.  No stored SpMV form is refreshed in place: A_new comes from sgpu_op_create and the plan cache or autotune. */
+int sgpu_amg_set_operator(sgpu_amg *h, int level, sgpu_op *A_new, value_t eig_max);
 /* saena_object::profile_matvecs (saena_object.cpp:618-638): average time of `iter` matvecs with A of every level;
  * us_per_level[nlevels] receives microseconds (this rank, HIP events around the launches, halo included). */
 int sgpu_amg_profile_matvecs(sgpu_amg *h, int iter, double *us_per_level);

@@ -15,7 +15,8 @@
 //   * the helpers those drivers take from the reference's other headers: saena::find_split (aux_functions2.cpp:1511-1528),
 //     print_time (aux_functions.cpp:72-128), saena_free / saena_aligned_alloc (aux_functions.h:299-312), read_from_file_rhs
 //     (aux_functions.cpp:347-497: the rhs reader of experiments/profile_file.cpp), omp_get_wtime when OpenMP is off.
-// Out of the path's scope and therefore absent: GMRES, lazy updates, the Nektar++ set_matrix, PETSc (solve_petsc compiles and
+// saena::amg::update1 / update2 come with saena.hpp: one rank works, more ranks throw ("one rank").
+// Out of the path's scope and therefore absent: GMRES, update3, the Nektar++ set_matrix, PETSc (solve_petsc compiles and
 // reports that it is not available).
 #pragma once
 #ifndef SAENA_MPI_HPP

@@ -99,6 +99,7 @@ SYMBOLS = {
     "sgpu_solve_smoother": (C.c_int, [_VP, _VP, _VP, _PI, _PD, C.c_int]),
     "sgpu_amg_set_solve_params": (C.c_int, [_VP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]),
     "sgpu_amg_profile_matvecs": (C.c_int, [_VP, C.c_int, _PD]),
+    "sgpu_amg_set_operator": (C.c_int, [_VP, C.c_int, _VP, C.c_double]),
     "sgpu_coarsest_solve": (C.c_int, [_VP, _VP, _VP, _PI]),
     "sgpu_debug_on_fatal_print": (C.c_int, [C.c_char_p]),
     "sgpu_debug_launch_count": (C.c_int, [C.POINTER(C.c_long)]),
@@ -675,6 +676,13 @@ class Amg:
 
     def set_solve_params(self, max_iter, tol, smoother, pre, post):
         check(lib().sgpu_amg_set_solve_params(self.h, int(max_iter), float(tol), 0 if smoother == "jacobi" else 1, int(pre), int(post)))
+
+    def set_operator(self, level, op, eig_max=0.0):
+        """sgpu_amg_set_operator: `op` replaces A of `level` (same size, one rank); every captured graph of the hierarchy is dropped.
+        The operator it replaces stays alive and the caller's: destroy it after this call.  Returns that operator."""
+        check(lib().sgpu_amg_set_operator(self.h, int(level), op.h, float(eig_max)))
+        old, self.A[level] = self.A[level], op
+        return old
 
     def profile_matvecs(self, iters=5):
         us = np.zeros(len(self.A))

@@ -624,14 +624,36 @@ struct PhaseTimer {       // SAENA_SETUP_TIMING=1: per-level phase times of the 
     bool on = std::getenv("SAENA_SETUP_TIMING") != nullptr;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     int level;
-    explicit PhaseTimer(int l) : level(l) {}
+    const char *tag;
+    explicit PhaseTimer(int l, const char *tg = "setup") : level(l), tag(tg) {}
     void lap(const char *what) {
         if (!on) return;
         const auto n = std::chrono::steady_clock::now();
-        fprintf(stderr, "[setup L%d] %-22s %8.3f s\n", level, what, std::chrono::duration<double>(n - t).count());
+        fprintf(stderr, "[%s L%d] %-22s %8.3f s\n", tag, level, what, std::chrono::duration<double>(n - t).count());
         t = n;
     }
 };
+
+// The tail of coarsen, shared with update(): Ac = (R A) P (triple_mat_mult, setup2:361-849), the filter at this level's step
+// of the threshold schedule (setup2:117-121, :852-916; the caller owns the schedule's two counters), and the assembled
+// operator (setup2:341 matrix_setup).  The pattern of Ac is whatever the products and the filter keep for THESE values.
+std::unique_ptr<saena_matrix> galerkin_coarse(Comm &c, const Csr &Rc, const Csr &Af, const Csr &Pc, const amg_options &opts,
+                                              int &filter_it, double &filter_thre_cur, PhaseTimer &pt) {
+    Csr RA = spgemm(Rc, Af);
+    pt.lap("R*A");
+    Csr AcN = spgemm(RA, Pc);
+    RA = Csr();
+    pt.lap("(RA)*P");
+    if (++filter_it >= opts.filter_start) {
+        if (filter_thre_cur > opts.filter_max) filter_thre_cur = opts.filter_max;
+        filter_csr(AcN, filter_thre_cur);
+        filter_thre_cur *= std::pow(10, opts.filter_rate);
+    }
+    pt.lap("filter");
+    std::unique_ptr<saena_matrix> Ac(new saena_matrix(&c));
+    Ac->setup_from_csr(Pc.ncols, AcN.ptr, std::move(AcN.col), std::move(AcN.val));
+    return Ac;
+}
 } // namespace
 
 int amg_hierarchy::coarsen(int l) {
@@ -702,21 +724,9 @@ int amg_hierarchy::coarsen(int l) {
     Csr Rc = transpose(Pc);
     pt.lap("R = P^T");
 
-    // ---- Ac = (R A) P  (triple_mat_mult, setup2:361-849) ----
-    Csr RA = spgemm(Rc, Ac_);
-    pt.lap("R*A");
-    Csr AcN = spgemm(RA, Pc);
-    RA = Csr();
-    pt.lap("(RA)*P");
+    // ---- Ac = (R A) P, filtered, assembled: the part update() repeats over kept transfer operators ----
+    std::unique_ptr<saena_matrix> Ac = galerkin_coarse(c, Rc, Ac_, Pc, opts, filter_it, filter_thre_cur, pt);
 
-    // ---- filter (setup2:117-121, :852-916) ----
-    if (++filter_it >= opts.filter_start) {
-        if (filter_thre_cur > opts.filter_max) filter_thre_cur = opts.filter_max;
-        filter_csr(AcN, filter_thre_cur);
-        filter_thre_cur *= std::pow(10, opts.filter_rate);
-    }
-
-    pt.lap("filter");
     // ---- hand the three operators over in the reference's layout ----
     transfer_matrix &P = g.P;
     P.comm = &c; P.Mbig = A.Mbig; P.Nbig = new_size; P.M = A.M;
@@ -729,8 +739,7 @@ int amg_hierarchy::coarsen(int l) {
     R.nnz_l = R.nnz_g = Rc.ptr[new_size];
     R.L.build_single_rank(new_size, A.M, Rc.ptr, std::move(Rc.col), std::move(Rc.val));
 
-    g.Ac_store.reset(new saena_matrix(&c));
-    g.Ac_store->setup_from_csr(new_size, AcN.ptr, std::move(AcN.col), std::move(AcN.val));   // setup2:341 matrix_setup
+    g.Ac_store = std::move(Ac);
     pt.lap("layouts of P, R, Ac");
     return ret_val;
 }
@@ -755,6 +764,65 @@ int amg_hierarchy::setup(saena_matrix *A, const amg_options &o) {
     }
     levels.resize((size_t)max_level + 1);
     return 0;
+}
+
+// update1 / update2 (saena::amg::update1 / update2, src/saena_object_lazy.cpp:7-77): new operator values through the kept
+// aggregates and transfer operators.  Everything is built aside and committed at the end, so a throw leaves the hierarchy as it was.
+int amg_hierarchy::update(saena_matrix *A_new, int mode, update_undo *undo) {
+    if (!dist.empty()) throw std::runtime_error("amg update: the hierarchy was built over more than one rank; update runs on one rank only");
+    if (levels.empty() || !levels[0].A) throw std::runtime_error("amg update: there is no hierarchy yet (set_matrix has not been called)");
+    if (mode != 1 && mode != 2) throw std::runtime_error("amg update: mode " + std::to_string(mode) + " is not 1 (update1) or 2 (update2)");
+    if (!A_new) throw std::runtime_error("amg update: null matrix");
+    if (A_new->comm->nranks != 1 || levels[0].A->comm->nranks != 1) throw std::runtime_error("amg update: runs on one rank only");
+    if (!A_new->assembled) throw std::runtime_error("amg update: the matrix is not assembled");
+    if (A_new->Mbig != levels[0].A->Mbig)
+        throw std::runtime_error("amg update: the matrix has " + std::to_string(A_new->Mbig) + " rows, level 0 of the hierarchy has " +
+                                 std::to_string(levels[0].A->Mbig));
+    const bool cheby = opts.smoother == "chebyshev";
+    // (a value the caller set on A_new is kept, as setup keeps it; an unset one is computed into a local first)
+    const bool eig0_missing = cheby && std::fabs(A_new->eig_max_of_invdiagXA) < SAENA_ALMOST_ZERO;
+    PhaseTimer pt0(0, "update");
+    const double eig0 = eig0_missing ? find_eig(*A_new) : A_new->eig_max_of_invdiagXA;
+    if (eig0_missing) pt0.lap("find_eig");
+    std::vector<std::unique_ptr<saena_matrix>> fresh;
+    if (mode == 2) {
+        // the schedule the setup walked, from its start: one step per coarsened level
+        double thre = opts.filter_thre;
+        int it = 0;
+        const saena_matrix *Af = A_new;
+        for (int l = 0; l < max_level; ++l) {
+            PhaseTimer pt(l, "update");
+            const amg_level &g = levels[(size_t)l];
+            const Csr Ac_ = csr_of(Af->L, Af->Mbig), Pc = csr_of(g.P.L, g.P.Nbig), Rc = csr_of(g.R.L, g.R.Nbig);
+            pt.lap("CSR views of R, A, P");
+            fresh.push_back(galerkin_coarse(*A_new->comm, Rc, Ac_, Pc, opts, it, thre, pt));
+            pt.lap("layout of Ac");
+            if (cheby) { fresh.back()->eig_max_of_invdiagXA = find_eig(*fresh.back()); pt.lap("find_eig"); }
+            Af = fresh.back().get();
+        }
+    }
+    // ---- commit: nothing below throws ----
+    if (undo) { undo->A0 = levels[0].A; undo->mode = mode; undo->Ac.clear(); undo->Ac.reserve(fresh.size()); }   // (reserved here: no push_back below allocates)
+    if (eig0_missing) A_new->eig_max_of_invdiagXA = eig0;
+    levels[0].A = A_new;
+    if (mode == 2)
+        for (int l = 0; l < max_level; ++l) {
+            levels[(size_t)l].Ac_store.swap(fresh[(size_t)l]);
+            levels[(size_t)l + 1].A = levels[(size_t)l].Ac_store.get();
+            if (undo) undo->Ac.push_back(std::move(fresh[(size_t)l]));
+        }
+    return 0;
+}
+
+void amg_hierarchy::undo_update(update_undo &u) {
+    if (!u.A0) return;
+    levels[0].A = u.A0;
+    if (u.mode == 2)
+        for (int l = 0; l < max_level && (size_t)l < u.Ac.size(); ++l) {
+            levels[(size_t)l].Ac_store = std::move(u.Ac[(size_t)l]);
+            levels[(size_t)l + 1].A = levels[(size_t)l].Ac_store.get();
+        }
+    u = update_undo();
 }
 
 // ---------------------------------------------------------------------------

@@ -117,6 +117,24 @@ public:
 
     // saena_object::setup (saena_object.cpp:175-406)
     int setup(saena_matrix *A, const amg_options &o);
+    // saena::amg::update1 / update2 (src/saena_object_lazy.cpp:7-77): a matrix of the same size with other values (its
+    // pattern may differ too) through the hierarchy setup() built.  One rank.  A_new becomes level 0 and must outlive the
+    // hierarchy; the matrix it replaces is no longer referenced.
+    //   mode 1: nothing else changes -- every coarser A, every P, R, roots and agg stays bit for bit.
+    //   mode 2: every coarse A is rebuilt over the KEPT P, R and aggregates by the tail of coarsen: (R A) P through the same
+    //           spgemm (and hook), the filter on the threshold schedule replayed from opts, setup_from_csr; then find_eig where
+    //           setup calls it.  The result is what setup(A_new) would build if its aggregation and transfer operators were
+    //           the old hierarchy's.  The pattern of a coarse level follows the values (the products drop |v| <= 1e-14, the
+    //           filter lumps by threshold), so nothing of the old coarse operators is reused.  eig_max is recomputed, where the
+    //           reference carries the old value over.  The number of levels never changes.
+    // Throws -- and leaves the hierarchy exactly as it was -- when there is no hierarchy yet, when it was built over more than
+    // one rank, when A_new is not assembled or has another Mbig, and for any other mode.  SAENA_SETUP_TIMING=1 prints the
+    // phases as "[update L<l>] ...".
+    // `undo` (optional) receives what the update replaced; undo_update() puts it back -- for a caller whose own follow-up (the
+    // device side of saena_amg_update) can still fail after the host side has committed.
+    struct update_undo { saena_matrix *A0 = nullptr; int mode = 0; std::vector<std::unique_ptr<saena_matrix>> Ac; };
+    int update(saena_matrix *A_new, int mode, update_undo *undo = nullptr);
+    void undo_update(update_undo &u);
 
     // Multi-rank use: setup_distributed -> setup_rows_distributed, every rank builds its rows of every level (`dist`).
     // Partition per level: the fine split is A's; a coarse level inherits it through the aggregates (splitNew[r] =

@@ -313,6 +313,58 @@ int amg::set_matrix(saena::matrix *A, saena::options *opts) {
     return 0;
 }
 
+// saena::amg::update1 / update2 (saena.cpp, src/saena_object_lazy.cpp:7-77): the host hierarchy first (amg_hierarchy::update), then
+// the refreshed levels' device operators, made as set_matrix makes them and installed with sgpu_amg_set_operator
+int amg::update(saena::matrix *A_new, int mode) {
+    if (!H_ || !damg_) throw std::runtime_error("saena::amg::update: there is no hierarchy yet (set_matrix first)");
+    if (!A_new) throw std::runtime_error("saena::amg::update: null matrix");
+    saena_host::amg_hierarchy::update_undo undo;
+    H_->update(A_new->get_internal_matrix(), mode, &undo);          // throws, the hierarchy untouched: more than one rank, size, mode, not assembled
+    const int n = H_->max_level + 1, nl = mode == 1 ? 1 : n;
+    std::vector<sgpu_op *> fresh((size_t)nl, nullptr);
+    std::vector<double> old_eig((size_t)nl, 0.0);
+    int done = nl;
+    try {
+        const saena_host::amg_options &o = H_->opts;
+        const bool tune = !std::getenv("SAENA_NO_AUTOTUNE");
+        for (int l = 0; l < nl; ++l) {
+            sgpu_op *op = nullptr;
+            if (l == 0) op = A_new->device_op();
+            else {
+                const saena_host::amg_level &g = H_->levels[(size_t)l];
+                sgpu_op_desc d;
+                fill_desc(g.A->L, &g.A->inv_diag, &d);
+                d.halo_fp32 = l >= o.float_level ? 1 : 0;
+                gchk(sgpu_op_create(&d, &op), "sgpu_op_create(A)");
+                fresh[(size_t)l] = op;
+            }
+            if (tune) gchk(sgpu_op_autotune(op), "sgpu_op_autotune");
+            if (l >= 1 && o.switch_to_dense) {            // saena_object_setup2.cpp:328
+                const double rows = (double)H_->level_rows(l), dens = (double)H_->level_nnzA(l) / (rows * rows);
+                if (dens > o.dense_thre && rows <= o.dense_sz_thre) sgpu_op_set_variant(op, forms::F_DENSE);
+            }
+            if (l == 0) fresh[0] = op;
+        }
+        for (int l = nl - 1; l >= 0; --l) {               // coarsest first: its factorisation is the step that refuses an operator
+            gchk(sgpu_amg_set_operator(damg_, l, fresh[(size_t)l], H_->level_eig(l)), "sgpu_amg_set_operator");
+            done = l;
+        }
+    } catch (...) {                                       // the device and the host hierarchy as they were
+        H_->undo_update(undo);
+        for (int l = done; l < nl; ++l) sgpu_amg_set_operator(damg_, l, dA_[(size_t)l], H_->level_eig(l));
+        for (int l = 1; l < nl; ++l) if (fresh[(size_t)l]) sgpu_op_destroy(fresh[(size_t)l]);
+        throw;
+    }
+    for (int l = 0; l < nl; ++l) {
+        if (l >= 1) sgpu_op_destroy(dA_[(size_t)l]);      // level-0 A belongs to its saena::matrix
+        dA_[(size_t)l] = fresh[(size_t)l];
+    }
+    A_ = A_new;
+    return 0;
+}
+int amg::update1(saena::matrix *A_new) { return update(A_new, 1); }
+int amg::update2(saena::matrix *A_new) { return update(A_new, 2); }
+
 int vector::print_entry(int ran) {
     if (ran < 0 || ran == c_.rank()) {
         printf("vector on proc %d, size %zu\n", c_.rank(), val_.size());

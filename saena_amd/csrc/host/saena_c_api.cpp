@@ -22,6 +22,7 @@ struct saena_amg_h {
     bool set = false;
     // device side (libsaena_amd.so only)
     std::vector<sgpu_op *> dA, dP, dR;
+    std::vector<double> deig;                 // eig_max of every dA, as the device hierarchy holds it
     sgpu_amg *damg = nullptr;
 };
 
@@ -291,6 +292,23 @@ int saena_amg_set_matrix(saena_amg_h *S, saena_matrix_h *A, const saena_options_
     });
 }
 
+#ifdef SAENA_WITH_GPU
+static int refresh_device(saena_amg_h *S, int mode);
+#endif
+int saena_amg_update(saena_amg_h *S, saena_matrix_h *A_new, int mode) {
+    if (!S || !A_new) { h_err = "saena_amg_update: null argument"; return -1; }
+    if (!S->set) { h_err = "saena_amg_update: there is no hierarchy yet (set_matrix has not been called)"; return -1; }
+    amg_hierarchy::update_undo undo;
+    if (guard([&] { S->H.update(&A_new->A, mode, &undo); })) return -1;
+#ifdef SAENA_WITH_GPU
+    if (S->damg) {
+        const int s = refresh_device(S, mode);
+        if (s) { S->H.undo_update(undo); return s; }       // the device side is as it was: so is the host side
+    }
+#endif
+    return 0;
+}
+
 int saena_amg_num_levels(saena_amg_h *S) { return S->set ? S->H.max_level + 1 : 0; }
 
 int saena_amg_level_split(saena_amg_h *S, int l, index_t *split_out) {
@@ -353,26 +371,68 @@ static int gchk(int s) { if (s != 0) { h_err = sgpu_last_error(); } return s; }
 static void drop_device(saena_amg_h *S) {
     if (S->damg) { sgpu_amg_destroy(S->damg); S->damg = nullptr; }
     for (auto *v : {&S->dA, &S->dP, &S->dR}) { for (sgpu_op *o : *v) sgpu_op_destroy(o); v->clear(); }
+    S->deig.clear();
 }
 void saena_amg_free(saena_amg_h *S) { if (S) { drop_device(S); delete S; } }
+
+// The device operator of A on level l, as to_device and update make it: the level's layout, its halo wire type, the plan cache
+// or autotune, the dense form where the options ask for it.
+static int make_device_A(saena_amg_h *S, int l, sgpu_op **out) {
+    sgpu_op_desc d; sgpu_op *o = nullptr;
+    // float_level (saena_object.cpp:241-244,277-285): A of level >= float_level, P/R of level >= float_level
+    // exchange their halos in fp32 (compute stays fp64).  Only matters with more than one rank.
+    if (saena_amg_level_desc(S, l, 0, &d)) return -1;
+    d.halo_fp32 = l >= S->H.opts.float_level ? 1 : 0;
+    if (gchk(sgpu_op_create(&d, &o))) return -2;
+    // right after the create: the host copy of the values lives only until then
+    if (!std::getenv("SAENA_NO_AUTOTUNE") && gchk(sgpu_op_autotune(o))) { sgpu_op_destroy(o); return -2; }
+    if (S->H.opts.switch_to_dense && l >= 1) {   // saena_object_setup2.cpp:328: switch_to_dense && density > dense_thre && Mbig <= dense_sz_thre
+        const double rows = (double)S->H.level_rows(l), dens = (double)S->H.level_nnzA(l) / (rows * rows);
+        if (dens > S->H.opts.dense_thre && rows <= S->H.opts.dense_sz_thre) sgpu_op_set_variant(o, forms::F_DENSE);   // refused (halo, size): stays sparse
+    }
+    *out = o;
+    return 0;
+}
+
+// the device half of saena_amg_update: new A operators for the refreshed levels, installed with sgpu_amg_set_operator; the old
+// ones go only after every replacement has succeeded, and on a failure the installed ones are put back
+static int refresh_device(saena_amg_h *S, int mode) {
+    const int n = S->H.max_level + 1, nl = mode == 1 ? 1 : n;
+    std::vector<sgpu_op *> fresh((size_t)nl, nullptr);
+    auto drop_fresh = [&] { for (sgpu_op *o : fresh) if (o) sgpu_op_destroy(o); };
+    for (int l = 0; l < nl; ++l)
+        if (const int s = make_device_A(S, l, &fresh[(size_t)l])) { drop_fresh(); return s; }
+    int done = nl, st = 0;                                  // coarsest first: its factorisation is the step that refuses an operator
+    for (int l = nl - 1; l >= 0 && !st; --l) {
+        st = sgpu_amg_set_operator(S->damg, l, fresh[(size_t)l], S->H.level_eig(l));
+        if (!st) done = l;
+    }
+    if (st) {
+        const std::string why = sgpu_last_error();
+        for (int l = done; l < nl; ++l) sgpu_amg_set_operator(S->damg, l, S->dA[(size_t)l], S->deig[(size_t)l]);
+        drop_fresh();
+        h_err = why;
+        return st;
+    }
+    for (int l = 0; l < nl; ++l) {
+        sgpu_op_destroy(S->dA[(size_t)l]);
+        S->dA[(size_t)l] = fresh[(size_t)l];
+        S->deig[(size_t)l] = S->H.level_eig(l);
+    }
+    return 0;
+}
 
 int saena_amg_to_device(saena_amg_h *S) {
     if (!S->set) { h_err = "set_matrix has not been called"; return -1; }
     drop_device(S);
     const int n = S->H.max_level + 1;
-    std::vector<double> eig;
+    const int fl = S->H.opts.float_level;
+    const bool tune = !std::getenv("SAENA_NO_AUTOTUNE");
     for (int l = 0; l < n; ++l) {
         sgpu_op_desc d; sgpu_op *o = nullptr;
-        // float_level (saena_object.cpp:241-244,277-285): A of level >= float_level, P/R of level >= float_level
-        // exchange their halos in fp32 (compute stays fp64).  Only matters with more than one rank.
-        const int fl = S->H.opts.float_level;
-        if (saena_amg_level_desc(S, l, 0, &d)) return -1;
-        d.halo_fp32 = l >= fl ? 1 : 0;
-        if (gchk(sgpu_op_create(&d, &o))) return -2;
+        if (const int s = make_device_A(S, l, &o)) return s;
         S->dA.push_back(o);
-        const bool tune = !std::getenv("SAENA_NO_AUTOTUNE");     // right after each create: the host copy of the values lives only until then
-        if (tune && gchk(sgpu_op_autotune(o))) return -2;
-        eig.push_back(S->H.level_eig(l));
+        S->deig.push_back(S->H.level_eig(l));
         if (l < n - 1) {
             if (saena_amg_level_desc(S, l, 1, &d)) return -1;
             d.halo_fp32 = l >= fl ? 1 : 0; if (gchk(sgpu_op_create(&d, &o))) return -2; S->dP.push_back(o);
@@ -382,17 +442,12 @@ int saena_amg_to_device(saena_amg_h *S) {
             if (tune && gchk(sgpu_op_autotune(o))) return -2;
         }
     }
-    if (S->H.opts.switch_to_dense)            // saena_object_setup2.cpp:328: switch_to_dense && density > dense_thre && Mbig <= dense_sz_thre
-        for (int l = 1; l < n; ++l) {
-            const double rows = (double)S->H.level_rows(l), dens = (double)S->H.level_nnzA(l) / (rows * rows);
-            if (dens > S->H.opts.dense_thre && rows <= S->H.opts.dense_sz_thre) sgpu_op_set_variant(S->dA[(size_t)l], forms::F_DENSE);   // refused (halo, size): stays sparse
-        }
     sgpu_amg_params p;
     sgpu_amg_default_params(&p);
     const amg_options &o = S->H.opts;
     p.preSmooth = o.preSmooth; p.postSmooth = o.postSmooth; p.smoother = o.smoother == "jacobi" ? 0 : 1;
     p.solver_max_iter = o.solver_max_iter; p.solver_tol = o.relative_tol;
-    return gchk(sgpu_amg_create(n, S->dA.data(), S->dP.data(), S->dR.data(), eig.data(), &p, &S->damg));
+    return gchk(sgpu_amg_create(n, S->dA.data(), S->dP.data(), S->dR.data(), S->deig.data(), &p, &S->damg));
 }
 
 sgpu_amg *saena_amg_device_handle(saena_amg_h *S) { return S->damg; }

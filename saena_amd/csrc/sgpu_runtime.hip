@@ -3403,6 +3403,33 @@ int vcycle0(sgpu_amg *h, double *u, const double *rhs, bool u_zero = false) {
     return SGPU_OK;
 }
 
+// dense inverse of a small one-rank operator by Gauss-Jordan with partial pivoting, on the host (the direct coarsest solve of
+// sgpu_amg_create and sgpu_amg_set_operator); inv: row-major M x M
+int dense_inverse(const sgpu_op *Ac, std::vector<double> &inv) {
+    const int n = Ac->M;
+    std::vector<double> a((size_t)n * n, 0.0);
+    inv.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) {
+        inv[(size_t)i * n + i] = 1.0;
+        for (int k = Ac->loc.h_rp[i]; k < Ac->loc.h_rp[i + 1]; ++k) a[(size_t)i * n + Ac->loc.h_col[k]] = Ac->h_val[k];
+    }
+    for (int c = 0; c < n; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < n; ++r) if (std::fabs(a[(size_t)r * n + c]) > std::fabs(a[(size_t)piv * n + c])) piv = r;
+        if (a[(size_t)piv * n + c] == 0.0) return fail(SGPU_ERR_ARG, "coarsest operator is singular");
+        if (piv != c) for (int j = 0; j < n; ++j) { std::swap(a[(size_t)piv * n + j], a[(size_t)c * n + j]); std::swap(inv[(size_t)piv * n + j], inv[(size_t)c * n + j]); }
+        const double d = 1.0 / a[(size_t)c * n + c];
+        for (int j = 0; j < n; ++j) { a[(size_t)c * n + j] *= d; inv[(size_t)c * n + j] *= d; }
+        for (int r = 0; r < n; ++r) {
+            if (r == c) continue;
+            const double f = a[(size_t)r * n + c];
+            if (f == 0.0) continue;
+            for (int j = 0; j < n; ++j) { a[(size_t)r * n + j] -= f * a[(size_t)c * n + j]; inv[(size_t)r * n + j] -= f * inv[(size_t)c * n + j]; }
+        }
+    }
+    return SGPU_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3458,27 +3485,8 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
     h->coarse_host_driven = coarse_local && coarse_big;   // the same on every rank: the host-driven CG is collective
     if (h->prm.coarse_solver == 1 && coarse_local && A[nlevels - 1]->M > 0 && !h->coarse_host_driven) {
         // dense inverse by Gauss-Jordan with partial pivoting (host, once)
-        sgpu_op *Ac = A[nlevels - 1];
-        const int n = Ac->M;
-        std::vector<double> a((size_t)n * n, 0.0), inv((size_t)n * n, 0.0);
-        for (int i = 0; i < n; ++i) {
-            inv[(size_t)i * n + i] = 1.0;
-            for (int k = Ac->loc.h_rp[i]; k < Ac->loc.h_rp[i + 1]; ++k) a[(size_t)i * n + Ac->loc.h_col[k]] = Ac->h_val[k];
-        }
-        for (int c = 0; c < n; ++c) {
-            int piv = c;
-            for (int r = c + 1; r < n; ++r) if (std::fabs(a[(size_t)r * n + c]) > std::fabs(a[(size_t)piv * n + c])) piv = r;
-            if (a[(size_t)piv * n + c] == 0.0) return fail(SGPU_ERR_ARG, "coarsest operator is singular");
-            if (piv != c) for (int j = 0; j < n; ++j) { std::swap(a[(size_t)piv * n + j], a[(size_t)c * n + j]); std::swap(inv[(size_t)piv * n + j], inv[(size_t)c * n + j]); }
-            const double d = 1.0 / a[(size_t)c * n + c];
-            for (int j = 0; j < n; ++j) { a[(size_t)c * n + j] *= d; inv[(size_t)c * n + j] *= d; }
-            for (int r = 0; r < n; ++r) {
-                if (r == c) continue;
-                const double f = a[(size_t)r * n + c];
-                if (f == 0.0) continue;
-                for (int j = 0; j < n; ++j) { a[(size_t)r * n + j] -= f * a[(size_t)c * n + j]; inv[(size_t)r * n + j] -= f * inv[(size_t)c * n + j]; }
-            }
-        }
+        std::vector<double> inv;
+        CHK(dense_inverse(A[nlevels - 1], inv));
         CHK(dev_upload(h->Ainv, inv.data(), inv.size()));
     }
     for (int l = 0; l < nlevels - 1; ++l)          // no allocation may happen inside a graph capture
@@ -3803,6 +3811,43 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 #include "sgpu_block.hip.inc"
 #include "sgpu_gmres.hip.inc"
 #include "sgpu_eig.hip.inc"
+
+// sgpu_amg_set_operator (include/saena_gpu.h).  After the block helpers: the block work space of a hierarchy keeps a Chebyshev
+// direction per operator and K, which the incoming operator does not have yet.
+extern "C" int sgpu_amg_set_operator(sgpu_amg *h, int level, sgpu_op *A_new, value_t eig_max) {
+    CHK(need_ctx());
+    if (!h || !A_new) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: null argument");
+    if (g.nranks > 1 || g.multi()) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: runs on one rank only (this context has %d)", g.nranks);
+    if (level < 0 || level >= h->nlevels) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: level %d is outside 0..%d", level, h->nlevels - 1);
+    const bool coarsest = level == h->nlevels - 1;
+    if (A_new->M != A_new->N_local) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator is not square (%d x %d)", A_new->M, A_new->N_local);
+    if (A_new->M != h->A[level]->M) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator has %d rows, level %d has %d", A_new->M, level, h->A[level]->M);
+    if (A_new->has_remote || A_new->recvSize || A_new->vIndexSize) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator has a remote part; runs on one rank only");
+    if (!coarsest && !A_new->inv_diag && A_new->M > 0) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator has no inv_diag");
+    if (!coarsest && h->prm.smoother == 1 && !(eig_max > 0.0)) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: chebyshev needs eig_max > 0");
+    // nothing in flight, then no captured launch that names the outgoing operator's arrays
+    HIPCHK(hipStreamSynchronize(g.cs));
+    HIPCHK(hipStreamSynchronize(g.hs));
+    h->drop_graphs();
+    // everything that can fail, aside
+    DevArr<double> Ainv;
+    const bool direct = coarsest && h->prm.coarse_solver == 1 && h->coarse_local && A_new->M > 0 && !(A_new->M > sk::CG_MAXN);
+    if (direct) {
+        if (A_new->h_val.size() != A_new->loc.h_col.size()) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator keeps no host copy of its values to factor");
+        std::vector<double> inv;
+        CHK(dense_inverse(A_new, inv));
+        CHK(dev_upload(Ainv, inv.data(), inv.size()));
+    }
+    // what a capture must not allocate: the Chebyshev direction (scalar, and per K of every block work space that exists)
+    if (!coarsest && h->prm.smoother == 1) CHK(ensure_d(A_new));
+    for (int K : {2, 4, 8})
+        if (h->blk[block_slot(K)]) { CHK(ensure_blk_d(A_new, K)); CHK(ensure_blk_halo(A_new, K)); }
+    // commit
+    if (direct) h->Ainv = std::move(Ainv);
+    h->A[(size_t)level] = A_new;
+    h->eig[(size_t)level] = eig_max;
+    return SGPU_OK;
+}
 
 // ===========================================================================
 // Setup-time collectives of the host layer over the same RCCL communicator

@@ -89,6 +89,7 @@ HOST_SYMBOLS.update({
     "saena_amg_new": (_VP, []),
     "saena_amg_free": (None, [_VP]),
     "saena_amg_set_matrix": (C.c_int, [_VP, _VP, C.POINTER(OptionsC)]),
+    "saena_amg_update": (C.c_int, [_VP, _VP, C.c_int]),
     "saena_amg_num_levels": (C.c_int, [_VP]),
     "saena_amg_level_info": (C.c_int, [_VP, C.c_int, _PI, C.POINTER(C.c_long), C.POINTER(C.c_long), _PD]),
     "saena_amg_level_aggregates": (C.c_int, [_VP, C.c_int, _PI, _PI]),
@@ -493,6 +494,15 @@ class AmgSolver:
         self.h = self.L.saena_amg_new()
         _check(self.L, self.L.saena_amg_set_matrix(self.h, A.h, C.byref(opts)))
         self.opts = opts
+
+    def update(self, A_new: Matrix, mode):
+        """saena::amg::update1 / update2 (saena_amg_update): A_new, of the same size, becomes level 0 of the built hierarchy.  mode 1:
+        nothing else changes; mode 2: every coarse operator is rebuilt over the kept aggregates, P and R.  One rank.  A hierarchy
+        that is on the device gets new device operators for the refreshed levels.  A_new must stay alive; a refusal raises and
+        leaves the hierarchy as it was."""
+        _check(self.L, self.L.saena_amg_update(self.h, A_new.h, int(mode)))
+        self.A = A_new
+        return self
 
     @property
     def num_levels(self):
