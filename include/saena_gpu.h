@@ -173,6 +173,11 @@ int sgpu_op_get_x_windows(const sgpu_op *op, int *rows_per_workgroup);
  * launched in the mode: what its LAST launch ran (a halo launch or another epilogue of an eligible operator runs k_vidxw).
  * Results are bit-identical whichever runs. */
 int sgpu_op_get_x_window_kernel(const sgpu_op *op, int *kernel);
+/* bits per entry of the code stream variant 17 reads on this operator: 8 for k_vidx, k_vidxw and k_vidxw_fast on the 8-bit codes,
+ * 1 where k_vidxw_fast with scalar dictionaries (kernel 2) reads the codes packed to one bit per entry (every code is 0 or 1 there;
+ * SAENA_VIDXW_BITS=0, read when the windows are built, keeps the 8-bit codes); 0: the operator is not on variant 17.  Once the
+ * operator was launched in the mode: what its LAST launch read.  Results are bit-identical in both formats. */
+int sgpu_op_get_x_window_code_width(const sgpu_op *op, int *bits_per_entry);
 /* time the (variant, lanes) candidates that apply to this operator and keep the fastest (plan-time autotune; no
  * collective).  Call it right after sgpu_op_create: operators of up to 768 entries per row hold a host copy of their
  * values (8 B per entry) for the re-ordered forms from the create until this call -- or until sgpu_op_destroy. */

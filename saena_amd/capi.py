@@ -72,6 +72,7 @@ SYMBOLS = {
     "sgpu_op_set_x_windows": (C.c_int, [_VP, C.c_int]),
     "sgpu_op_get_x_windows": (C.c_int, [_VP, _PI]),
     "sgpu_op_get_x_window_kernel": (C.c_int, [_VP, _PI]),
+    "sgpu_op_get_x_window_code_width": (C.c_int, [_VP, _PI]),
     "sgpu_spmv": (C.c_int, [_VP, _VP, _VP]),
     "sgpu_residual": (C.c_int, [_VP, _VP, _VP, _VP]),
     "sgpu_residual_negative": (C.c_int, [_VP, _VP, _VP, _VP]),
@@ -430,6 +431,13 @@ class Operator:
         1 k_vidxw_fast with its dictionaries in LDS, 2 k_vidxw_fast with dictionaries of at most two values in scalar registers"""
         v = C.c_int()
         check(lib().sgpu_op_get_x_window_kernel(self.h, C.byref(v)))
+        return v.value
+
+    def x_window_code_width(self):
+        """bits per entry of the code stream variant 17 reads (of the last launch in the mode, once there was one): 8, or 1 where
+        k_vidxw_fast reads the codes of scalar dictionaries packed to one bit per entry; 0: another variant"""
+        v = C.c_int()
+        check(lib().sgpu_op_get_x_window_code_width(self.h, C.byref(v)))
         return v.value
 
     def exchange_mode(self):

@@ -900,14 +900,16 @@ __device__ __forceinline__ double vw_pick(unsigned w, int bit, unsigned long lon
 // pos: the row's pattern (LDS byte offsets for the workgroup's first row), xr: the lane's row in the windows, cc: the codes of the
 // first turn, ld_codes(j): those of positions j ... j + 7; len: the row's length; w8: the slice's positions; lmin / lmax: the shortest
 // and the longest pattern, body0 = vwfast::body(lmin, lmax, 0).  The values: dw[code] (the wave's dictionary in LDS), or with SD one of
-// the two values s0 / s1 of a dictionary that stays in scalar registers, by bit 0 of the code.
-template <bool SD, class LdCodes>
+// the two values s0 / s1 of a dictionary that stays in scalar registers, by bit 0 of the code.  BITS (with SD alone): a turn's codes are
+// ONE byte, bit u the code of position j + u (vw_fast.h: bit codes), CC an unsigned; else CC is sk_u2v, eight bytes of codes.
+template <bool SD, bool BITS, class CC, class LdCodes>
 __device__ __forceinline__ double vw_row_sum(const unsigned short *pos, const char *xr, const double *dw, unsigned long long s0, unsigned long long s1,
-                                             int len, int w8, int lmin, int lmax, int body0, sk_u2v cc, LdCodes ld_codes) {
+                                             int len, int w8, int lmin, int lmax, int body0, CC cc, LdCodes ld_codes) {
+    static_assert(!BITS || SD, "bit codes: scalar dictionaries only");
     double sum = 0.0;
     // N positions of a trip, the first four without a select where every row holds them (FREE4).  A position past the row's length
     // adds -0.0, which changes no sum (signed zeros and NaNs included): the row sum stays k_vidx's, bit for bit, without a branch
-    auto trip = [&](auto NN, auto FREE4, int j, const sk_u2v cc) {
+    auto trip = [&](auto NN, auto FREE4, int j, const CC cc) {
         constexpr int N = decltype(NN)::value;
         const sk_u4v pp = *reinterpret_cast<const sk_u4v *>(pos + j);
         double xx[N], dv[N];
@@ -915,7 +917,8 @@ __device__ __forceinline__ double vw_row_sum(const unsigned short *pos, const ch
         for (int u = 0; u < N; ++u) {
             const unsigned w = u < 2 ? pp.x : u < 4 ? pp.y : u < 6 ? pp.z : pp.w;
             xx[u] = *reinterpret_cast<const double *>(xr + ((u & 1) ? (w >> 16) : (w & 0xffffu)));
-            if constexpr (SD) dv[u] = vw_pick(u < 4 ? cc.x : cc.y, 8 * (u & 3), s0, s1);
+            if constexpr (BITS) dv[u] = vw_pick(cc, u, s0, s1);
+            else if constexpr (SD) dv[u] = vw_pick(u < 4 ? cc.x : cc.y, 8 * (u & 3), s0, s1);
             else dv[u] = dw[((u < 4 ? cc.x : cc.y) >> (8 * (u & 3))) & 0xffu];
         }
 #pragma unroll
@@ -926,7 +929,7 @@ __device__ __forceinline__ double vw_row_sum(const unsigned short *pos, const ch
         }
     };
     for (int j = 0; j < w8; j += 8) {                              // (w8 <= pt_w: no row is longer than the longest pattern)
-        sk_u2v cn = cc;
+        CC cn = cc;
         if (j + 8 < w8) cn = ld_codes(j + 8);
         // wave-uniform: the positions at or beyond the longest pattern are not computed (never fewer than four, though: the
         // lengths 1 ... 3 share the body of 4), those below the shortest take no select
@@ -1066,7 +1069,7 @@ __global__ __launch_bounds__(1024) void k_vidxw(const SpmvArgs a, const VwHead h
     const int len = row ? (int)tab[pid] : 0;
     const unsigned short *pos = tab + lp + pid * a.pt_w;
     const char *xr = reinterpret_cast<const char *>(xw + tid);
-    const double sum = vw_row_sum<false>(pos, xr, dict + dw0, 0ull, 0ull, len, w8, lmin, lmax, vwfast::body(lmin, lmax, 0), cc, ld_codes);
+    const double sum = vw_row_sum<false, false>(pos, xr, dict + dw0, 0ull, 0ull, len, w8, lmin, lmax, vwfast::body(lmin, lmax, 0), cc, ld_codes);
     if (row) {
         if constexpr (PREF) {                                      // epilogue<>'s arithmetic on the operands fetched at the top
             if constexpr (EPI == EPI_RESIDUAL) st_y<NT>(a, a.y + r0 + (unsigned)tid, sum - pre_b);
@@ -1094,10 +1097,13 @@ typedef double sk_gdouble;
 // SD: the dictionaries hold at most two values; the wave's two are loaded as scalars with the prologue's loads (the wave's dictionary
 // is uniform; vi_dict is padded by one element for the dictionary of ONE value at the end) and a position's value is picked by bit 0
 // of its code: no dictionary in LDS, no LDS read per position for the value.
+// BITS (with SD alone): arg.vcode holds the bit codes and arg.cbytes their bytes per slice (vw_fast.h): a lane's turn is one byte,
+// loaded where the eight bytes of codes were, and a position's value is picked by bit u of it.
 // blockDim.x = R; dynamic LDS: [windows of x][R / 256 dictionaries of VI_MAX unless SD][table] (vwfast::plan).
-template <int R, int EPI, bool NT, bool SD>
+template <int R, int EPI, bool NT, bool SD, bool BITS = false>
 __global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
     static_assert((R == 256 || R == 512) && (EPI == EPI_SPMV || EPI == EPI_RESIDUAL || EPI == EPI_JACOBI), "vw_fast.h: the rule");
+    static_assert(!BITS || SD, "vw_fast.h: bit codes where the dictionaries stay in scalar registers");
     extern __shared__ __attribute__((aligned(16))) double vw_lds[];
     constexpr int SH = R == 256 ? 2 : 3, D = R >> 8;                // log2(slices) and dictionaries per workgroup
     // the argument, whole, in scalar registers HERE: one batch of loads and one wait.  The compiler would sink each field's load to its
@@ -1126,8 +1132,10 @@ __global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
     const unsigned tc = min((unsigned)tid, (unsigned)(f.nrows - 1 - r0));      // a valid row for the loads of a lane without one
     // ---- 1. every global load of the lane: codes, pattern id, the epilogue's operands, the dictionary, a table chunk, the windows
     const bool ntv = NT && s >= f.nt_from;
-    const sk_u2v *c8 = reinterpret_cast<const sk_u2v *>(f.vcode + sc * f.cbytes);
-    auto ld_codes = [&](int j) { const unsigned i = (unsigned)((j >> 3) * 64 + lane); sk_u2v v; if (ntv) v = __builtin_nontemporal_load(c8 + i); else v = c8[i]; return v; };
+    using CC = std::conditional_t<BITS, unsigned, sk_u2v>;            // a turn's codes: a byte of bits, or eight bytes
+    using CElem = std::conditional_t<BITS, unsigned char, sk_u2v>;
+    const CElem *c8 = reinterpret_cast<const CElem *>(f.vcode + sc * f.cbytes);
+    auto ld_codes = [&](int j) -> CC { const unsigned i = (unsigned)((j >> 3) * 64 + lane); CElem v; if (ntv) v = __builtin_nontemporal_load(c8 + i); else v = c8[i]; return v; };
     int pid;
     if constexpr (NT) pid = __builtin_nontemporal_load(f.dst + r0 + tc); else pid = (f.dst + r0)[tc];
     double pre_b = 0.0, pre_dg = 0.0, pre_u = 0.0;
@@ -1136,7 +1144,7 @@ __global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
         if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(f.inv_diag + r0 + tc); pre_u = (f.u + r0)[tc]; }
     }
     const sk_u4v tc0 = reinterpret_cast<const sk_u4v *>(f.ptab)[tid < f.n8 ? tid : 0];
-    sk_u2v cc = ld_codes(0);
+    CC cc = ld_codes(0);
     unsigned long long s0 = 0, s1 = 0, d0v = 0, d1v = 0;
     double dv0 = 0.0;
     if constexpr (SD) {                                            // the wave's dictionary (a spare wave: the workgroup's first), as two scalars
@@ -1177,7 +1185,7 @@ __global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
     const int len = row ? (int)reinterpret_cast<const unsigned short *>(lds + f.tab_off)[pid] : 0;
     const unsigned short *pos = reinterpret_cast<const unsigned short *>(lds + f.pos_off + pid * f.pw2);
     const double *dw = reinterpret_cast<const double *>(lds + f.dict_off) + (D > 1 ? __builtin_amdgcn_readfirstlane(tid >> 8) * f.vd_u : 0);
-    const double sum = vw_row_sum<SD>(pos, lds + t8, dw, s0, s1, len, f.w8, f.lmin, f.lmax, f.body0, cc, ld_codes);
+    const double sum = vw_row_sum<SD, BITS>(pos, lds + t8, dw, s0, s1, len, f.w8, f.lmin, f.lmax, f.body0, cc, ld_codes);
     if (row) {
         sk_gdouble *yp = reinterpret_cast<sk_gdouble *>(y_bits) + r0 + (unsigned)tid;
         double out = sum;                                          // epilogue<>'s arithmetic on the operands fetched at the top
@@ -2211,6 +2219,17 @@ __global__ __launch_bounds__(BLOCK) void k_sell_scatter(const T *__restrict__ sr
             dst[o] = src[q0 + j];
         }
     }
+}
+
+// ---- setup: k_vidx's codes -> the bit codes of k_vidxw_fast (vw_fast.h).  The eight codes of a lane's turn are one 8-byte word and
+// the words lie in the order of the bit codes' bytes, padding included: thread i packs word i into byte i.  A code above 1 raises *above1
+// (build_xwin then keeps the byte codes).  nwords: 8-byte words of the code array = bytes of the bit array.
+__global__ __launch_bounds__(BLOCK) void k_vi_pack_bits(const sk_u2v *__restrict__ code, unsigned char *__restrict__ bits, unsigned nwords, int *__restrict__ above1) {
+    const unsigned i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nwords) return;
+    const sk_u2v c = code[i];
+    bits[i] = (unsigned char)vwfast::pack8(c.x, c.y);
+    if (vwfast::above1(c.x, c.y)) atomicOr(above1, 1);
 }
 
 // ---- setup: the 8-bit value codes and per-workgroup dictionaries of k_vidx, on the device ----

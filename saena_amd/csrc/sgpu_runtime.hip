@@ -213,14 +213,17 @@ struct CsrPart {
     } vi;
     int             vi_uw8 = 0;           // every slice has this many code positions (a multiple of 8), or 0: read vi_cptr
     int64_t         vi_bytes = 0;         // codes + pattern ids + x + y as this form stores them
+    int64_t         vi_code_bytes = 0;    // ... the codes alone (without the padding behind them)
     // ... launched with x in LDS windows (k_vidxw, a MODE of variant 17: sgpu_op_set_x_windows): per workgroup size R = 256 << k the
     // window list and the ONE table as 16-bit LDS byte offsets -- two small tables next to k_vidx's arrays -- and plan: what of
     // xwin_plan.h's plan every launch passes by value (the head, the common-path kernel's argument) or sizes its LDS by; vw_rows: the R in
-    // use, 0 = direct gathers
-    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; xwplan::VwScalars plan; bool ok = false; char tried = 0; };
+    // use, 0 = direct gathers.  bits: the codes at one bit per entry (vw_fast.h), where the plan at this R keeps its dictionaries in scalar
+    // registers -- packed from vi_code by build_xwin, read by k_vidxw_fast alone, and gone with the tables of this R
+    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; DevArr<unsigned char> bits; xwplan::VwScalars plan; bool ok = false; char tried = 0; };
     XWin            vw[3];
     int             vw_rows = 0;
     mutable int     vw_last = -1;         // what the last launch in the mode ran (0 k_vidxw, 1 / 2 k_vidxw_fast as fast_kind), -1: none since the mode was set
+    mutable int     vw_last_width = -1;   // ... and the bits per entry of the code stream it read (8, or 1: the bit codes), -1: none
     // x in LDS (variant 10): absolute 16-bit column ids and nnz-balanced row chunks, one per CU.  The chunk plan (k_sellx is built
     // on top of it) ...
     struct XldsPlan {
@@ -280,7 +283,7 @@ unsigned part_storage_mask(const CsrPart &P) {
         P.sc.sl_col || P.sc.sl_len || P.sc.sl_base || P.sc.sl_segptr,
         P.sp.sp_pat || P.sp.sp_tab || P.sp.sp_wgptr || P.sp.sp_rbase,
         P.vi.vi_code || P.vi.vi_cptr || P.vi.vi_dptr || P.vi.vi_dict,
-        P.vw[0].tab || P.vw[0].win, P.vw[1].tab || P.vw[1].win, P.vw[2].tab || P.vw[2].win,
+        P.vw[0].tab || P.vw[0].win || P.vw[0].bits, P.vw[1].tab || P.vw[1].win || P.vw[1].bits, P.vw[2].tab || P.vw[2].win || P.vw[2].bits,
         P.sp2.sp2_val || P.sp2.sp2_ptr,
         P.spx.spx_tab || P.spx.spx_pat || P.spx.spx_win || P.spx.spx_wgptr,
         P.rt.rt_pat || P.rt.rt_itab || P.rt.rt_vtab,
@@ -1086,7 +1089,7 @@ int build_vidx(CsrPart &P) {
     SGPU_LAUNCH(sk::k_vi_compact, dim3(ngrp), dim3(sk::BLOCK), 0, g.cs, (const double *)tmp, (const int *)P.vi.vi_dptr, P.vi.vi_dict.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.cs));
-    P.vi_uw8 = sw.uw;
+    P.vi_uw8 = sw.uw; P.vi_code_bytes = tot;
     P.vi_bytes = tot + (P.sp.sp_rbase ? 6 : 2) * (int64_t)M + 8 * (int64_t)P.ncols + 8 * (int64_t)M + 8 * (int64_t)dptr[(size_t)ngrp];
     P.vi.vi_ok = true;
     if (std::getenv("SAENA_SETUP_TIMING"))
@@ -1120,7 +1123,28 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     if (plan.refusal) return no(xwplan::refusal_text(plan.refusal));
     CHK(dev_upload(X.tab, plan.tab.data(), plan.tab.size(), 8));
     CHK(dev_upload(X.win, plan.win.data(), plan.win.size()));
-    X.plan = plan.s; X.ok = true;
+    X.plan = plan.s;
+    // the bit codes (vw_fast.h), where the dictionaries stay in scalar registers: packed on the device from k_vidx's codes, padding
+    // included (build_vidx allocated 64 uw bytes per slice + CODE_PAD); a code above 1 -- none, by the dictionaries' lengths -- keeps the bytes
+    const char *bits_env = std::getenv("SAENA_VIDXW_BITS");
+    const bool bits_off = bits_env && std::atoi(bits_env) == 0;
+    const int ns = (M + 63) / 64;
+    const int64_t byte_codes = P.vi_code_bytes, bit_bytes = byte_codes / 8;
+    const char *bits_why = plan.s.fast_kind == 0 ? "the general kernel is kept" : plan.s.fast_kind == 1 ? "the dictionaries are in LDS" : "SAENA_VIDXW_BITS=0";
+    if (vwfast::bit_codes(plan.s.fast_kind, bits_off)) {
+        const size_t nb = (size_t)vwfast::bit_total(ns, P.vi_uw8);
+        DevArr<int> d_flag;
+        if (X.bits.alloc(nb) != hipSuccess || d_flag.alloc(1) != hipSuccess) { X.bits = {}; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", nb); }
+        HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g.cs));
+        SGPU_LAUNCH(sk::k_vi_pack_bits, dim3((unsigned)((nb + sk::BLOCK - 1) / sk::BLOCK)), dim3(sk::BLOCK), 0, g.cs, reinterpret_cast<const sk::sk_u2v *>(P.vi.vi_code.get()),
+                    X.bits.get(), (unsigned)nb, d_flag.get());
+        HIPCHK(hipGetLastError());
+        int above1 = 0;
+        HIPCHK(hipMemcpyAsync(&above1, d_flag, sizeof(int), hipMemcpyDeviceToHost, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
+        if (above1) { X.bits = {}; bits_why = "a code above 1"; }
+    }
+    X.ok = true;
     if (std::getenv("SAENA_SETUP_TIMING")) {
         const xwplan::VwScalars &s = X.plan;
         fprintf(stderr, "[sgpu] x windows for the value-indexed form: workgroups of %d rows, %d windows, %lld doubles of x + %d dictionaries + %lld table words = %.1f KiB of LDS (%.1f B of x per row); staged %s (%d trips)\n",
@@ -1130,6 +1154,10 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
                     s.fast_kind == 2 ? "scalar registers" : "LDS", s.fast_lds);
         else
             fprintf(stderr, "[sgpu] x windows at %d rows: the general kernel is kept (%s)\n", R, vwfast::clause_text(s.fast_clause));
+        if (X.bits)
+            fprintf(stderr, "[sgpu] x windows at %d rows: codes of 1 bit per entry, %lld bytes packed from %lld bytes of 8-bit codes\n", R, (long long)bit_bytes, (long long)byte_codes);
+        else
+            fprintf(stderr, "[sgpu] x windows at %d rows: codes of 8 bits per entry (%s), %lld bytes, 1-bit codes would take %lld\n", R, bits_why, (long long)byte_codes, (long long)bit_bytes);
     }
     return SGPU_OK;
 }
@@ -1456,9 +1484,11 @@ VidxwKernelFn pick_vidxw(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> VidxwKernelFn { return sk::k_vidxw<E(), H(), N()>; }); }); });
 }
 // the common path (vw_fast.h): 256 / 512 rows, the three epilogues with operands fetched up front, dictionaries in LDS / in scalar registers
-VidxwFastKernelFn pick_vidxw_fast(int rows, int epi, bool nt, bool sd) {
-    return among<256, 512>(rows, [&](auto R) { return among<sk::EPI_SPMV, sk::EPI_RESIDUAL, sk::EPI_JACOBI>(epi, [&](auto E) { return with_bool(nt, [&](auto N) { return with_bool(sd, [&](auto S) -> VidxwFastKernelFn {
-        return sk::k_vidxw_fast<R(), E(), N(), S()>; }); }); }); });
+// bits (with sd alone): the codes at one bit per entry
+VidxwFastKernelFn pick_vidxw_fast(int rows, int epi, bool nt, bool sd, bool bits) {
+    if (bits && !sd) return nullptr;
+    return among<256, 512>(rows, [&](auto R) { return among<sk::EPI_SPMV, sk::EPI_RESIDUAL, sk::EPI_JACOBI>(epi, [&](auto E) { return with_bool(nt, [&](auto N) { return with_bool(sd, [&](auto S) {
+        return with_bool(bits, [&](auto B) -> VidxwFastKernelFn { return sk::k_vidxw_fast<R(), E(), N(), S(), S() && B()>; }); }); }); }); });
 }
 SellKernelFn pick_rowt(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_rowt<E(), H(), N()>; }); }); });
@@ -1649,13 +1679,20 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
                 vwfast::VwFast f = X.plan.fast;
                 if (f.nblk != a.nblk) return fail(SGPU_ERR_STATE, "the x windows were planned for %d slices, the launch has %d", f.nblk, a.nblk);
                 f.vcode = a.vcode; f.dst = a.dst; f.ptab = X.tab.get(); f.vdict = a.vdict;
+                // the bit codes where build_xwin packed them: an eighth of the code stream, and the non-temporal rule is given what this launch reads
+                const bool bits = X.plan.fast_kind == 2 && X.bits;
+                bool ntf = nt;
+                if (bits) {
+                    f.vcode = X.bits.get(); f.cbytes = vwfast::bit_slice_bytes(f.w8);
+                    ntf = row_pattern_nt(a, P.vi_bytes - P.vi_code_bytes + P.vi_code_bytes / 8, a.nblk, (double)P.nnz / 8.0 / (double)std::max(1, a.nblk));
+                }
                 f.x = a.x; f.y = a.y; f.rhs = a.rhs; f.inv_diag = a.inv_diag; f.u = a.u; f.c0 = a.c0;
                 f.nt_from = a.nt_from; f.st_plain = a.st_plain; f.nrows = P.nrows;
-                P.vw_last = X.plan.fast_kind;
-                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, nt, X.plan.fast_kind == 2), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.fast_lds, g.cs, f);
+                P.vw_last = X.plan.fast_kind; P.vw_last_width = vwfast::code_width(bits);
+                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, ntf, X.plan.fast_kind == 2, bits), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.fast_lds, g.cs, f);
                 break;
             }
-            P.vw_last = 0;
+            P.vw_last = 0; P.vw_last_width = 8;
             SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.lds, g.cs, a, X.plan.head, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
@@ -2520,7 +2557,7 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
     if (!ok) return refuse_form(variant);
     op->loc.variant = variant;
     op->loc.vw_rows = 0;                                 // F_VIDX alone gathers directly; sgpu_op_set_x_windows turns the windows on
-    op->loc.vw_last = -1;
+    op->loc.vw_last = -1; op->loc.vw_last_width = -1;
     ++g_plan_generation;
     if (variant == F_VIDX)
         if (const char *e = std::getenv("SAENA_X_WINDOWS")) {     // development: pin the mode where only the variant can be pinned (counter passes); refused -> direct
@@ -2537,7 +2574,7 @@ int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
     CHK(need_ctx());
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     const int R = rows_per_workgroup;
-    op->loc.vw_last = -1;
+    op->loc.vw_last = -1; op->loc.vw_last_width = -1;
     if (R == 0) { op->loc.vw_rows = 0; ++g_plan_generation; return SGPU_OK; }
     const int k = xwin_slot(R);
     if (k < 0) return fail(SGPU_ERR_ARG, "x windows: rows per workgroup must be 0 (off), 256, 512 or 1024");
@@ -2564,6 +2601,16 @@ int sgpu_op_get_x_window_kernel(const sgpu_op *op, int *kernel) {
     const CsrPart &P = op->loc;
     const int k = P.variant == F_VIDX ? xwin_slot(P.vw_rows) : -1;
     *kernel = k < 0 ? 0 : P.vw_last >= 0 ? P.vw_last : P.vw[k].plan.fast_kind;
+    return SGPU_OK;
+}
+
+// bits per entry of the code stream the last launch of variant 17 read: 1 where k_vidxw_fast ran on the bit codes (vw_fast.h), 8
+// for k_vidx, k_vidxw and k_vidxw_fast on the byte codes; before a launch: what a launch without a halo would read; 0: not variant 17
+int sgpu_op_get_x_window_code_width(const sgpu_op *op, int *bits_per_entry) {
+    if (!op || !bits_per_entry) return fail(SGPU_ERR_ARG, "null argument");
+    const CsrPart &P = op->loc;
+    const int k = P.variant == F_VIDX ? xwin_slot(P.vw_rows) : -1;
+    *bits_per_entry = P.variant != F_VIDX ? 0 : k < 0 ? 8 : P.vw_last_width >= 0 ? P.vw_last_width : vwfast::code_width(P.vw[k].plan.fast_kind == 2 && P.vw[k].bits);
     return SGPU_OK;
 }
 

@@ -40,6 +40,32 @@ constexpr int kind(int clause, int vd_u) { return clause != TAKEN ? 0 : scalar_d
 // Jacobi sweep (2): the epilogues k_vidxw treats with operands fetched up front (kernels.hip.h: sk::Epi)
 constexpr bool launch_takes(int kind_, bool halo, int epi) { return kind_ != 0 && !halo && epi >= 0 && epi <= 2; }
 
+// ---- bit codes: the codes of an operator with scalar dictionaries are 0 or 1 and the kernel reads bit 0 alone, so the lean kernel
+// streams ONE BIT per entry: byte [slice][turn j / 8][lane] holds, as bit u, bit 0 of the code of position j + u.  A lane's turn is one
+// byte where k_vidx's codes are eight; every entry still carries a code of its own.  build_xwin packs the array from k_vidx's codes
+// (which k_vidx, k_vidxw and every halo launch go on reading); both arrays end in one turn of one slice of zeros.
+constexpr int CODE_PAD = 512;                     // bytes k_vidx's codes are padded by: a turn of a slice (64 lanes x 8 positions)
+constexpr int BIT_PAD = CODE_PAD / 8;             // ... and the bit codes: the same turn
+// taken exactly where the dictionaries stay in scalar registers (kind 2), unless SAENA_VIDXW_BITS=0 (bits_off)
+constexpr bool bit_codes(int kind_, bool bits_off) { return kind_ == 2 && !bits_off; }
+// bits per entry of the code stream a launch reads
+constexpr int code_width(bool bits) { return bits ? 1 : 8; }
+// bytes of a slice of uw positions (a multiple of 8): an eighth of its 64 uw bytes of codes
+constexpr int bit_slice_bytes(int uw) { return 8 * uw; }
+constexpr int64_t bit_total(int nslices, int uw) { return (int64_t)nslices * bit_slice_bytes(uw) + BIT_PAD; }
+// the byte of (slice, turn, lane), turn < uw / 8, lane < 64 ...
+constexpr int64_t bit_index(int slice, int turn, int lane, int uw) { return (int64_t)slice * bit_slice_bytes(uw) + (int64_t)turn * 64 + lane; }
+// ... and the byte of k_vidx's codes that holds position j of that lane (k_vi_build's layout: a lane's turn is eight bytes side by
+// side).  The eight codes of bit_index(s, t, l, uw) begin at 8 bit_index(s, t, l, uw): the pack is one pass over 8-byte words
+constexpr int64_t code_index(int slice, int j, int lane, int uw) { return (int64_t)slice * 64 * uw + ((int64_t)(j >> 3) * 64 + lane) * 8 + (j & 7); }
+// a turn's eight codes (c[0]: position j, as the low byte of the low word) -> its byte; above1: a code that is neither 0 nor 1
+constexpr unsigned pack8(unsigned lo, unsigned hi) {
+    unsigned b = 0;
+    for (int u = 0; u < 4; ++u) b |= ((lo >> (8 * u)) & 1u) << u | ((hi >> (8 * u)) & 1u) << (4 + u);
+    return b;
+}
+constexpr bool above1(unsigned lo, unsigned hi) { return ((lo | hi) & 0xfefefefeu) != 0; }
+
 // ---- the row loop's body, for both kernels: positions j ... j + 7 of a row, lmin / lmax the shortest and the longest pattern ----
 // the positions at or beyond the longest pattern are not computed (never fewer than four: the lengths 1 ... 3 share the body of 4),
 // the first four take no select where every row holds them -> 2 (n - 4) + free4, n = 4 ... 8
@@ -68,7 +94,7 @@ struct Trip {
 // below, and the operator's arrays); launch_part copies it and sets x, y, rhs, inv_diag, u, c0, nt_from, st_plain, nrows.
 struct VwFast {
     // the prologue's loads
-    const unsigned char  *vcode;      // k_vidx's codes
+    const unsigned char  *vcode;      // k_vidx's codes, or the bit codes (launch_part sets this and cbytes by the format)
     const unsigned short *dst;        // pattern ids
     const void           *ptab;       // the table as 16-bit words (build_xwin's), read in 16-byte chunks
     const double         *vdict;      // the dictionaries back to back
@@ -76,7 +102,7 @@ struct VwFast {
     const double         *rhs, *inv_diag, *u;
     int nrows, nblk;                  // rows; slices of 64 rows
     int rq, rr;                       // the XCD remap: workgroups / NXCD, workgroups % NXCD
-    int cbytes;                       // bytes of a slice's codes: 64 uw
+    int cbytes;                       // bytes of a slice's codes: 64 uw (bit codes: 8 uw)
     int n8;                           // 16-byte chunks of the table (1 ... R)
     int vd_u, ngd;                    // values per dictionary; dictionaries of the operator
     unsigned xbytes;                  // 8 ncols: the buffer descriptor's num_records
