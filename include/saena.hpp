@@ -88,6 +88,10 @@ public:
 
     void set_eig(const std::string &opts_fname);   // reads the optional eig="..." attribute of the options XML
     void set_eig(double eig);
+    // NOT in the reference: the value set_eig(double) takes, estimated on the device (sgpu_op_eig_max: the setup's Lanczos recurrence,
+    // `steps` of them, through this matrix's device operator, which is created if it does not exist yet).  One rank.  Nothing is stored:
+    // A.set_eig(A.estimate_eig()) before amg::update1(&A) leaves the update without its host Lanczos loop.
+    double estimate_eig(int steps = 20);
     void set_remove_boundary(bool remove_bound);
     // NOT in the reference: resolution of assemble()'s nnz-balanced row partition (0 = the reference's nparts^2 buckets)
     void set_partition_buckets(int n_buckets);
@@ -241,6 +245,10 @@ public:
     // aggregation, smoothed P and transpose; the number of levels stays.  The caller keeps A_new alive and may destroy the old
     // matrix; the right-hand side stays set.  After a throw the hierarchy is as it was.
     // update3, the reference's local-difference approximation of update2, is not provided.
+    // NOT in the reference, opt-in, before set_matrix / update1 / update2: eig_max of every level (Chebyshev smoother) from the device
+    // estimate instead of the host Lanczos loop, on one rank -- the same recurrence, equal within 1e-12 relative, not bit for bit.
+    // Also on with SAENA_DEVICE_EIG=1.  Where the device declines, the host loop runs; a value set with matrix::set_eig is kept.
+    void set_device_eig(bool on);
     int update1(saena::matrix *A_new);
     int update2(saena::matrix *A_new);
     int set_rhs(saena::vector &rhs);                          // note: this function copies the rhs
@@ -324,6 +332,7 @@ private:
     bool switch_to_dense_ = false;
     float dense_thre_override_ = 0;
     int max_level_override_ = -1;
+    bool device_eig_ = false;
     void drop_device();
     int update(saena::matrix *A_new, int mode);
     // which: 0 solve, 1 solve_pCG, 2 solve_CG, 3 solve_smoother, 4 solve_pFGMRES (the only one that reads restart / precondition)

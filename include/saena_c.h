@@ -62,6 +62,11 @@ int   saena_matrix_set_remove_boundary(saena_matrix_h *A, int remove_bound);    
 int   saena_matrix_set_partition_buckets(saena_matrix_h *A, int n_buckets);
 int   saena_matrix_add_duplicates(saena_matrix_h *A, int add);                                      /* :47 */
 int   saena_matrix_set_eig(saena_matrix_h *A, double eig);                                          /* :38 (value form) */
+/* [GPU] the value saena_matrix_set_eig takes, estimated on the device (sgpu_op_eig_max, include/saena_gpu.h: the setup's Lanczos
+ * recurrence, `steps` of them, 0 = the setup's 20) for an assembled matrix on one rank; within 1e-12 relative of what the host setup
+ * computes.  Nothing is stored: pass the value to saena_matrix_set_eig and saena_amg_update(A, 1) runs no host Lanczos.  The device
+ * operator is made for the call (sgpu_op_create) and destroyed. */
+int   saena_matrix_estimate_eig(saena_matrix_h *A, int steps, double *eig_max);
 int   saena_matrix_assemble(saena_matrix_h *A);                                                     /* :49 */
 int   saena_matrix_assemble_with_split(saena_matrix_h *A, const index_t *split);
 index_t saena_matrix_get_num_rows(saena_matrix_h *A);                                               /* :57 */
@@ -166,6 +171,12 @@ int   saena_amg_set_matrix(saena_amg_h *S, saena_matrix_h *A, const saena_option
  * device exactly as it was: no set_matrix yet, a hierarchy over more than one rank ("one rank"), A_new not assembled or of
  * another size, another mode, a coarsest operator the direct solve cannot factor. */
 int   saena_amg_update(saena_amg_h *S, saena_matrix_h *A_new, int mode);
+/* Opt-in, before saena_amg_set_matrix or saena_amg_update: on != 0 lets the one-rank setup and the updates take every level's eig_max
+ * (Chebyshev smoother) from the device estimate instead of the host Lanczos loop -- the same recurrence, equal within 1e-12 relative,
+ * not bit for bit.  Also on with SAENA_DEVICE_EIG=1 in the environment (read at every call).  Off by default.  Where no device context
+ * exists (libsaena_host.so, no sgpu_init), over several ranks, or when the device declines (memory), the host loop runs as before.  A
+ * value set with saena_matrix_set_eig is kept either way. */
+int   saena_amg_set_device_eig(saena_amg_h *S, int on);
 int   saena_amg_num_levels(saena_amg_h *S);                               /* max_level + 1 */
 /* coarse id of every fine row of `level` (the reference's `aggregate` after aggregate_index_update, src/saena_object_setup1.cpp:
  * 2103-2260); one-rank setups keep it, for the pins of the setup (tests/test_sa_pins.py).  out: rows of that level */

@@ -205,7 +205,19 @@ int sgpu_jacobi(sgpu_op *op, int iter, value_t omega, value_t *u, const value_t 
 /* iter Chebyshev steps, u in/out.  saena_matrix::chebyshev (saena_matrix.cpp:1074-1131),
  * eig_max = eig_max_of_invdiagXA (saena_matrix.h:183). */
 int sgpu_chebyshev(sgpu_op *op, int iter, value_t eig_max, value_t *u, const value_t *rhs);
-/* u -= P e : prolong_matrix::matvec followed by the correction loop of
+/* *eig_max = the Chebyshev smoother's eig_max_of_invdiagXA of this operator, estimated on the device: saena_object::find_eig
+ * (saena_object.cpp:572-592, lamlan_saena.h:38-59) as the host setup restates it -- min(steps, M) Lanczos steps on
+ * D^-1/2 A D^-1/2 from a fixed start vector, 1.0001 x the largest eigenvalue of the tridiagonal matrix -- with the recurrence run
+ * through the operator's current SpMV form and streaming kernels with fused partial sums.  steps: 1..64, or 0 for the setup's 20.
+ * The value agrees with the host setup's within 1e-12 relative (not bit for bit: the dots are summed in another order) and is the
+ * same bits from call to call and from process to process.  What sgpu_amg_create and sgpu_amg_set_operator expect in eig_max[l].
+ * SGPU_ERR_ARG, with the reason in sgpu_last_error() and before anything is launched: a null argument, steps outside 0..64, M == 0,
+ * an operator with a remote part or a context of more than one rank, an operator that is not square or has no inv_diag, a capture
+ * open on the compute stream.  The call owns its work space (five vectors of M doubles) and frees it before it returns; it waits for
+ * the compute stream once per step.  The operator is left as a plain sgpu_spmv leaves it: plan, plan cache, x-window mode and every
+ * captured graph untouched. */
+int sgpu_op_eig_max(sgpu_op *op, int steps, value_t *eig_max);
+/* u -= P e: prolong_matrix::matvec followed by the correction loop of
  * saena_object::vcycle (saena_object_solve.cpp:1325,1360-1361), fused. */
 int sgpu_prolong_correct(sgpu_op *P, const value_t *e_coarse, value_t *u);
 

@@ -146,6 +146,10 @@ int sgpu_debug_eig_stop(sgpu_amg *h, int K, int iteration);
 int sgpu_debug_eig_vector(sgpu_amg *h, int K, int which, value_t *dst);
 int sgpu_debug_time_eig(sgpu_amg *h, int kind, int ns, const value_t *X, const value_t *Y, value_t *Out, size_t n, int K, int reps, float *ms_per_run);
 
+/* tests (tests/test_gpu_lanczos.py): begin = 1 opens a capture on the compute stream (thread-local mode), begin = 0 ends it and
+ * discards the graph -- for the entry points that must refuse to run inside a capture.  Nothing is launched in between by the tests. */
+int sgpu_debug_capture(int begin);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,8 @@ SYMBOLS = {
     "sgpu_jacobi": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP]),
     "sgpu_chebyshev": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _VP]),
     "sgpu_prolong_correct": (C.c_int, [_VP, _VP, _VP]),
+    "sgpu_op_eig_max": (C.c_int, [_VP, C.c_int, _PD]),
+    "sgpu_debug_capture": (C.c_int, [C.c_int]),
     "sgpu_debug_pack": (C.c_int, [_VP, _VP, _PD]),
     "sgpu_debug_gather_probe": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_block_plan": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_long)]),
@@ -472,6 +474,13 @@ class Operator:
 
     def prolong_correct(self, e_coarse, u):
         check(lib().sgpu_prolong_correct(self.h, e_coarse.ptr, u.ptr))
+
+    def eig_max(self, steps=20):
+        """the Chebyshev smoother's eig_max of this operator, estimated on the device (sgpu_op_eig_max): the host setup's Lanczos
+        recurrence through the operator's current SpMV form; steps in 1..64, 0 = the setup's 20"""
+        v = C.c_double()
+        check(lib().sgpu_op_eig_max(self.h, int(steps), C.byref(v)))
+        return v.value
 
     # block vectors (BlockVector): K right-hand sides through one pass over the operator
     def set_block_lanes(self, lanes):

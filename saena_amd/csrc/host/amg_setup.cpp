@@ -153,6 +153,8 @@ Csr transpose(const Csr &A) {
 } // namespace
 // C = A B on the GPU when libsaena_amd.so has a device context (sgpu_spgemm.hip installs this; bit-identical result)
 spgemm_hook_fn g_spgemm_hook = nullptr;
+// eig_max of a one-rank level on the GPU, where the caller opted in (amg_setup.h; sgpu_lanczos.hip.inc installs this)
+eig_hook_fn g_eig_hook = nullptr;
 // what the last product did, and every product since spgemm_stats_reset() (amg_setup.h)
 spgemm_stats g_spgemm_last, g_spgemm_total;
 void spgemm_stats_reset() { g_spgemm_last = spgemm_stats(); g_spgemm_total = spgemm_stats(); }
@@ -481,26 +483,10 @@ index_t amg_hierarchy::aggregate(const saena_matrix &A, const std::vector<nnz_t>
     return (index_t)aggArray.size();
 }
 
-// largest eigenvalue of D^-1 A: 20 Lanczos steps on D^-1/2 A D^-1/2 (lamlan_saena.h:38-59,
-// lambda_lanczos.hpp:95 max_iteration = 20), result x 1.0001.  The reference starts from a random
-// vector (its estimate "fluctuates in each execution"); here the start vector is a fixed LCG sequence.
-double amg_hierarchy::find_eig(const saena_matrix &A) {
-    if (A.comm->nranks != 1) throw std::runtime_error("find_eig: multi-rank setup is not implemented in this round");
-    const index_t n = A.M;
-    const Csr C = csr_of(A.L, n);
-    std::vector<double> isd((size_t)n);
-    for (index_t i = 0; i < n; ++i) isd[i] = std::sqrt(std::fabs(A.inv_diag[i]));
-    auto matvec = [&](const std::vector<double> &x, std::vector<double> &y) {
-        parallel_rows(n, &C.ptr, [&](int, index_t lo, index_t hi) {
-            for (index_t i = lo; i < hi; ++i) {
-                double s_ = 0;
-                for (nnz_t k = C.ptr[i]; k < C.ptr[i + 1]; ++k) s_ += C.val[k] * isd[C.col[k]] * x[C.col[k]];
-                y[i] = s_ * isd[i];
-            }
-        });
-    };
-    const int m = std::min<index_t>(20, n);
-    std::vector<double> v((size_t)n), vprev((size_t)n, 0.0), w((size_t)n), alpha, beta;
+// The two ends of find_eig that do not depend on who runs the recurrence: shared with the device estimate (sgpu_op_eig_max,
+// sgpu_lanczos.hip.inc), which replaces the loops in between and nothing else.
+// The start vector: a fixed LCG sequence over the row index in (-1, 1), normalised (the norm summed in row order).
+void lanczos_start_vector(index_t n, double *v) {
     unsigned long long lcg = 88172645463325252ULL;
     double nrm = 0;
     for (index_t i = 0; i < n; ++i) {
@@ -509,22 +495,11 @@ double amg_hierarchy::find_eig(const saena_matrix &A) {
         nrm += v[i] * v[i];
     }
     nrm = std::sqrt(nrm);
-    for (auto &x : v) x /= nrm;
-    double b = 0;
-    for (int k = 0; k < m; ++k) {
-        matvec(v, w);
-        double a = 0;
-        for (index_t i = 0; i < n; ++i) a += w[i] * v[i];
-        alpha.push_back(a);
-        for (index_t i = 0; i < n; ++i) w[i] -= a * v[i] + b * vprev[i];
-        b = 0;
-        for (index_t i = 0; i < n; ++i) b += w[i] * w[i];
-        b = std::sqrt(b);
-        if (k + 1 < m) beta.push_back(b);
-        if (b < 1e-300) break;
-        vprev = v;
-        for (index_t i = 0; i < n; ++i) v[i] = w[i] / b;
-    }
+    for (index_t i = 0; i < n; ++i) v[i] /= nrm;
+}
+// 1.0001 x the largest eigenvalue of the Lanczos tridiagonal matrix (diagonal alpha, off-diagonal beta; alpha holds at least one
+// value, beta at most alpha.size() - 1 of them are read)
+double lanczos_ritz_max(const std::vector<double> &alpha, const std::vector<double> &beta) {
     // largest eigenvalue of the tridiagonal matrix by bisection on the Sturm count
     const int kdim = (int)alpha.size();
     double lo = alpha[0], hi = alpha[0];
@@ -548,6 +523,61 @@ double amg_hierarchy::find_eig(const saena_matrix &A) {
         if (count_below(mid) >= kdim) hi = mid; else lo = mid;
     }
     return 1.0001 * 0.5 * (lo + hi);
+}
+
+// largest eigenvalue of D^-1 A: 20 Lanczos steps on D^-1/2 A D^-1/2 (lamlan_saena.h:38-59,
+// lambda_lanczos.hpp:95 max_iteration = 20), result x 1.0001.  The reference starts from a random
+// vector (its estimate "fluctuates in each execution"); here the start vector is a fixed LCG sequence.
+double amg_hierarchy::find_eig(const saena_matrix &A) {
+    if (A.comm->nranks != 1) throw std::runtime_error("find_eig: multi-rank setup is not implemented in this round");
+    const index_t n = A.M;
+    const Csr C = csr_of(A.L, n);
+    std::vector<double> isd((size_t)n);
+    for (index_t i = 0; i < n; ++i) isd[i] = std::sqrt(std::fabs(A.inv_diag[i]));
+    auto matvec = [&](const std::vector<double> &x, std::vector<double> &y) {
+        parallel_rows(n, &C.ptr, [&](int, index_t lo, index_t hi) {
+            for (index_t i = lo; i < hi; ++i) {
+                double s_ = 0;
+                for (nnz_t k = C.ptr[i]; k < C.ptr[i + 1]; ++k) s_ += C.val[k] * isd[C.col[k]] * x[C.col[k]];
+                y[i] = s_ * isd[i];
+            }
+        });
+    };
+    const int m = std::min<index_t>(20, n);
+    std::vector<double> v((size_t)n), vprev((size_t)n, 0.0), w((size_t)n), alpha, beta;
+    lanczos_start_vector(n, v.data());
+    double b = 0;
+    for (int k = 0; k < m; ++k) {
+        matvec(v, w);
+        double a = 0;
+        for (index_t i = 0; i < n; ++i) a += w[i] * v[i];
+        alpha.push_back(a);
+        for (index_t i = 0; i < n; ++i) w[i] -= a * v[i] + b * vprev[i];
+        b = 0;
+        for (index_t i = 0; i < n; ++i) b += w[i] * w[i];
+        b = std::sqrt(b);
+        if (k + 1 < m) beta.push_back(b);
+        if (b < 1e-300) break;
+        vprev = v;
+        for (index_t i = 0; i < n; ++i) v[i] = w[i] / b;
+    }
+    return lanczos_ritz_max(alpha, beta);
+}
+
+// eig_max of a one-rank level: the device estimate where the switch is on, a hook is installed and it accepts; find_eig otherwise
+double amg_hierarchy::level_eig(const saena_matrix &A, bool *on_device) const {
+    *on_device = false;
+    const char *e = std::getenv("SAENA_DEVICE_EIG");
+    if ((device_eig || (e && std::atoi(e) == 1)) && g_eig_hook && A.comm->nranks == 1 && A.M > 0 && A.inv_diag.size() == (size_t)A.M) {
+        std::vector<nnz_t> ptr((size_t)A.M + 1, 0);
+        for (index_t i = 0; i < A.M; ++i) ptr[(size_t)i + 1] = ptr[(size_t)i] + A.L.nnzPerRow_local[(size_t)i];
+        double eig = 0.0;
+        if (g_eig_hook(A.M, ptr.data(), A.L.col_local.data(), A.L.val_local.data(), A.inv_diag.data(), 20, &eig) == 0) {
+            *on_device = true;
+            return eig;
+        }
+    }
+    return find_eig(A);
 }
 
 // filter (setup2:852-916): entries with |v| <= THRE are lumped into the diagonal (one-rank CSR form)
@@ -754,13 +784,21 @@ int amg_hierarchy::setup(saena_matrix *A, const amg_options &o) {
     levels.clear();
     levels.resize((size_t)max_level + 1);
     levels[0].A = A;
-    if (opts.smoother == "chebyshev" && std::fabs(A->eig_max_of_invdiagXA) < SAENA_ALMOST_ZERO)   // :201-204
-        A->eig_max_of_invdiagXA = find_eig(*A);
+    bool dev = false;
+    if (opts.smoother == "chebyshev" && std::fabs(A->eig_max_of_invdiagXA) < SAENA_ALMOST_ZERO) {   // :201-204
+        PhaseTimer pt(0);
+        A->eig_max_of_invdiagXA = level_eig(*A, &dev);
+        pt.lap(dev ? "find_eig (device)" : "find_eig");
+    }
     for (int i = 0; i < max_level; ++i) {                               // :239
         const int res = coarsen(i);
         if (res == 1) max_level = i + 1;                                // :287-289 this will be the last level
         levels[i + 1].A = levels[i].Ac_store.get();
-        if (opts.smoother == "chebyshev") levels[i + 1].A->eig_max_of_invdiagXA = find_eig(*levels[i + 1].A);   // :315
+        if (opts.smoother == "chebyshev") {                             // :315
+            PhaseTimer pt(i + 1);
+            levels[i + 1].A->eig_max_of_invdiagXA = level_eig(*levels[i + 1].A, &dev);
+            pt.lap(dev ? "find_eig (device)" : "find_eig");
+        }
     }
     levels.resize((size_t)max_level + 1);
     return 0;
@@ -782,8 +820,9 @@ int amg_hierarchy::update(saena_matrix *A_new, int mode, update_undo *undo) {
     // (a value the caller set on A_new is kept, as setup keeps it; an unset one is computed into a local first)
     const bool eig0_missing = cheby && std::fabs(A_new->eig_max_of_invdiagXA) < SAENA_ALMOST_ZERO;
     PhaseTimer pt0(0, "update");
-    const double eig0 = eig0_missing ? find_eig(*A_new) : A_new->eig_max_of_invdiagXA;
-    if (eig0_missing) pt0.lap("find_eig");
+    bool dev = false;
+    const double eig0 = eig0_missing ? level_eig(*A_new, &dev) : A_new->eig_max_of_invdiagXA;
+    if (eig0_missing) pt0.lap(dev ? "find_eig (device)" : "find_eig");
     std::vector<std::unique_ptr<saena_matrix>> fresh;
     if (mode == 2) {
         // the schedule the setup walked, from its start: one step per coarsened level
@@ -797,7 +836,7 @@ int amg_hierarchy::update(saena_matrix *A_new, int mode, update_undo *undo) {
             pt.lap("CSR views of R, A, P");
             fresh.push_back(galerkin_coarse(*A_new->comm, Rc, Ac_, Pc, opts, it, thre, pt));
             pt.lap("layout of Ac");
-            if (cheby) { fresh.back()->eig_max_of_invdiagXA = find_eig(*fresh.back()); pt.lap("find_eig"); }
+            if (cheby) { fresh.back()->eig_max_of_invdiagXA = level_eig(*fresh.back(), &dev); pt.lap(dev ? "find_eig (device)" : "find_eig"); }
             Af = fresh.back().get();
         }
     }

@@ -28,6 +28,18 @@ extern spgemm_hook_fn g_spgemm_hook;
 // Every right operand of the setup is an assembled operator, a smoothed prolongator whose rows were sorted and merged, or
 // rows fetched from one of those; see gpu_spgemm in sgpu_spgemm.hip.  A's rows may come in any order, duplicates included.
 
+// Optional device estimate of eig_max (find_eig below) for a one-rank operator: CSR in (64-bit row pointers, columns ascending in
+// every row), inv_diag[n], the number of Lanczos steps; *eig_max out.  libsaena_amd.so installs it at sgpu_init next to the product
+// hook (sgpu_lanczos.hip.inc: a temporary operator from sgpu_op_create, sgpu_op_eig_max, destroy); 0 on success, non-zero to decline
+// (no memory, a context of several ranks): the host find_eig then runs.  It is asked only where amg_hierarchy::device_eig or
+// SAENA_DEVICE_EIG=1 says so: with the switch off nothing changes by a bit whether or not it is installed.  nullptr in libsaena_host.so.
+typedef int (*eig_hook_fn)(int n, const long *ptr, const int *col, const double *val, const double *inv_diag, int steps, double *eig_max);
+extern eig_hook_fn g_eig_hook;
+// The two ends of find_eig that do not depend on who runs the recurrence (the host loops, or the device through the hook): the LCG
+// start vector over the row index, normalised, and 1.0001 x the largest eigenvalue of the tridiagonal matrix (Sturm bisection).
+void lanczos_start_vector(index_t n, double *v);
+double lanczos_ritz_max(const std::vector<double> &alpha, const std::vector<double> &beta);
+
 // Which path served the rows of a product: counted by the host kernel and by the host side of the device driver (no
 // kernel takes part), for the tests that must know which accumulator they exercised.  g_spgemm_last is the last product,
 // g_spgemm_total the sum over the products since spgemm_stats_reset().  The setup multiplies from one thread at a time.
@@ -194,12 +206,17 @@ public:
     static std::vector<cooEntry> matmat(const saena_matrix &A, const saena_matrix &B);
     // find_eig (saena_object.cpp:572-592, lamlan_saena.h): largest eigenvalue of D^-1 A by 20 Lanczos steps, x 1.0001
     static double find_eig(const saena_matrix &A);
+    // Opt-in: setup() and update() take eig_max of their one-rank levels from g_eig_hook (the same recurrence on the device; equal to
+    // find_eig's value within 1e-12 relative, not bit for bit: the dots are summed in another order).  Also on with SAENA_DEVICE_EIG=1,
+    // read at every call.  Without a hook, or when it declines, find_eig runs.  A value the caller set on a matrix is kept either way.
+    bool device_eig = false;
 
 private:
     double filter_thre_cur = 0;
     int    filter_it = 0;
     int  coarsen(int l);                          // saena_object::coarsen (saena_object.cpp:409-452)
     void filter(std::vector<cooEntry> &v, index_t sz, index_t ofst);   // setup2:852-916
+    double level_eig(const saena_matrix &A, bool *on_device) const;   // the hook where the switch is on and it accepts, else find_eig
 };
 
 } // namespace saena_host

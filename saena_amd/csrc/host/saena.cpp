@@ -114,6 +114,11 @@ void matrix::set_eig(const std::string &fname) {          // saena.cpp:124-135: 
     const double e = std::stod(s.substr(p + 5, q - p - 5));
     if (e != 0.0) m_pImpl->set_eig(e);
 }
+double matrix::estimate_eig(int steps) {
+    double e = 0.0;
+    gchk(sgpu_op_eig_max(device_op(), steps, &e), "saena::matrix::estimate_eig");
+    return e;
+}
 void matrix::set_remove_boundary(bool b) { m_pImpl->remove_boundary = b; }
 void matrix::set_partition_buckets(int n) { m_pImpl->partition_buckets = n < 0 ? 0 : n; }
 int matrix::add_duplicates(bool add) { add_dup = add; m_pImpl->add_duplicates = add; return 0; }
@@ -241,6 +246,7 @@ void options::set_solve_params(int max_iter, double tol, std::string sm, int pre
 amg::amg() {}
 amg::~amg() { destroy(); }
 void amg::set_dynamic_levels(const bool &dl) { dynamic_levels_ = dl; }
+void amg::set_device_eig(bool on) { device_eig_ = on; if (H_) H_->device_eig = on; }
 int amg::set_verbose(bool v) { verbose = v; return 0; }
 int amg::set_multigrid_max_level(int m) { max_level_override_ = m; return 0; }
 int amg::get_num_levels() const { return H_ ? H_->max_level + 1 : 0; }
@@ -270,6 +276,7 @@ int amg::set_matrix(saena::matrix *A, saena::options *opts) {
     o.switch_to_dense = opts->get_switch_dense() || switch_to_dense_; o.dense_thre = opts->get_dense_thre(); o.dense_sz_thre = opts->get_dense_sz_thre();
     if (dense_thre_override_ > 0) o.dense_thre = dense_thre_override_;
     H_ = new saena_host::amg_hierarchy();
+    H_->device_eig = device_eig_;
     H_->setup_distributed(A->get_internal_matrix(), o);      // one rank: plain setup; more: every rank builds its rows of every level
     const int n = H_->max_level + 1;
     const bool multi = !H_->dist.empty();

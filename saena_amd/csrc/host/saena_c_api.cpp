@@ -309,6 +309,12 @@ int saena_amg_update(saena_amg_h *S, saena_matrix_h *A_new, int mode) {
     return 0;
 }
 
+int saena_amg_set_device_eig(saena_amg_h *S, int on) {
+    if (!S) { h_err = "saena_amg_set_device_eig: null argument"; return -1; }
+    S->H.device_eig = on != 0;
+    return 0;
+}
+
 int saena_amg_num_levels(saena_amg_h *S) { return S->set ? S->H.max_level + 1 : 0; }
 
 int saena_amg_level_split(saena_amg_h *S, int l, index_t *split_out) {
@@ -358,6 +364,7 @@ int saena_amg_level_desc(saena_amg_h *S, int l, int which, sgpu_op_desc *out) {
 #ifndef SAENA_WITH_GPU
 static int no_gpu() { h_err = "this entry point needs libsaena_amd.so (the GPU library); there is no CPU fallback"; return -1; }
 void saena_amg_free(saena_amg_h *S) { delete S; }
+int saena_matrix_estimate_eig(saena_matrix_h *, int, double *) { return no_gpu(); }
 int saena_amg_to_device(saena_amg_h *) { return no_gpu(); }
 sgpu_amg *saena_amg_device_handle(saena_amg_h *) { no_gpu(); return nullptr; }
 sgpu_op *saena_amg_device_op(saena_amg_h *, int, int) { no_gpu(); return nullptr; }
@@ -374,6 +381,18 @@ static void drop_device(saena_amg_h *S) {
     S->deig.clear();
 }
 void saena_amg_free(saena_amg_h *S) { if (S) { drop_device(S); delete S; } }
+
+// sgpu_op_eig_max on a device operator made for the call from the matrix's layout (the heuristic plan: no autotune, nothing kept)
+int saena_matrix_estimate_eig(saena_matrix_h *A, int steps, double *eig_max) {
+    if (!A || !eig_max) { h_err = "saena_matrix_estimate_eig: null argument"; return -1; }
+    sgpu_op_desc d; sgpu_op *o = nullptr;
+    if (saena_matrix_get_desc(A, &d)) return -1;
+    d.halo_fp32 = 0;
+    if (gchk(sgpu_op_create(&d, &o))) return -2;
+    const int s = gchk(sgpu_op_eig_max(o, steps, eig_max));
+    sgpu_op_destroy(o);
+    return s;
+}
 
 // The device operator of A on level l, as to_device and update make it: the level's layout, its halo wire type, the plan cache
 // or autotune, the dense form where the options ask for it.

@@ -11,6 +11,7 @@
 #include "kernels_block.hip.h"
 #include "kernels_gmres.hip.h"
 #include "kernels_eig.hip.h"
+#include "kernels_lanczos.hip.h"
 #include "dispatch.h"
 #include "devmem.h"
 #include "forms.h"
@@ -43,6 +44,7 @@
 #include <vector>
 
 extern "C" void sgpu_install_spgemm_hook(int on);
+extern "C" void sgpu_install_eig_hook(int on);
 
 using devmem::DevArr;
 using devmem::PinArr;
@@ -2155,6 +2157,7 @@ int sgpu_init(int device_id, int rank, int nranks, const void *uid) {
     }
     g.live = true;
     sgpu_install_spgemm_hook(1);         // the AMG setup's Galerkin products run on this device from now on (sgpu_spgemm.hip)
+    sgpu_install_eig_hook(1);            // and, where the caller opts in, its eig_max estimates (sgpu_lanczos.hip.inc)
     if (g.comm && !std::getenv("SAENA_NO_CHAIN_CALIBRATION")) {
         const int s = calibrate_chain();
         if (s != SGPU_OK) { sgpu_finalize(); return s; }      // streams, buffers and the communicator go with the failed context (the error text stays)
@@ -2175,6 +2178,7 @@ int sgpu_debug_init_host_transport(int device_id, int rank, int nranks, sgpu_hos
 int sgpu_finalize(void) {
     if (!g.live) return SGPU_OK;
     sgpu_install_spgemm_hook(0);
+    sgpu_install_eig_hook(0);
     hipDeviceSynchronize();
     if (g.comm) { ncclCommDestroy(g.comm); g.comm = nullptr; }
     if (g.tk0) { hipEventDestroy(g.tk0); hipEventDestroy(g.tk1); g.tk0 = g.tk1 = nullptr; }
@@ -3858,6 +3862,7 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 #include "sgpu_block.hip.inc"
 #include "sgpu_gmres.hip.inc"
 #include "sgpu_eig.hip.inc"
+#include "sgpu_lanczos.hip.inc"
 
 // sgpu_amg_set_operator (include/saena_gpu.h).  After the block helpers: the block work space of a hierarchy keeps a Chebyshev
 // direction per operator and K, which the incoming operator does not have yet.

@@ -44,6 +44,7 @@ HOST_SYMBOLS = {
     "saena_matrix_set_partition_buckets": (C.c_int, [_VP, C.c_int]),
     "saena_matrix_add_duplicates": (C.c_int, [_VP, C.c_int]),
     "saena_matrix_set_eig": (C.c_int, [_VP, C.c_double]),
+    "saena_matrix_estimate_eig": (C.c_int, [_VP, C.c_int, _PD]),
     "saena_matrix_assemble": (C.c_int, [_VP]),
     "saena_matrix_assemble_with_split": (C.c_int, [_VP, _PI]),
     "saena_matrix_get_num_rows": (C.c_int, [_VP]),
@@ -90,6 +91,7 @@ HOST_SYMBOLS.update({
     "saena_amg_free": (None, [_VP]),
     "saena_amg_set_matrix": (C.c_int, [_VP, _VP, C.POINTER(OptionsC)]),
     "saena_amg_update": (C.c_int, [_VP, _VP, C.c_int]),
+    "saena_amg_set_device_eig": (C.c_int, [_VP, C.c_int]),
     "saena_amg_num_levels": (C.c_int, [_VP]),
     "saena_amg_level_info": (C.c_int, [_VP, C.c_int, _PI, C.POINTER(C.c_long), C.POINTER(C.c_long), _PD]),
     "saena_amg_level_aggregates": (C.c_int, [_VP, C.c_int, _PI, _PI]),
@@ -299,6 +301,17 @@ class Matrix:
         _check(self.L, self.L.saena_band_matrix(self.h, M, bw))
         return self
 
+    def set_eig(self, eig):
+        """saena::matrix::set_eig(double): the Chebyshev eig_max of this matrix, kept by set_matrix and the updates as it is"""
+        _check(self.L, self.L.saena_matrix_set_eig(self.h, float(eig)))
+        return self
+
+    def estimate_eig(self, steps=20):
+        """the value set_eig takes, estimated on the device (saena_matrix_estimate_eig; GPU library, one rank); nothing is stored"""
+        v = C.c_double()
+        _check(self.L, self.L.saena_matrix_estimate_eig(self.h, int(steps), C.byref(v)))
+        return v.value
+
     def assemble(self, split=None):
         if split is None:
             _check(self.L, self.L.saena_matrix_assemble(self.h))
@@ -489,11 +502,19 @@ OPTIONS001 = dict(solver_max_iter=50, relative_tol=1e-8, smoother="jacobi", preS
 class AmgSolver:
     """saena::amg mirror (reference include/saena.hpp:195-265): set_matrix on the host, solve on the GPU."""
 
-    def __init__(self, A: Matrix, opts: OptionsC):
+    def __init__(self, A: Matrix, opts: OptionsC, device_eig=None):
+        """device_eig: True lets the one-rank setup and the updates take eig_max from the device estimate (saena_amg_set_device_eig);
+        None leaves the library's default (off, unless SAENA_DEVICE_EIG=1)"""
         self.A, self.L = A, A.L
         self.h = self.L.saena_amg_new()
+        if device_eig is not None:
+            self.set_device_eig(device_eig)
         _check(self.L, self.L.saena_amg_set_matrix(self.h, A.h, C.byref(opts)))
         self.opts = opts
+
+    def set_device_eig(self, on):
+        _check(self.L, self.L.saena_amg_set_device_eig(self.h, 1 if on else 0))
+        return self
 
     def update(self, A_new: Matrix, mode):
         """saena::amg::update1 / update2 (saena_amg_update): A_new, of the same size, becomes level 0 of the built hierarchy.  mode 1:
