@@ -249,6 +249,13 @@ public:
     // estimate instead of the host Lanczos loop, on one rank -- the same recurrence, equal within 1e-12 relative, not bit for bit.
     // Also on with SAENA_DEVICE_EIG=1.  Where the device declines, the host loop runs; a value set with matrix::set_eig is kept.
     void set_device_eig(bool on);
+    // NOT in the reference, before set_matrix: how the coarsest level is solved (sgpu_amg_params.coarse_solver).  "direct" (the
+    // default): the dense inverse; "cg": solve_coarsest_CG; "device_cg": the same CG, and where the coarsest level has more than
+    // 1 024 rows (set_multigrid_max_level cut the hierarchy off, coarsening stalled) the device-resident CG instead of the host-driven
+    // loop the other two fall back to there: the V-cycle stays one captured graph and solve_pCG_block, solve_pFGMRES and eigs take
+    // the hierarchy.  Any other name throws.  SAENA_COARSE_SOLVER=direct|cg|device_cg in the environment, read by set_matrix,
+    // overrides it for drivers compiled unchanged.
+    void set_coarse_solver(const std::string &name);
     int update1(saena::matrix *A_new);
     int update2(saena::matrix *A_new);
     int set_rhs(saena::vector &rhs);                          // note: this function copies the rhs
@@ -333,6 +340,7 @@ private:
     float dense_thre_override_ = 0;
     int max_level_override_ = -1;
     bool device_eig_ = false;
+    int coarse_solver_ = 1;
     void drop_device();
     int update(saena::matrix *A_new, int mode);
     // which: 0 solve, 1 solve_pCG, 2 solve_CG, 3 solve_smoother, 4 solve_pFGMRES (the only one that reads restart / precondition)

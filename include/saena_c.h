@@ -177,6 +177,13 @@ int   saena_amg_update(saena_amg_h *S, saena_matrix_h *A_new, int mode);
  * exists (libsaena_host.so, no sgpu_init), over several ranks, or when the device declines (memory), the host loop runs as before.  A
  * value set with saena_matrix_set_eig is kept either way. */
 int   saena_amg_set_device_eig(saena_amg_h *S, int on);
+/* Before saena_amg_to_device: how the device hierarchy solves its coarsest level (sgpu_amg_params.coarse_solver, include/saena_gpu.h).
+ * name: "direct" (the default: dense inverse), "cg" (solve_coarsest_CG) or "device_cg" (that CG, and on a coarsest level of more than
+ * 1 024 rows the device-resident CG instead of the host-driven loop the other two run there: the V-cycle stays a captured graph and
+ * the block, FGMRES and LOBPCG solves take the hierarchy); any other name is refused (-1).  SAENA_COARSE_SOLVER=direct|cg|device_cg in
+ * the environment, read by saena_amg_to_device, overrides it for drivers compiled unchanged.  Exported like every other symbol
+ * (host/exports.map hides the operator new wrappers only). */
+int   saena_amg_set_coarse_solver(saena_amg_h *S, const char *name);
 int   saena_amg_num_levels(saena_amg_h *S);                               /* max_level + 1 */
 /* coarse id of every fine row of `level` (the reference's `aggregate` after aggregate_index_update, src/saena_object_setup1.cpp:
  * 2103-2260); one-rank setups keep it, for the pins of the setup (tests/test_sa_pins.py).  out: rows of that level */

@@ -239,7 +239,16 @@ typedef struct {
     value_t jacobi_omega;                 /* 0 => float(2.0/3) */
     int     coarse_solver;                /* 1 (default) direct: dense inverse factored once on the host, like the reference's
                                              default direct_solver "SuperLU" (saena_object.h:165, saena_object_solve.cpp:793-958);
-                                             0 CG (solve_coarsest_CG, saena_object_solve.cpp:14-114) */
+                                             0 CG (solve_coarsest_CG, saena_object_solve.cpp:14-114);
+                                             2 device CG: value 0's LDS-resident CG, the same bits, on a coarsest level of at most
+                                             1 024 rows; on a larger one that lives whole on one rank, the same recurrence with
+                                             its vectors in device memory and its scalars on the device -- a fixed sequence of
+                                             2 + 3 (CG_coarsest_max_iter - 1) launches without a host round trip, so the V-cycle
+                                             is captured and sgpu_vcycle_block, sgpu_solve_pCG_block, sgpu_solve_FGMRES and
+                                             sgpu_eigs_LOBPCG take the hierarchy.  Under 0 and 1 such a level is solved by a
+                                             host-driven CG loop (no graph capture; those four entry points return SGPU_ERR_ARG).
+                                             A coarsest level that is row-partitioned over the ranks takes the distributed
+                                             host-driven CG under every value */
     int     CG_coarsest_max_iter;         /* 150   saena_object.h:156 */
     value_t CG_coarsest_tol;              /* 1e-12 saena_object.h:155 */
     int     solver_max_iter;              /* saena::options */
@@ -274,7 +283,8 @@ int sgpu_amg_set_solve_params(sgpu_amg *h, int solver_max_iter, double solver_to
  * level, eig_max > 0 under Chebyshev on a non-coarsest level, a context of one rank: anything else is SGPU_ERR_ARG; both streams are
  * waited for; EVERY captured graph of the hierarchy is dropped (the scalar cache, the multi-rank tail, the block caches, FGMRES's and
  * LOBPCG's: they hold raw pointers into the outgoing operator), so the next call of each captures again; on the coarsest level with
- * coarse_solver 1 the dense inverse is recomputed (a singular operator is SGPU_ERR_ARG); the Chebyshev direction of A_new is
+ * coarse_solver 1 the dense inverse is recomputed (a singular operator is SGPU_ERR_ARG; under coarse_solver 2 no inverse exists and
+ * the device CG's work space is kept); the Chebyshev direction of A_new is
  * allocated, for the scalar V-cycle and for every block work space the hierarchy already has (a capture must not allocate); then
  * A[level] and eig_max[level] are swapped.  After any error the hierarchy is as it was: the old operator, the old inverse.  The work
  * vectors of the hierarchy and the block, FGMRES and LOBPCG work spaces stay (the sizes are equal); only their graphs go.  The old

@@ -150,6 +150,12 @@ int sgpu_debug_time_eig(sgpu_amg *h, int kind, int ns, const value_t *X, const v
  * discards the graph -- for the entry points that must refuse to run inside a capture.  Nothing is launched in between by the tests. */
 int sgpu_debug_capture(int begin);
 
+/* measurement scripts (tests/perf_coarse_cg.py): ms per launch of the device coarsest CG's product kernel (coarse_solver = 2, a
+ * coarsest level past 1 024 rows) on the hierarchy's coarsest operator, y = A x with the partial sums of x . y, `reps` back-to-back
+ * launches between two events after one warm-up launch: what sgpu_time_kernel(op, 0, ...) measures for the operator's tuned form.
+ * x, y: device vectors of the coarsest level's rows.  SGPU_ERR_STATE where the hierarchy runs no device CG on this rank. */
+int sgpu_debug_dcg_matvec_time(sgpu_amg *h, const value_t *x, value_t *y, int reps, float *ms_per_launch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@
 //     print_time (aux_functions.cpp:72-128), saena_free / saena_aligned_alloc (aux_functions.h:299-312), read_from_file_rhs
 //     (aux_functions.cpp:347-497: the rhs reader of experiments/profile_file.cpp), omp_get_wtime when OpenMP is off.
 // saena::amg::update1 / update2 come with saena.hpp: one rank works, more ranks throw ("one rank").
+// saena::amg::set_coarse_solver comes with it too ("direct", "cg", "device_cg"; SAENA_COARSE_SOLVER for a driver compiled unchanged).
 // Out of the path's scope and therefore absent: GMRES, update3, the Nektar++ set_matrix, PETSc (solve_petsc compiles and
 // reports that it is not available).
 #pragma once

@@ -82,6 +82,7 @@ SYMBOLS = {
     "sgpu_prolong_correct": (C.c_int, [_VP, _VP, _VP]),
     "sgpu_op_eig_max": (C.c_int, [_VP, C.c_int, _PD]),
     "sgpu_debug_capture": (C.c_int, [C.c_int]),
+    "sgpu_debug_dcg_matvec_time": (C.c_int, [_VP, _VP, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_pack": (C.c_int, [_VP, _VP, _PD]),
     "sgpu_debug_gather_probe": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_block_plan": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_long)]),
@@ -569,6 +570,11 @@ class Operator:
             pass
 
 
+def coarse_solver_code(name):
+    """sgpu_amg_params.coarse_solver of a name: "direct" 1, "device_cg" 2, anything else ("CG", "cg") 0"""
+    return {"direct": 1, "device_cg": 2}.get(name, 0)
+
+
 class Amg:
     """sgpu_amg over Operators A[l], P[l], R[l]."""
 
@@ -582,7 +588,7 @@ class Amg:
         prm.smoother = 0 if smoother == "jacobi" else 1
         prm.solver_max_iter, prm.solver_tol = max_iter, tol
         prm.use_graph = 1 if use_graph else 0
-        prm.coarse_solver = 1 if coarse_solver == "direct" else 0
+        prm.coarse_solver = coarse_solver_code(coarse_solver)
         prm.CG_coarsest_max_iter, prm.CG_coarsest_tol = int(cg_max_iter), float(cg_tol)
         HA = (_VP * n)(*[a.h for a in A])
         HP = (_VP * n)(*([p.h for p in P] + [None] * (n - len(P))))
@@ -639,6 +645,12 @@ class Amg:
         """ms per V-cycle, `reps` of them back to back inside the library; u / rhs: DeviceVectors (scalar) or BlockVectors"""
         ms = C.c_float()
         check(lib().sgpu_debug_time_vcycle(self.h, u.ptr, rhs.ptr, getattr(u, "K", 0), reps, C.byref(ms)))
+        return ms.value
+
+    def time_dcg_matvec(self, x, y, reps):
+        """ms per launch of the device coarsest CG's product kernel on the coarsest operator (sgpu_debug_dcg_matvec_time)"""
+        ms = C.c_float()
+        check(lib().sgpu_debug_dcg_matvec_time(self.h, x.ptr, y.ptr, int(reps), C.byref(ms)))
         return ms.value
 
     def solve_pCG_block(self, U, RHS, cap=256):

@@ -155,6 +155,15 @@ Csr transpose(const Csr &A) {
 spgemm_hook_fn g_spgemm_hook = nullptr;
 // eig_max of a one-rank level on the GPU, where the caller opted in (amg_setup.h; sgpu_lanczos.hip.inc installs this)
 eig_hook_fn g_eig_hook = nullptr;
+int coarse_solver_code(const char *name) {
+    if (!name) return -1;
+    const std::string s(name);
+    return s == "direct" ? 1 : s == "cg" ? 0 : s == "device_cg" ? 2 : -1;
+}
+int coarse_solver_choice(int set_value) {
+    const int env = coarse_solver_code(std::getenv("SAENA_COARSE_SOLVER"));
+    return env >= 0 ? env : set_value;
+}
 // what the last product did, and every product since spgemm_stats_reset() (amg_setup.h)
 spgemm_stats g_spgemm_last, g_spgemm_total;
 void spgemm_stats_reset() { g_spgemm_last = spgemm_stats(); g_spgemm_total = spgemm_stats(); }

@@ -40,6 +40,12 @@ extern eig_hook_fn g_eig_hook;
 void lanczos_start_vector(index_t n, double *v);
 double lanczos_ritz_max(const std::vector<double> &alpha, const std::vector<double> &beta);
 
+// sgpu_amg_params.coarse_solver by name: "direct" 1, "cg" 0, "device_cg" 2; -1 for anything else (a null pointer included).
+// coarse_solver_choice: what a to_device passes to sgpu_amg_create -- SAENA_COARSE_SOLVER where the environment names a solver (a
+// driver compiled unchanged), else the value its setter left.
+int coarse_solver_code(const char *name);
+int coarse_solver_choice(int set_value);
+
 // Which path served the rows of a product: counted by the host kernel and by the host side of the device driver (no
 // kernel takes part), for the tests that must know which accumulator they exercised.  g_spgemm_last is the last product,
 // g_spgemm_total the sum over the products since spgemm_stats_reset().  The setup multiplies from one thread at a time.

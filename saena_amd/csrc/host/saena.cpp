@@ -247,6 +247,11 @@ amg::amg() {}
 amg::~amg() { destroy(); }
 void amg::set_dynamic_levels(const bool &dl) { dynamic_levels_ = dl; }
 void amg::set_device_eig(bool on) { device_eig_ = on; if (H_) H_->device_eig = on; }
+void amg::set_coarse_solver(const std::string &name) {
+    const int c = saena_host::coarse_solver_code(name.c_str());
+    if (c < 0) throw std::runtime_error("saena::amg::set_coarse_solver: \"" + name + "\" is none of direct, cg, device_cg");
+    coarse_solver_ = c;
+}
 int amg::set_verbose(bool v) { verbose = v; return 0; }
 int amg::set_multigrid_max_level(int m) { max_level_override_ = m; return 0; }
 int amg::get_num_levels() const { return H_ ? H_->max_level + 1 : 0; }
@@ -312,6 +317,7 @@ int amg::set_matrix(saena::matrix *A, saena::options *opts) {
     sgpu_amg_default_params(&p);
     p.preSmooth = o.preSmooth; p.postSmooth = o.postSmooth; p.smoother = o.smoother == "jacobi" ? 0 : 1;
     p.solver_max_iter = o.solver_max_iter; p.solver_tol = o.relative_tol;
+    p.coarse_solver = saena_host::coarse_solver_choice(coarse_solver_);
     gchk(sgpu_amg_create(n, dA_.data(), dP_.data(), dR_.data(), eig.data(), &p, &damg_), "sgpu_amg_create");
     if (verbose && A->get_comm().rank() == 0) {
         printf("_____________________________\n\nnumber of levels = << %d >> (the finest level is 0)\n", n - 1);

@@ -20,6 +20,7 @@ struct saena_transfer_h { transfer_matrix T; };
 struct saena_amg_h {
     amg_hierarchy H;
     bool set = false;
+    int coarse_solver = 1;                    // saena_amg_set_coarse_solver: what to_device passes to sgpu_amg_create
     // device side (libsaena_amd.so only)
     std::vector<sgpu_op *> dA, dP, dR;
     std::vector<double> deig;                 // eig_max of every dA, as the device hierarchy holds it
@@ -315,6 +316,14 @@ int saena_amg_set_device_eig(saena_amg_h *S, int on) {
     return 0;
 }
 
+int saena_amg_set_coarse_solver(saena_amg_h *S, const char *name) {
+    if (!S || !name) { h_err = "saena_amg_set_coarse_solver: null argument"; return -1; }
+    const int c = coarse_solver_code(name);
+    if (c < 0) { h_err = std::string("saena_amg_set_coarse_solver: \"") + name + "\" is none of direct, cg, device_cg"; return -1; }
+    S->coarse_solver = c;
+    return 0;
+}
+
 int saena_amg_num_levels(saena_amg_h *S) { return S->set ? S->H.max_level + 1 : 0; }
 
 int saena_amg_level_split(saena_amg_h *S, int l, index_t *split_out) {
@@ -466,6 +475,7 @@ int saena_amg_to_device(saena_amg_h *S) {
     const amg_options &o = S->H.opts;
     p.preSmooth = o.preSmooth; p.postSmooth = o.postSmooth; p.smoother = o.smoother == "jacobi" ? 0 : 1;
     p.solver_max_iter = o.solver_max_iter; p.solver_tol = o.relative_tol;
+    p.coarse_solver = coarse_solver_choice(S->coarse_solver);
     return gchk(sgpu_amg_create(n, S->dA.data(), S->dP.data(), S->dR.data(), S->deig.data(), &p, &S->damg));
 }
 

@@ -336,7 +336,10 @@ int coarse_solve_block(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, b
     double *crhs = B.cm, *cu = B.cm + (size_t)n * K;
     CHK(block_unpack(rhs, crhs, (size_t)n, K));
     if (u_zero) CHK(sgpu_vec_fill(cu, 0.0, (size_t)n * K)); else CHK(block_unpack(u, cu, (size_t)n, K));
-    for (int j = 0; j < K; ++j) CHK(coarse_cg_single(h, A, cu + (size_t)j * n, crhs + (size_t)j * n, nullptr));
+    // the device CG past CG_MAXN rows (coarse_solver == 2): the scalar solver again, so a column has the bits of its scalar solve
+    const bool dev = h->coarse_device_cg && n > sk::CG_MAXN;
+    for (int j = 0; j < K; ++j) CHK(dev ? coarse_cg_device(h, A, cu + (size_t)j * n, crhs + (size_t)j * n, nullptr)
+                                        : coarse_cg_single(h, A, cu + (size_t)j * n, crhs + (size_t)j * n, nullptr));
     return block_pack(cu, u, (size_t)n, K);
 }
 

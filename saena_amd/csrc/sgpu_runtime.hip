@@ -12,6 +12,7 @@
 #include "kernels_gmres.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_lanczos.hip.h"
+#include "kernels_coarse_cg.hip.h"
 #include "dispatch.h"
 #include "devmem.h"
 #include "forms.h"
@@ -3247,6 +3248,9 @@ struct sgpu_amg {
     double *tail_out = nullptr;        // which of u[tail_level] / alt[tail_level] holds the sub-V-cycle's result
     uint64_t graph_gen = 0;            // g_plan_generation the graphs were captured under
     bool coarse_host_driven = false;   // coarsest level too large for the LDS-resident solvers: host-driven CG, no graph capture
+    bool coarse_device_cg = false;     // ... and coarse_solver == 2: the device-resident CG instead (sgpu_coarse_cg.hip.inc), capturable
+    DevArr<double> dcg;                // its work space on a rank whose coarsest rows exceed CG_MAXN: res, dir, mt, partial sums, scalars
+    int dcg_rows = 0;
     std::unique_ptr<AmgBlock> blk[3];  // K = 2, 4, 8
     std::unique_ptr<AmgGmres> gm;      // sgpu_solve_FGMRES
     std::unique_ptr<AmgEig> eigs[3];   // sgpu_eigs_LOBPCG, K = 2, 4, 8
@@ -3311,6 +3315,9 @@ int coarse_cg_dist(sgpu_amg *h, sgpu_op *A, double *u, const double *rhs, int *i
     return SGPU_OK;
 }
 
+int ensure_dcg(sgpu_amg *h, int M);                                                         // sgpu_coarse_cg.hip.inc
+int coarse_cg_device(sgpu_amg *h, sgpu_op *A, double *u, const double *rhs, int *iters);
+
 int coarse_solve(sgpu_amg *h, double *u, const double *rhs, int *iters) {
     sgpu_op *A = h->A[h->nlevels - 1];
     if (h->Ainv) {
@@ -3321,6 +3328,7 @@ int coarse_solve(sgpu_amg *h, double *u, const double *rhs, int *iters) {
     }
     if (h->coarse_local && !h->coarse_host_driven) {
         if (A->M == 0) { if (iters) *iters = 0; return SGPU_OK; }      // this rank holds no coarsest rows
+        if (h->coarse_device_cg && A->M > sk::CG_MAXN) return coarse_cg_device(h, A, u, rhs, iters);
         return coarse_cg_single(h, A, u, rhs, iters);
     }
     // row-partitioned coarsest operator, or one with more than CG_MAXN rows (coarsening stalled, max_level cut-off):
@@ -3533,7 +3541,10 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
         coarse_big = flags[1] != 0.0;
     }
     h->coarse_local = coarse_local;
-    h->coarse_host_driven = coarse_local && coarse_big;   // the same on every rank: the host-driven CG is collective
+    // the same on every rank: the host-driven CG is collective.  coarse_solver == 2 keeps such a level on the device
+    h->coarse_device_cg = h->prm.coarse_solver == 2 && coarse_local && coarse_big;
+    h->coarse_host_driven = coarse_local && coarse_big && !h->coarse_device_cg;
+    if (h->coarse_device_cg && A[nlevels - 1]->M > sk::CG_MAXN) CHK(ensure_dcg(h.get(), A[nlevels - 1]->M));   // no allocation may happen inside a graph capture
     if (h->prm.coarse_solver == 1 && coarse_local && A[nlevels - 1]->M > 0 && !h->coarse_host_driven) {
         // dense inverse by Gauss-Jordan with partial pivoting (host, once)
         std::vector<double> inv;
@@ -3863,6 +3874,7 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 #include "sgpu_gmres.hip.inc"
 #include "sgpu_eig.hip.inc"
 #include "sgpu_lanczos.hip.inc"
+#include "sgpu_coarse_cg.hip.inc"
 
 // sgpu_amg_set_operator (include/saena_gpu.h).  After the block helpers: the block work space of a hierarchy keeps a Chebyshev
 // direction per operator and K, which the incoming operator does not have yet.
@@ -3890,6 +3902,7 @@ extern "C" int sgpu_amg_set_operator(sgpu_amg *h, int level, sgpu_op *A_new, val
         CHK(dense_inverse(A_new, inv));
         CHK(dev_upload(Ainv, inv.data(), inv.size()));
     }
+    if (coarsest && h->coarse_device_cg && A_new->M > sk::CG_MAXN) CHK(ensure_dcg(h, A_new->M));    // (kept: the row count is the outgoing operator's)
     // what a capture must not allocate: the Chebyshev direction (scalar, and per K of every block work space that exists)
     if (!coarsest && h->prm.smoother == 1) CHK(ensure_d(A_new));
     for (int K : {2, 4, 8})

@@ -92,6 +92,7 @@ HOST_SYMBOLS.update({
     "saena_amg_set_matrix": (C.c_int, [_VP, _VP, C.POINTER(OptionsC)]),
     "saena_amg_update": (C.c_int, [_VP, _VP, C.c_int]),
     "saena_amg_set_device_eig": (C.c_int, [_VP, C.c_int]),
+    "saena_amg_set_coarse_solver": (C.c_int, [_VP, C.c_char_p]),
     "saena_amg_num_levels": (C.c_int, [_VP]),
     "saena_amg_level_info": (C.c_int, [_VP, C.c_int, _PI, C.POINTER(C.c_long), C.POINTER(C.c_long), _PD]),
     "saena_amg_level_aggregates": (C.c_int, [_VP, C.c_int, _PI, _PI]),
@@ -502,18 +503,26 @@ OPTIONS001 = dict(solver_max_iter=50, relative_tol=1e-8, smoother="jacobi", preS
 class AmgSolver:
     """saena::amg mirror (reference include/saena.hpp:195-265): set_matrix on the host, solve on the GPU."""
 
-    def __init__(self, A: Matrix, opts: OptionsC, device_eig=None):
+    def __init__(self, A: Matrix, opts: OptionsC, device_eig=None, coarse_solver=None):
         """device_eig: True lets the one-rank setup and the updates take eig_max from the device estimate (saena_amg_set_device_eig);
-        None leaves the library's default (off, unless SAENA_DEVICE_EIG=1)"""
+        None leaves the library's default (off, unless SAENA_DEVICE_EIG=1).
+        coarse_solver: "direct", "cg" or "device_cg" (saena_amg_set_coarse_solver), read by to_device; None leaves the library's
+        default ("direct", unless SAENA_COARSE_SOLVER names another)"""
         self.A, self.L = A, A.L
         self.h = self.L.saena_amg_new()
         if device_eig is not None:
             self.set_device_eig(device_eig)
+        if coarse_solver is not None:
+            self.set_coarse_solver(coarse_solver)
         _check(self.L, self.L.saena_amg_set_matrix(self.h, A.h, C.byref(opts)))
         self.opts = opts
 
     def set_device_eig(self, on):
         _check(self.L, self.L.saena_amg_set_device_eig(self.h, 1 if on else 0))
+        return self
+
+    def set_coarse_solver(self, name):
+        _check(self.L, self.L.saena_amg_set_coarse_solver(self.h, str(name).encode()))
         return self
 
     def update(self, A_new: Matrix, mode):
