@@ -178,6 +178,13 @@ int sgpu_op_get_x_window_kernel(const sgpu_op *op, int *kernel);
  * SAENA_VIDXW_BITS=0, read when the windows are built, keeps the 8-bit codes); 0: the operator is not on variant 17.  Once the
  * operator was launched in the mode: what its LAST launch read.  Results are bit-identical in both formats. */
 int sgpu_op_get_x_window_code_width(const sgpu_op *op, int *bits_per_entry);
+/* how k_vidxw_fast reads its rows on this operator: 1 as LANE MASKS -- where the dictionaries stay in scalar registers, the codes
+ * are bits, no pattern is longer than eight positions and every pattern is an ordered subset of the longest one (stencil-like
+ * operators), a slice of 64 rows is 128 bytes of 64-bit masks, two bits per (row, slot), read as scalars; no pattern id, no code
+ * and no table is loaded (such a launch still reports a code width of 1) -- 0 through the pattern table (every other operator, the
+ * mode off, another variant; SAENA_VIDXW_MASKS=0, read when the windows are built, keeps the table rows).  Once the operator was
+ * launched in the mode: what its LAST launch read.  Results are bit-identical in both formats. */
+int sgpu_op_get_x_window_row_format(const sgpu_op *op, int *format);
 /* time the (variant, lanes) candidates that apply to this operator and keep the fastest (plan-time autotune; no
  * collective).  Call it right after sgpu_op_create: operators of up to 768 entries per row hold a host copy of their
  * values (8 B per entry) for the re-ordered forms from the create until this call -- or until sgpu_op_destroy. */

@@ -73,6 +73,7 @@ SYMBOLS = {
     "sgpu_op_get_x_windows": (C.c_int, [_VP, _PI]),
     "sgpu_op_get_x_window_kernel": (C.c_int, [_VP, _PI]),
     "sgpu_op_get_x_window_code_width": (C.c_int, [_VP, _PI]),
+    "sgpu_op_get_x_window_row_format": (C.c_int, [_VP, _PI]),
     "sgpu_spmv": (C.c_int, [_VP, _VP, _VP]),
     "sgpu_residual": (C.c_int, [_VP, _VP, _VP, _VP]),
     "sgpu_residual_negative": (C.c_int, [_VP, _VP, _VP, _VP]),
@@ -441,6 +442,13 @@ class Operator:
         k_vidxw_fast reads the codes of scalar dictionaries packed to one bit per entry; 0: another variant"""
         v = C.c_int()
         check(lib().sgpu_op_get_x_window_code_width(self.h, C.byref(v)))
+        return v.value
+
+    def x_window_row_format(self):
+        """how k_vidxw_fast reads its rows (of the last launch in the mode, once there was one): 1 as lane masks in scalar registers,
+        0 through the pattern table (or the mode is off, or another variant)"""
+        v = C.c_int()
+        check(lib().sgpu_op_get_x_window_row_format(self.h, C.byref(v)))
         return v.value
 
     def exchange_mode(self):

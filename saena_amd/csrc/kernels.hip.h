@@ -28,6 +28,7 @@
 #include "xwin_stage.h"
 #include "xwin_head.h"      // NXCD, VI_MAX, VW_MAX_LDS, SPX_ROWS, SPX_MAXWIN, SPX_LDS_BYTES and VwHead: shared with the host-side plans
 #include "vw_fast.h"
+#include "vw_masks.h"
 
 namespace sk {
 
@@ -1100,12 +1101,106 @@ typedef double sk_gdouble;
 // BITS (with SD alone): arg.vcode holds the bit codes and arg.cbytes their bytes per slice (vw_fast.h): a lane's turn is one byte,
 // loaded where the eight bytes of codes were, and a position's value is picked by bit u of it.
 // blockDim.x = R; dynamic LDS: [windows of x][R / 256 dictionaries of VI_MAX unless SD][table] (vwfast::plan).
-template <int R, int EPI, bool NT, bool SD, bool BITS = false>
+// MASKS (with BITS alone): arg.masks holds the rows as lane masks (vw_masks.h) and arg.slot_off the slots' LDS byte offsets.  The
+// wave's record and its two dictionary values are SCALAR loads, issued behind the x trips' loads; no pattern id, no code, no table
+// chunk is loaded, nothing but the windows goes to LDS, and the x addresses (8 tid + a scalar) are known before the barrier.  Slot u
+// of a lane: (value mask ? s1 : s0) * x, added where the presence mask holds the lane, -0.0 where not -- the selects take the masks
+// straight from their scalar register pairs.  (Wave-uniform shortcuts chosen by scalar tests on the record -- a scalar value where a
+// slot's value mask is all-or-nothing, no select where every row holds every slot -- measured SLOWER than this body alone: DESIGN.md
+// section 4, sixth pass.)
+template <int R, int EPI, bool NT, bool SD, bool BITS = false, bool MASKS = false>
 __global__ __launch_bounds__(R) void k_vidxw_fast(const vwfast::VwFast arg) {
     static_assert((R == 256 || R == 512) && (EPI == EPI_SPMV || EPI == EPI_RESIDUAL || EPI == EPI_JACOBI), "vw_fast.h: the rule");
     static_assert(!BITS || SD, "vw_fast.h: bit codes where the dictionaries stay in scalar registers");
+    static_assert(!MASKS || BITS, "vw_masks.h: mask rows where the codes are bits");
     extern __shared__ __attribute__((aligned(16))) double vw_lds[];
     constexpr int SH = R == 256 ? 2 : 3, D = R >> 8;                // log2(slices) and dictionaries per workgroup
+    if constexpr (MASKS) {
+        vwfast::VwFast f = arg;
+        if constexpr (EPI == EPI_SPMV) f.rhs = nullptr;
+        if constexpr (EPI != EPI_JACOBI) { f.inv_diag = nullptr; f.u = nullptr; f.c0 = 0.0; }
+        if constexpr (!NT) f.st_plain = 0;
+        unsigned long long y_bits = reinterpret_cast<unsigned long long>(f.y);
+        // the argument in one batch, as below -- but NOT volatile: behind a volatile statement the compiler takes the record's uniform
+        // loads for clobbered and issues them as vector loads with a readfirstlane pair per word.  This is a property of the compiled
+        // code that nothing in the tree checks: on a compiler change, run tools/kernel_waits.py on this instantiation again -- its
+        // prologue must list three "scalar load"s behind the last argument wait and four vector loads (profiles/r13_*_prologue_isa_*)
+        asm("" : "+s"(f.trip[0].lds8), "+s"(f.trip[0].cnt), "+s"(f.trip[1].lds8), "+s"(f.trip[1].cnt), "+s"(f.trip[2].lds8), "+s"(f.trip[2].cnt),
+                 "+s"(f.trip[3].lds8), "+s"(f.trip[3].cnt), "+s"(f.S8), "+s"(f.lmax), "+s"(f.st_plain), "+s"(y_bits), "+s"(f.c0),
+                 "+s"(f.slot_off[0]), "+s"(f.slot_off[1]), "+s"(f.slot_off[2]), "+s"(f.slot_off[3]), "+s"(f.slot_off[4]), "+s"(f.slot_off[5]),
+                 "+s"(f.slot_off[6]), "+s"(f.slot_off[7])
+               : "s"(f.nrows), "s"(f.nblk), "s"(f.rq), "s"(f.rr), "s"(f.vd_u), "s"(f.xbytes),
+                 "s"(f.trip[0].col), "s"(f.trip[1].col), "s"(f.trip[2].col), "s"(f.trip[3].col));
+        const int tid = threadIdx.x;
+        const unsigned t8 = 8u * (unsigned)tid;
+        const int b = vwfast::remap((int)blockIdx.x, f.rq, f.rr);
+        const int r0 = b * R;
+        const int s = __builtin_amdgcn_readfirstlane((b << SH) + (tid >> 6));
+        const bool live = s < f.nblk;                              // (the last workgroup's spare waves still stage and meet the barrier)
+        const bool row = r0 + tid < f.nrows;
+        const unsigned tc = min((unsigned)tid, (unsigned)(f.nrows - 1 - r0));
+        // ---- 1. the lane's global loads: the epilogue's operands and the windows; then the wave's scalar loads
+        double pre_b = 0.0, pre_dg = 0.0, pre_u = 0.0;
+        if constexpr (EPI != EPI_SPMV) {
+            pre_b = ld_once<NT>(f.rhs + r0 + tc);
+            if constexpr (EPI == EPI_JACOBI) { pre_dg = ld_once<NT>(f.inv_diag + r0 + tc); pre_u = (f.u + r0)[tc]; }
+        }
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(f.x), 0, (int)f.xbytes, 0x00020000);
+        double v[vwfast::TRIPS];
+#pragma unroll
+        for (int u = 0; u < vwfast::TRIPS; ++u) {
+            const sk_u2w q = __builtin_amdgcn_raw_buffer_load_b64(rs, 8u * (unsigned)(r0 + f.trip[u].col) + t8, 0, 0);
+            __builtin_memcpy(&v[u], &q, sizeof(double));
+        }
+        // (a spare wave: slice 0's record and the workgroup's first dictionary, neither used)
+        const unsigned long long *mp = arg.masks + (size_t)(live ? s : 0) * vwmasks::REC_WORDS;
+        const unsigned long long *dp = reinterpret_cast<const unsigned long long *>(arg.vdict) + (live ? s >> 2 : b * D) * f.vd_u;
+        unsigned long long pm[vwmasks::MAXSLOT], vm[vwmasks::MAXSLOT];
+#pragma unroll
+        for (int u = 0; u < vwmasks::MAXSLOT; ++u) { pm[u] = mp[u]; vm[u] = mp[vwmasks::MAXSLOT + u]; }
+        const unsigned long long s0 = dp[0], s1 = dp[1];
+        // ---- 2. -> LDS
+        char *lds = reinterpret_cast<char *>(vw_lds);
+#pragma unroll
+        for (int u = 0; u < vwfast::TRIPS; ++u) *reinterpret_cast<double *>(lds + (tid < f.trip[u].cnt ? f.trip[u].lds8 + (int)t8 : f.S8)) = v[u];
+        __syncthreads();
+        if (!live) return;
+        // ---- 3. the row: N slots (never fewer than four: the lengths 1 ... 3 share the body of 4, their further masks are empty)
+        const char *xr = lds + t8;
+        const double d0 = __longlong_as_double((long long)s0), d1 = __longlong_as_double((long long)s1);
+        double sum = 0.0;
+        auto go = [&](auto NN) {                                     // branch-free: no test on the record, one body for every wave
+            constexpr int N = decltype(NN)::value;
+            double xx[N];
+#pragma unroll
+            for (int u = 0; u < N; ++u) xx[u] = *reinterpret_cast<const double *>(xr + f.slot_off[u]);
+#pragma unroll
+            for (int u = 0; u < N; ++u) {
+                const double p = (__builtin_amdgcn_inverse_ballot_w64(vm[u]) ? d1 : d0) * xx[u];
+                sum += __builtin_amdgcn_inverse_ballot_w64(pm[u]) ? p : -0.0;
+            }
+        };
+        switch (f.lmax) {
+        case 0: case 1: case 2: case 3: case 4: go(std::integral_constant<int, 4>{}); break;
+        case 5: go(std::integral_constant<int, 5>{}); break;
+        case 6: go(std::integral_constant<int, 6>{}); break;
+        case 7: go(std::integral_constant<int, 7>{}); break;
+        default: go(std::integral_constant<int, 8>{}); break;
+        }
+        if (row) {
+            sk_gdouble *yp = reinterpret_cast<sk_gdouble *>(y_bits) + r0 + (unsigned)tid;
+            double out = sum;
+            if constexpr (EPI == EPI_RESIDUAL) out = sum - pre_b;
+            if constexpr (EPI == EPI_JACOBI) {
+                double t = sum - pre_b;
+                t *= pre_dg * f.c0;
+                out = pre_u - t;
+            }
+            if constexpr (NT) { if (f.st_plain) *yp = out; else __builtin_nontemporal_store(out, yp); }
+            else *yp = out;
+        }
+        return;
+    }
     // the argument, whole, in scalar registers HERE: one batch of loads and one wait.  The compiler would sink each field's load to its
     // first use, behind the barrier and into the row loop; as results of an asm statement they are neither sunk nor loaded again
     vwfast::VwFast f = arg;
@@ -2230,6 +2325,33 @@ __global__ __launch_bounds__(BLOCK) void k_vi_pack_bits(const sk_u2v *__restrict
     const sk_u2v c = code[i];
     bits[i] = (unsigned char)vwfast::pack8(c.x, c.y);
     if (vwfast::above1(c.x, c.y)) atomicOr(above1, 1);
+}
+
+// ---- setup: pattern ids, table and k_vidx's codes -> the rows of k_vidxw_fast as lane masks (vw_masks.h): a wave per slice, a lane
+// per row.  A lane forms its row's presence and value bits per slot (vwmasks::lane_bits: its pattern's length from the table, its
+// positions' slots from pslot, its codes from the first turn of its slice -- the rule admits one turn), sixteen ballots make the
+// record, lanes 0 ... 15 store a word each.  A code above 1 or a position without a slot raises *flag (build_xwin then keeps the
+// table rows).  tab: build_xwin's table (the lengths lead it); uw: positions per slice; grid: ceil(nslices / 4) x BLOCK.
+__global__ __launch_bounds__(BLOCK) void k_vi_pack_masks(const unsigned short *__restrict__ pid, const unsigned short *__restrict__ tab, const unsigned char *__restrict__ pslot,
+                                                         const sk_u2v *__restrict__ code, int uw, int nrows, int nslices, unsigned long long *__restrict__ masks, int *__restrict__ flag) {
+    const int s = (int)(blockIdx.x * (BLOCK / 64) + threadIdx.x / 64), lane = threadIdx.x & 63;
+    if (s >= nslices) return;                                      // (a whole wave)
+    const long long r = (long long)s * 64 + lane;
+    unsigned b = 0;
+    if (r < nrows) {
+        const int p = pid[r];
+        const int len = min((int)tab[p], vwmasks::MAXSLOT);
+        const sk_u2v c = code[(size_t)s * (size_t)(8 * uw) + lane];            // (vwfast::code_index: a lane's turn is one 8-byte word)
+        b = vwmasks::lane_bits(len, pslot + (size_t)p * vwmasks::MAXSLOT, [&](int j) { return ((j < 4 ? c.x : c.y) >> (8 * (j & 3))) & 0xffu; });
+    }
+    if (b >> 16) atomicOr(flag, (int)(b >> 16));
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int w = 0; w < vwmasks::REC_WORDS; ++w) {                 // word w: presence masks, then value masks -- bit w of the lane's bits
+        const unsigned long long m = __ballot((b >> w) & 1u);
+        if (lane == w) mine = m;
+    }
+    if (lane < vwmasks::REC_WORDS) masks[(size_t)s * vwmasks::REC_WORDS + lane] = mine;
 }
 
 // ---- setup: the 8-bit value codes and per-workgroup dictionaries of k_vidx, on the device ----

@@ -221,12 +221,14 @@ struct CsrPart {
     // window list and the ONE table as 16-bit LDS byte offsets -- two small tables next to k_vidx's arrays -- and plan: what of
     // xwin_plan.h's plan every launch passes by value (the head, the common-path kernel's argument) or sizes its LDS by; vw_rows: the R in
     // use, 0 = direct gathers.  bits: the codes at one bit per entry (vw_fast.h), where the plan at this R keeps its dictionaries in scalar
-    // registers -- packed from vi_code by build_xwin, read by k_vidxw_fast alone, and gone with the tables of this R
-    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; DevArr<unsigned char> bits; xwplan::VwScalars plan; bool ok = false; char tried = 0; };
+    // registers -- packed from vi_code by build_xwin, read by k_vidxw_fast alone, and gone with the tables of this R.  masks: the rows
+    // as lane masks (vw_masks.h), a record per slice, where the bit codes exist and the rule takes the table: same owner, same lifetime
+    struct XWin { DevArr<unsigned short> tab; DevArr<int> win; DevArr<unsigned char> bits; DevArr<unsigned long long> masks; xwplan::VwScalars plan; bool ok = false; char tried = 0; };
     XWin            vw[3];
     int             vw_rows = 0;
     mutable int     vw_last = -1;         // what the last launch in the mode ran (0 k_vidxw, 1 / 2 k_vidxw_fast as fast_kind), -1: none since the mode was set
     mutable int     vw_last_width = -1;   // ... and the bits per entry of the code stream it read (8, or 1: the bit codes), -1: none
+    mutable int     vw_last_rows = -1;    // ... and its row format (0: through the table, 1: lane masks), -1: none
     // x in LDS (variant 10): absolute 16-bit column ids and nnz-balanced row chunks, one per CU.  The chunk plan (k_sellx is built
     // on top of it) ...
     struct XldsPlan {
@@ -286,7 +288,8 @@ unsigned part_storage_mask(const CsrPart &P) {
         P.sc.sl_col || P.sc.sl_len || P.sc.sl_base || P.sc.sl_segptr,
         P.sp.sp_pat || P.sp.sp_tab || P.sp.sp_wgptr || P.sp.sp_rbase,
         P.vi.vi_code || P.vi.vi_cptr || P.vi.vi_dptr || P.vi.vi_dict,
-        P.vw[0].tab || P.vw[0].win || P.vw[0].bits, P.vw[1].tab || P.vw[1].win || P.vw[1].bits, P.vw[2].tab || P.vw[2].win || P.vw[2].bits,
+        P.vw[0].tab || P.vw[0].win || P.vw[0].bits || P.vw[0].masks, P.vw[1].tab || P.vw[1].win || P.vw[1].bits || P.vw[1].masks,
+        P.vw[2].tab || P.vw[2].win || P.vw[2].bits || P.vw[2].masks,
         P.sp2.sp2_val || P.sp2.sp2_ptr,
         P.spx.spx_tab || P.spx.spx_pat || P.spx.spx_win || P.spx.spx_wgptr,
         P.rt.rt_pat || P.rt.rt_itab || P.rt.rt_vtab,
@@ -1122,7 +1125,9 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
     HIPCHK(hipStreamSynchronize(g.cs));
     // (the environment is read per operator, so that one process can build both paths)
     const char *fast_env = std::getenv("SAENA_VIDXW_FAST");
-    const xwplan::VwPlan plan = xwplan::plan_vidxw(tab.data(), npat, W, M, P.ncols, R, P.vi_uw8, dptr.data(), fast_env && std::atoi(fast_env) == 0);
+    const char *masks_env = std::getenv("SAENA_VIDXW_MASKS");
+    const xwplan::VwPlan plan = xwplan::plan_vidxw(tab.data(), npat, W, M, P.ncols, R, P.vi_uw8, dptr.data(), fast_env && std::atoi(fast_env) == 0,
+                                                   masks_env && std::atoi(masks_env) == 0);
     if (plan.refusal) return no(xwplan::refusal_text(plan.refusal));
     CHK(dev_upload(X.tab, plan.tab.data(), plan.tab.size(), 8));
     CHK(dev_upload(X.win, plan.win.data(), plan.win.size()));
@@ -1147,6 +1152,25 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
         HIPCHK(hipStreamSynchronize(g.cs));
         if (above1) { X.bits = {}; bits_why = "a code above 1"; }
     }
+    // the rows as lane masks (vw_masks.h), where the rule takes the table and the codes are bits: packed on the device from the pattern
+    // ids, the table just uploaded, the pattern -> slot table and k_vidx's codes; a code above 1 or a position without a slot -- none,
+    // by the rule -- keeps the table rows
+    const char *masks_why = !X.bits && plan.s.mask_clause == vwmasks::TAKEN ? "the codes are 8 bits per entry" : vwmasks::clause_text(plan.s.mask_clause);
+    const size_t mask_bytes = (size_t)vwmasks::total_words(ns) * sizeof(unsigned long long);
+    if (plan.s.mask_clause == vwmasks::TAKEN && X.bits) {
+        DevArr<unsigned char> d_pslot;
+        DevArr<int> d_flag;
+        CHK(dev_upload(d_pslot, plan.pslot.data(), plan.pslot.size()));
+        if (X.masks.alloc((size_t)vwmasks::total_words(ns)) != hipSuccess || d_flag.alloc(1) != hipSuccess) { X.masks = {}; return fail(SGPU_ERR_NOMEM, "hipMalloc of %zu bytes failed", mask_bytes); }
+        HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int), g.cs));
+        SGPU_LAUNCH(sk::k_vi_pack_masks, dim3((unsigned)((ns + sk::BLOCK / 64 - 1) / (sk::BLOCK / 64))), dim3(sk::BLOCK), 0, g.cs, (const unsigned short *)P.sp.sp_pat, (const unsigned short *)X.tab.get(),
+                    (const unsigned char *)d_pslot.get(), reinterpret_cast<const sk::sk_u2v *>(P.vi.vi_code.get()), P.vi_uw8, M, ns, X.masks.get(), d_flag.get());
+        HIPCHK(hipGetLastError());
+        int flag = 0;
+        HIPCHK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
+        if (flag) { X.masks = {}; masks_why = flag & vwmasks::CODE_ABOVE_1 ? "a code above 1" : "a position without a slot"; }
+    }
     X.ok = true;
     if (std::getenv("SAENA_SETUP_TIMING")) {
         const xwplan::VwScalars &s = X.plan;
@@ -1161,6 +1185,10 @@ int build_xwin(CsrPart &P, int k, std::string *why = nullptr) {
             fprintf(stderr, "[sgpu] x windows at %d rows: codes of 1 bit per entry, %lld bytes packed from %lld bytes of 8-bit codes\n", R, (long long)bit_bytes, (long long)byte_codes);
         else
             fprintf(stderr, "[sgpu] x windows at %d rows: codes of 8 bits per entry (%s), %lld bytes, 1-bit codes would take %lld\n", R, bits_why, (long long)byte_codes, (long long)bit_bytes);
+        if (X.masks)
+            fprintf(stderr, "[sgpu] x windows at %d rows: rows as lane masks, %zu bytes in %d records of %d slots\n", R, mask_bytes, ns, s.head.lmax);
+        else
+            fprintf(stderr, "[sgpu] x windows at %d rows: rows through the table (%s)\n", R, masks_why);
     }
     return SGPU_OK;
 }
@@ -1487,11 +1515,11 @@ VidxwKernelFn pick_vidxw(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> VidxwKernelFn { return sk::k_vidxw<E(), H(), N()>; }); }); });
 }
 // the common path (vw_fast.h): 256 / 512 rows, the three epilogues with operands fetched up front, dictionaries in LDS / in scalar registers
-// bits (with sd alone): the codes at one bit per entry
-VidxwFastKernelFn pick_vidxw_fast(int rows, int epi, bool nt, bool sd, bool bits) {
-    if (bits && !sd) return nullptr;
+// bits (with sd alone): the codes at one bit per entry; masks (with bits alone): the rows as lane masks (vw_masks.h)
+VidxwFastKernelFn pick_vidxw_fast(int rows, int epi, bool nt, bool sd, bool bits, bool masks) {
+    if ((bits && !sd) || (masks && !bits)) return nullptr;
     return among<256, 512>(rows, [&](auto R) { return among<sk::EPI_SPMV, sk::EPI_RESIDUAL, sk::EPI_JACOBI>(epi, [&](auto E) { return with_bool(nt, [&](auto N) { return with_bool(sd, [&](auto S) {
-        return with_bool(bits, [&](auto B) -> VidxwFastKernelFn { return sk::k_vidxw_fast<R(), E(), N(), S(), S() && B()>; }); }); }); }); });
+        return with_bool(bits, [&](auto B) { return with_bool(masks, [&](auto K) -> VidxwFastKernelFn { return sk::k_vidxw_fast<R(), E(), N(), S(), S() && B(), S() && B() && K()>; }); }); }); }); }); });
 }
 SellKernelFn pick_rowt(int epi, bool halo, bool nt) {
     return per_epi(epi, [&](auto E) { return with_bool(halo, [&](auto H) { return with_bool(nt, [&](auto N) -> SellKernelFn { return sk::k_rowt<E(), H(), N()>; }); }); });
@@ -1684,18 +1712,23 @@ int launch_part(const CsrPart &P, int epi, const double *x, double *y, const Epi
                 f.vcode = a.vcode; f.dst = a.dst; f.ptab = X.tab.get(); f.vdict = a.vdict;
                 // the bit codes where build_xwin packed them: an eighth of the code stream, and the non-temporal rule is given what this launch reads
                 const bool bits = X.plan.fast_kind == 2 && X.bits;
+                // the rows as lane masks where build_xwin packed them: such a launch reads neither pattern ids (2 B a row: the mode has no
+                // rowbase) nor codes but a record per slice, and the non-temporal rule is given that; it reports the bit codes' width
+                const bool masks = bits && X.masks;
                 bool ntf = nt;
-                if (bits) {
-                    f.vcode = X.bits.get(); f.cbytes = vwfast::bit_slice_bytes(f.w8);
+                if (masks)
+                    ntf = row_pattern_nt(a, P.vi_bytes - P.vi_code_bytes - 2 * (int64_t)P.nrows + (int64_t)vwmasks::REC_BYTES * a.nblk, a.nblk, (double)vwmasks::REC_BYTES);
+                else if (bits)
                     ntf = row_pattern_nt(a, P.vi_bytes - P.vi_code_bytes + P.vi_code_bytes / 8, a.nblk, (double)P.nnz / 8.0 / (double)std::max(1, a.nblk));
-                }
+                if (bits) { f.vcode = X.bits.get(); f.cbytes = vwfast::bit_slice_bytes(f.w8); }
                 f.x = a.x; f.y = a.y; f.rhs = a.rhs; f.inv_diag = a.inv_diag; f.u = a.u; f.c0 = a.c0;
                 f.nt_from = a.nt_from; f.st_plain = a.st_plain; f.nrows = P.nrows;
-                P.vw_last = X.plan.fast_kind; P.vw_last_width = vwfast::code_width(bits);
-                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, ntf, X.plan.fast_kind == 2, bits), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.fast_lds, g.cs, f);
+                f.masks = masks ? X.masks.get() : nullptr;
+                P.vw_last = X.plan.fast_kind; P.vw_last_width = vwfast::code_width(bits); P.vw_last_rows = masks ? 1 : 0;
+                SGPU_LAUNCH_PICKED("k_vidxw_fast", pick_vidxw_fast(P.vw_rows, epi, ntf, X.plan.fast_kind == 2, bits, masks), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.fast_lds, g.cs, f);
                 break;
             }
-            P.vw_last = 0; P.vw_last_width = 8;
+            P.vw_last = 0; P.vw_last_width = 8; P.vw_last_rows = 0;
             SGPU_LAUNCH_PICKED("k_vidxw", pick_vidxw(epi, halo, nt), dim3((a.nblk + spb - 1) / spb), dim3(P.vw_rows), (size_t)X.plan.lds, g.cs, a, X.plan.head, P.nrows);
         } else
         SGPU_LAUNCH_PICKED("k_vidx", pick_vidx(epi, halo, nt), dim3((a.nblk + 3) / 4), dim3(sk::BLOCK), lds, g.cs, a, P.nrows);
@@ -2562,7 +2595,7 @@ int sgpu_op_set_variant(sgpu_op *op, int variant) {
     if (!ok) return refuse_form(variant);
     op->loc.variant = variant;
     op->loc.vw_rows = 0;                                 // F_VIDX alone gathers directly; sgpu_op_set_x_windows turns the windows on
-    op->loc.vw_last = -1; op->loc.vw_last_width = -1;
+    op->loc.vw_last = -1; op->loc.vw_last_width = -1; op->loc.vw_last_rows = -1;
     ++g_plan_generation;
     if (variant == F_VIDX)
         if (const char *e = std::getenv("SAENA_X_WINDOWS")) {     // development: pin the mode where only the variant can be pinned (counter passes); refused -> direct
@@ -2579,7 +2612,7 @@ int sgpu_op_set_x_windows(sgpu_op *op, int rows_per_workgroup) {
     CHK(need_ctx());
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     const int R = rows_per_workgroup;
-    op->loc.vw_last = -1; op->loc.vw_last_width = -1;
+    op->loc.vw_last = -1; op->loc.vw_last_width = -1; op->loc.vw_last_rows = -1;
     if (R == 0) { op->loc.vw_rows = 0; ++g_plan_generation; return SGPU_OK; }
     const int k = xwin_slot(R);
     if (k < 0) return fail(SGPU_ERR_ARG, "x windows: rows per workgroup must be 0 (off), 256, 512 or 1024");
@@ -2616,6 +2649,16 @@ int sgpu_op_get_x_window_code_width(const sgpu_op *op, int *bits_per_entry) {
     const CsrPart &P = op->loc;
     const int k = P.variant == F_VIDX ? xwin_slot(P.vw_rows) : -1;
     *bits_per_entry = P.variant != F_VIDX ? 0 : k < 0 ? 8 : P.vw_last_width >= 0 ? P.vw_last_width : vwfast::code_width(P.vw[k].plan.fast_kind == 2 && P.vw[k].bits);
+    return SGPU_OK;
+}
+
+// the row format of the last launch of variant 17 in the x-window mode: 1 where k_vidxw_fast read its rows as lane masks
+// (vw_masks.h), 0 where the rows went through the pattern table; before a launch: what a launch without a halo would read
+int sgpu_op_get_x_window_row_format(const sgpu_op *op, int *format) {
+    if (!op || !format) return fail(SGPU_ERR_ARG, "null argument");
+    const CsrPart &P = op->loc;
+    const int k = P.variant == F_VIDX ? xwin_slot(P.vw_rows) : -1;
+    *format = k < 0 ? 0 : P.vw_last_rows >= 0 ? P.vw_last_rows : (P.vw[k].plan.fast_kind == 2 && P.vw[k].bits && P.vw[k].masks) ? 1 : 0;
     return SGPU_OK;
 }
 

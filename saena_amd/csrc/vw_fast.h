@@ -18,6 +18,7 @@ namespace vwfast {
 constexpr int TRIPS = 4;                          // trips the lean kernel issues, used or not (the 7-point levels: 1 + 2 + 1)
 using sk::NXCD;
 using sk::VI_MAX;                                 // values of a dictionary, one per 256 rows
+constexpr int MASK_SLOTS = 8;                     // slots of a row held as lane masks (vw_masks.h: MAXSLOT)
 
 // ---- the rule ----
 // which clause refuses an operator x R, in the order the rule is written; TAKEN: eligible
@@ -98,6 +99,7 @@ struct VwFast {
     const unsigned short *dst;        // pattern ids
     const void           *ptab;       // the table as 16-bit words (build_xwin's), read in 16-byte chunks
     const double         *vdict;      // the dictionaries back to back
+    const unsigned long long *masks;  // the rows as lane masks, a record per slice (vw_masks.h), or null: rows through the table
     const double         *x;
     const double         *rhs, *inv_diag, *u;
     int nrows, nblk;                  // rows; slices of 64 rows
@@ -115,6 +117,7 @@ struct VwFast {
     // the row loop and the store
     int w8;                           // positions of a slice (a multiple of 8)
     int lmin, lmax, body0;            // the shortest and the longest pattern; body(lmin, lmax, 0)
+    int slot_off[MASK_SLOTS];         // mask rows: the LDS byte offset of slot u for the workgroup's first row (vw_masks.h: rule)
     int st_plain;
     double *y;
     double  c0;

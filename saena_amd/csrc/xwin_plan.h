@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <vector>
 #include "vw_fast.h"
+#include "vw_masks.h"
 
 namespace xwplan {
 
@@ -70,16 +71,19 @@ struct VwScalars {
     int wp = 0, lds = 0;
     vwfast::VwFast fast{};
     int fast_kind = 0, fast_clause = 0, fast_lds = 0;
+    int mask_clause = vwmasks::NOT_SCALAR;     // vw_masks.h's rule at this R: TAKEN -> fast.slot_off holds the slots, the rows can be lane masks
 };
 struct VwPlan {
     int refusal = ACCEPTED;
     VwScalars s;
     std::vector<unsigned short> tab;           // the table as 16-bit words
     std::vector<int> win;                      // the window list as uploaded
+    std::vector<unsigned char> pslot;          // mask rows (mask_clause TAKEN or SWITCHED_OFF): pattern x position -> slot, vwmasks::MAXSLOT per pattern
 };
 // tab: the pattern table as read back, npat rows of W + 1 ints; M x ncols: the operator; R: rows per workgroup; uw: the slices' common
-// code width (0: they differ); dptr: where the dictionaries begin, one per 256 rows and the end; fast_off: SAENA_VIDXW_FAST=0
-inline VwPlan plan_vidxw(const int *tab, int npat, int W, int M, int ncols, int R, int uw, const int *dptr, bool fast_off) {
+// code width (0: they differ); dptr: where the dictionaries begin, one per 256 rows and the end; fast_off: SAENA_VIDXW_FAST=0;
+// masks_off: SAENA_VIDXW_MASKS=0
+inline VwPlan plan_vidxw(const int *tab, int npat, int W, int M, int ncols, int R, int uw, const int *dptr, bool fast_off, bool masks_off = false) {
     VwPlan p;
     auto no = [&](Refusal r) { p.refusal = r; return p; };
     std::vector<int> offs;
@@ -138,6 +142,11 @@ inline VwPlan plan_vidxw(const int *tab, int npat, int W, int M, int ncols, int 
     p.s.fast_kind = vwfast::kind(p.s.fast_clause, vd_u);
     if (p.s.fast_kind)
         p.s.fast_lds = vwfast::plan(p.s.fast, R, (M + 63) / 64, ncols, (int)S, lp, (int)words, wp, uw, vd_u, h.lmin, h.lmax, h.trip, p.s.fast_kind == 2);
+    // the rows as lane masks where vw_masks.h's rule takes the table: the slots' LDS byte offsets are the longest pattern's positions
+    p.pslot.assign((size_t)npat * vwmasks::MAXSLOT, (unsigned char)vwmasks::NO_SLOT);
+    int nslot = 0;
+    p.s.mask_clause = vwmasks::rule(p.s.fast_kind, p.tab.data(), p.tab.data() + lp, npat, wp, masks_off, &nslot, p.s.fast.slot_off, p.pslot.data());
+    if (p.s.mask_clause != vwmasks::TAKEN && p.s.mask_clause != vwmasks::SWITCHED_OFF) p.pslot.clear();
     return p;
 }
 
