@@ -299,6 +299,13 @@ public:
     // eig_residuals() holds ||A x_j - lambda_j x_j||, last_iterations() the iterations; returns 1 if a wanted pair did not converge.
     // Expect slow convergence when nev cuts a cluster of equal eigenvalues in two: let nev end at a gap of the spectrum.
     int eigs(value_t *&x, std::vector<value_t> &lambda, saena::options *opts, int K, int nev, const value_t *x0 = nullptr, bool precondition = true);
+    // The same for the generalised problem A x = lambda B x (sgpu_eigs_LOBPCG_gen, one rank): B is an assembled symmetric positive
+    // definite matrix of the same size and partition (a mass matrix, consistent or lumped).  The eigenvectors are B-orthonormal on
+    // return; a column is converged when ||A x - lambda B x|| < tol lambda ||B x||; eig_residuals() holds ||A x_j - lambda_j B x_j||.
+    // The preconditioner is the V-cycle of A.  A distinct name: no call of eigs becomes ambiguous.  A LUMPED (diagonal) B must be
+    // assembled after B.set_remove_boundary(false): assemble() otherwise takes every single-entry row for a boundary node and removes
+    // it, and eigs_gen refuses the B that is left for its size, with a message that says so.
+    int eigs_gen(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B, saena::options *opts, int K, int nev, const value_t *x0 = nullptr, bool precondition = true);
     const std::vector<value_t> &eig_residuals() const { return eig_res_; }
     comm get_orig_comm();
 
@@ -334,7 +341,9 @@ private:
     std::vector<value_t> rhs_blk_;                 // set_rhs_block: column-major size x nrhs_
     int nrhs_ = 0;
     std::vector<std::vector<value_t>> hist_blk_;   // per column of the last solve_pCG_block
-    std::vector<value_t> eig_res_;                 // of the last eigs
+    std::vector<value_t> eig_res_;                 // of the last eigs / eigs_gen
+    int eigs_common(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B, saena::options *opts, int K, int nev, const value_t *x0,
+                    bool precondition, const char *what);
     bool dynamic_levels_ = true;
     bool switch_to_dense_ = false;
     float dense_thre_override_ = 0;

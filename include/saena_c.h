@@ -213,6 +213,14 @@ int   saena_amg_solve_pFGMRES(saena_amg_h *S, const value_t *rhs_host, value_t *
  * nev should end at a gap of the spectrum, not inside a cluster of equal eigenvalues.  SGPU_ERR_NOCONV: the outputs are still written */
 int   saena_amg_eigs(saena_amg_h *S, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
                      value_t *lambda, value_t *x_host, value_t *res, int *iters);
+/* [GPU] the same for the generalised problem A x = lambda B x (sgpu_eigs_LOBPCG_gen; one rank): B is an assembled symmetric positive
+ * definite matrix of A's size (a mass matrix, consistent or lumped); its device operator is made for the call and destroyed before it
+ * returns.  On return the columns of x_host are B-orthonormal, lambda ascends, res[K] = ||A x_j - lambda_j B x_j|| (may be NULL);
+ * column j is converged when that norm is below tol lambda_j ||B x_j||.  The preconditioner is the V-cycle of A, as above.
+ * A LUMPED (diagonal) B must be assembled after saena_matrix_set_remove_boundary(B, 0): saena_matrix_assemble otherwise takes every
+ * single-entry row for a boundary node and removes it; a B whose rows differ from A's is refused (-1) with a message that says so */
+int   saena_amg_eigs_gen(saena_amg_h *S, saena_matrix_h *B, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
+                         value_t *lambda, value_t *x_host, value_t *res, int *iters);
 
 /* ---- tests: the dense generalised symmetric eigenproblem of the Rayleigh-Ritz step (host/dense_eig.cpp) ----
  * A v = w B v for symmetric A and symmetric positive definite B of order 1 <= n <= 24, row-major: w[n] ascending, V[i * n + k] =

@@ -380,10 +380,31 @@ int sgpu_solve_FGMRES(sgpu_amg *h, value_t *u, const value_t *rhs, int restart, 
  * linearly dependent; X and lambda of the last completed iteration stay valid); a Ritz value <= 0 (the operator is not SPD).
  * The work space (six block vectors) is allocated at the first call with a given K and freed with the hierarchy; the V-cycle runs
  * through one fixed pair of them in a captured graph of its own, outside the block cache of eight.  Three host synchronisations per
- * iteration, each of at most 12 K^2 + K doubles. */
+ * iteration, each of at most 12 K^2 + K doubles.  The generalised problem A x = lambda B x: sgpu_eigs_LOBPCG_gen below. */
 int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, value_t tol, int precond,
                      value_t *lambda /*[K] host*/, value_t *res /*[K] host: recomputed ||r_j||*/, int *iters,
                      value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
+
+/* ---- LOBPCG: the generalised problem A x = lambda B x --------------------------
+ * As sgpu_eigs_LOBPCG, with a second symmetric positive definite operator B of the size of the level-0 operator A (a mass matrix,
+ * consistent or lumped; one rank, no remote part): every inner product of the algorithm is the B-inner product, and B X, B W, B P are
+ * carried next to A X, A W, A P (one more block SpMV, with B, per iteration).  The preconditioner is the same block V-cycle of A, in
+ * the same captured graph as the standard solve's: a generalised call neither drops nor recaptures it.
+ * On return X is B-orthonormal (X^T B X = I) and lambda ascends.  Column j is converged when
+ * ||A x_j - lambda_j B x_j|| < tol lambda_j ||B x_j|| -- the relative backward error, which does not change when B is rescaled and is
+ * sgpu_eigs_LOBPCG's criterion for B = I.  At the end of the solve A X and B X are recomputed and only the recomputed norms declare
+ * convergence; res[j] (may be NULL) is the last recomputed ||A x_j - lambda_j B x_j||, res_hist as above.
+ * B is applied by eager launches only and never enters a captured graph; nothing keeps a pointer to it after the call returns: the
+ * caller may destroy it, or pass another B to the next call on the same hierarchy.
+ * SGPU_ERR_ARG: everything sgpu_eigs_LOBPCG refuses; a null B; a B whose rows or columns differ from A's; a B with a remote part or a
+ * halo plan; a start Gram matrix X^T B X that is not numerically positive definite (dependent start vectors, or a B that is not
+ * positive definite).  SGPU_ERR_NOCONV: as sgpu_eigs_LOBPCG, and a W^T B W, an S^T B S or a Ritz value that shows that B or A is not
+ * SPD.  The extra work space (three block vectors, the partial sums and the K sums of ||B x_j||^2) is allocated at the first
+ * generalised call with a given K and freed with the hierarchy; a process that only calls sgpu_eigs_LOBPCG allocates none of it.
+ * Three host synchronisations per iteration, of at most 12 K^2 + 2 K doubles. */
+int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, int max_iter, value_t tol, int precond,
+                         value_t *lambda /*[K] host*/, value_t *res /*[K] host: recomputed ||A x_j - lambda_j B x_j||*/, int *iters,
+                         value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
 
 /* ---- measurement -----------------------------------------------------------
  * Runs `reps` back-to-back launches of one kernel on the compute stream,

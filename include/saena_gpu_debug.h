@@ -137,7 +137,11 @@ int sgpu_debug_time_gs(int kind, const value_t *V, size_t ld, int ncols, value_t
  *                 index `iteration` (0-based), before the Rayleigh-Ritz update: eig_vector then shows W, AW, P, AP as that step left them
  *   eig_vector:   after a solve, a copy of one of the solver's own block vectors (which: 0 AX, 1 R, 2 W, 3 AW, 4 P, 5 AP) into dst
  * time_eig (tests/perf_eig.py): ms per run of `reps` back-to-back runs, kind 0: block_gram of (X, Y), 1: block_mix of ns sources
- * (X, Y, X; zero coefficients) into Out, 2: eig_residual of (AX = X, X = Y) into Out. */
+ * (X, Y, X; zero coefficients) into Out, 2: eig_residual of (AX = X, X = Y) into Out.
+ * The generalised solve (sgpu_eigs_LOBPCG_gen; tests/test_gpu_geig_kernels.py, tests/test_gpu_geig.py): eig_stop stops it the same
+ * way, and after it eig_vector also gives which = 6 BX, 7 BW, 8 BP (SGPU_ERR_STATE before the first generalised solve with this K).
+ *   geig_residual: R = AX - BX diag(lambda_dev), rr_dev[j] = ||r_j||^2 and bb_dev[j] = ||(BX)_j||^2 (K doubles each) from one pass
+ *   time_geig (tests/perf_geig.py): ms per run of `reps` back-to-back runs of geig_residual with both reductions. */
 int sgpu_debug_block_gram(sgpu_amg *h, const value_t *X, const value_t *Y, size_t n, int K, value_t *out_dev);
 int sgpu_debug_block_mix(int K, int ns, const value_t *S0, const value_t *C0, const value_t *S1, const value_t *C1, const value_t *S2,
                          const value_t *C2, const value_t *Add, value_t *Out, size_t n);
@@ -145,6 +149,9 @@ int sgpu_debug_eig_residual(sgpu_amg *h, const value_t *AX, const value_t *X, co
 int sgpu_debug_eig_stop(sgpu_amg *h, int K, int iteration);
 int sgpu_debug_eig_vector(sgpu_amg *h, int K, int which, value_t *dst);
 int sgpu_debug_time_eig(sgpu_amg *h, int kind, int ns, const value_t *X, const value_t *Y, value_t *Out, size_t n, int K, int reps, float *ms_per_run);
+int sgpu_debug_geig_residual(sgpu_amg *h, const value_t *AX, const value_t *BX, const value_t *lambda_dev, value_t *R, size_t n, int K,
+                             value_t *rr_dev, value_t *bb_dev);
+int sgpu_debug_time_geig(sgpu_amg *h, const value_t *AX, const value_t *BX, value_t *R, size_t n, int K, int reps, float *ms_per_run);
 
 /* tests (tests/test_gpu_lanczos.py): begin = 1 opens a capture on the compute stream (thread-local mode), begin = 0 ends it and
  * discards the graph -- for the entry points that must refuse to run inside a capture.  Nothing is launched in between by the tests. */

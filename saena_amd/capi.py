@@ -135,6 +135,9 @@ SYMBOLS = {
     "sgpu_debug_gs_update": (C.c_int, [_VP, C.c_size_t, C.c_int, _PD, _VP, C.c_size_t, _PD]),
     "sgpu_debug_time_gs": (C.c_int, [C.c_int, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_eigs_LOBPCG": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PI, _PD, C.c_int]),
+    "sgpu_eigs_LOBPCG_gen": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PI, _PD, C.c_int]),
+    "sgpu_debug_geig_residual": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP, _VP]),
+    "sgpu_debug_time_geig": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_block_gram": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
     "sgpu_debug_block_mix": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t]),
     "sgpu_debug_eig_residual": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
@@ -681,14 +684,19 @@ class Amg:
     def debug_block_pcg_direction(self, num, den, Z, P, n, K, active):
         check(lib().sgpu_debug_block_pcg_direction(self.h, num.ptr, den.ptr, Z.ptr, P.ptr, int(n), int(K), int(active)))
 
-    def lobpcg(self, X, nev, max_iter=100, tol=1e-8, precond=True, cap=512):
-        """sgpu_eigs_LOBPCG on the block vector X (anything with .ptr and .K; start vectors in, eigenvectors out)
+    def lobpcg(self, X, nev, max_iter=100, tol=1e-8, precond=True, cap=512, B=None):
+        """sgpu_eigs_LOBPCG on the block vector X (anything with .ptr and .K; start vectors in, eigenvectors out); with B (an
+        Operator, or anything with .h) sgpu_eigs_LOBPCG_gen: A x = lambda B x, X B-orthonormal on return
         -> (lambda[K], res[K], iterations, [history of column j], converged)"""
         K = X.K
         lam, res, it = np.full(K, np.nan), np.full(K, np.nan), C.c_int()
         hist = np.full((K, cap), np.nan)
-        st = lib().sgpu_eigs_LOBPCG(self.h, X.ptr, K, int(nev), int(max_iter), float(tol), 1 if precond else 0, lam.ctypes.data_as(_PD),
-                                    res.ctypes.data_as(_PD), C.byref(it), hist.ctypes.data_as(_PD), cap)
+        if B is None:
+            st = lib().sgpu_eigs_LOBPCG(self.h, X.ptr, K, int(nev), int(max_iter), float(tol), 1 if precond else 0, lam.ctypes.data_as(_PD),
+                                        res.ctypes.data_as(_PD), C.byref(it), hist.ctypes.data_as(_PD), cap)
+        else:
+            st = lib().sgpu_eigs_LOBPCG_gen(self.h, B.h, X.ptr, K, int(nev), int(max_iter), float(tol), 1 if precond else 0,
+                                            lam.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it), hist.ctypes.data_as(_PD), cap)
         if st not in (0, -6):
             check(st)
         return lam, res, it.value, [h[~np.isnan(h)] for h in hist], st == 0
@@ -699,6 +707,14 @@ class Amg:
 
     def debug_eig_residual(self, AX, X, lam, R, n, K, rr):
         check(lib().sgpu_debug_eig_residual(self.h, AX.ptr, X.ptr, lam.ptr, R.ptr, int(n), int(K), rr.ptr))
+
+    def debug_geig_residual(self, AX, BX, lam, R, n, K, rr, bb):
+        check(lib().sgpu_debug_geig_residual(self.h, AX.ptr, BX.ptr, lam.ptr, R.ptr, int(n), int(K), rr.ptr, bb.ptr))
+
+    def time_geig(self, AX, BX, R, n, K, reps):
+        ms = C.c_float()
+        check(lib().sgpu_debug_time_geig(self.h, AX.ptr, BX.ptr, R.ptr, int(n), int(K), int(reps), C.byref(ms)))
+        return ms.value
 
     def debug_eig_stop(self, K, iteration):
         check(lib().sgpu_debug_eig_stop(self.h, int(K), int(iteration)))

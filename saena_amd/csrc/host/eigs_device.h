@@ -1,5 +1,6 @@
 // eigs_device.h -- what saena_amg_eigs (saena_c_api.cpp) and saena::amg::eigs (saena.cpp) share: the default start vectors and the
-// trip of column-major host arrays through sgpu_eigs_LOBPCG.
+// trip of column-major host arrays through sgpu_eigs_LOBPCG, or -- with a second operator B -- through sgpu_eigs_LOBPCG_gen
+// (saena_amg_eigs_gen, saena::amg::eigs_gen).
 #pragma once
 #include "../../../include/saena_gpu.h"
 
@@ -20,10 +21,11 @@ inline void default_eig_start(size_t n, int K, value_t *out) {
 }
 
 #ifdef SAENA_WITH_GPU
-// x0_host (column-major n x K, or null for the default start) up, packed into a block vector, sgpu_eigs_LOBPCG, and the eigenvectors
-// back into x_host the same way.  -> the sgpu status (SGPU_ERR_NOCONV: the outputs are written all the same; sgpu_last_error has the text)
+// x0_host (column-major n x K, or null for the default start) up, packed into a block vector, sgpu_eigs_LOBPCG (B null: A x = lambda x)
+// or sgpu_eigs_LOBPCG_gen (A x = lambda B x), and the eigenvectors back into x_host the same way.
+// -> the sgpu status (SGPU_ERR_NOCONV: the outputs are written all the same; sgpu_last_error has the text)
 inline int eigs_host_arrays(sgpu_amg *h, size_t n, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
-                            value_t *lambda, value_t *x_host, value_t *res, int *iters) {
+                            value_t *lambda, value_t *x_host, value_t *res, int *iters, sgpu_op *B = nullptr) {
     std::vector<value_t> start;
     if (!x0_host) {
         start.resize(n * (size_t)K);
@@ -35,7 +37,9 @@ inline int eigs_host_arrays(sgpu_amg *h, size_t n, const value_t *x0_host, int K
     if (s == SGPU_OK) s = sgpu_vec_alloc(&x, n * K);
     if (s == SGPU_OK) s = sgpu_vec_upload(cm, x0_host, n * K);
     if (s == SGPU_OK) s = sgpu_block_pack(cm, x, n, K);
-    if (s == SGPU_OK) s = sgpu_eigs_LOBPCG(h, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0);
+    if (s == SGPU_OK)
+        s = B ? sgpu_eigs_LOBPCG_gen(h, B, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0)
+              : sgpu_eigs_LOBPCG(h, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0);
     if (s == SGPU_OK || s == SGPU_ERR_NOCONV) {
         int s2 = sgpu_block_unpack(x, cm, n, K);
         if (s2 == SGPU_OK) s2 = sgpu_vec_download(x_host, cm, n * K);

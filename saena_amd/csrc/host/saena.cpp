@@ -469,9 +469,23 @@ int amg::solve_pCG_block(value_t *&u, saena::options *opts) {
     return st == SGPU_OK ? 0 : 1;
 }
 int amg::eigs(value_t *&x, std::vector<value_t> &lambda, saena::options *opts, int K, int nev, const value_t *x0, bool precondition) {
+    return eigs_common(x, lambda, nullptr, opts, K, nev, x0, precondition, "saena::amg::eigs");
+}
+int amg::eigs_gen(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B, saena::options *opts, int K, int nev, const value_t *x0, bool precondition) {
+    if (!B) throw std::runtime_error("saena::amg::eigs_gen: B is null (saena::amg::eigs solves the standard problem)");
+    return eigs_common(x, lambda, B, opts, K, nev, x0, precondition, "saena::amg::eigs_gen");
+}
+// both: B null is the standard problem.  B's device operator is the matrix's own (matrix::device_op(), as estimate_eig gets it); the
+// solver keeps no pointer to it
+int amg::eigs_common(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B, saena::options *opts, int K, int nev, const value_t *x0,
+                     bool precondition, const char *what) {
     if (!damg_) throw std::runtime_error("saena::amg: set_matrix first");
-    if (K != 2 && K != 4 && K != 8) throw std::runtime_error("saena::amg::eigs: a block holds 2, 4 or 8 vectors");
+    if (K != 2 && K != 4 && K != 8) throw std::runtime_error(std::string(what) + ": a block holds 2, 4 or 8 vectors");
     const size_t n = (size_t)A_->get_num_local_rows(), nK = n * (size_t)K;
+    if (B && (size_t)B->get_num_local_rows() != n)      // most often a lumped (diagonal) B, whose single-entry rows assemble() removed as boundary nodes
+        throw std::runtime_error(std::string(what) + ": B has " + std::to_string(B->get_num_local_rows()) + " rows, the matrix of set_matrix " +
+                                 std::to_string(n) + "; both must have the same size.  A diagonal (lumped) B loses its rows to the boundary removal of "
+                                 "assemble(): call B.set_remove_boundary(false) before assembling it");
     int max_iter = 100;
     double tol = 1e-8;
     if (opts) {
@@ -482,8 +496,9 @@ int amg::eigs(value_t *&x, std::vector<value_t> &lambda, saena::options *opts, i
     lambda.assign((size_t)K, 0.0);
     eig_res_.assign((size_t)K, 0.0);
     if (!x) x = static_cast<value_t *>(std::malloc(std::max<size_t>(1, nK) * sizeof(value_t)));
-    const int st = saena_host::eigs_host_arrays(damg_, n, x0, K, nev, max_iter, tol, precondition ? 1 : 0, lambda.data(), x, eig_res_.data(), &iters_);
-    if (st != SGPU_OK && st != SGPU_ERR_NOCONV) gchk(st, "eigs");
+    const int st = saena_host::eigs_host_arrays(damg_, n, x0, K, nev, max_iter, tol, precondition ? 1 : 0, lambda.data(), x, eig_res_.data(), &iters_,
+                                                B ? B->device_op() : nullptr);
+    if (st != SGPU_OK && st != SGPU_ERR_NOCONV) gchk(st, B ? "eigs_gen" : "eigs");
     return st == SGPU_OK ? 0 : 1;
 }
 int amg::set_scale(bool sc) {

@@ -382,6 +382,7 @@ int saena_amg_solve_pCG(saena_amg_h *, const value_t *, value_t *, int *, value_
 int saena_amg_solve_pCG_block(saena_amg_h *, const value_t *, value_t *, int, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_solve_pFGMRES(saena_amg_h *, const value_t *, value_t *, int, int, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_eigs(saena_amg_h *, const value_t *, int, int, int, value_t, int, value_t *, value_t *, value_t *, int *) { return no_gpu(); }
+int saena_amg_eigs_gen(saena_amg_h *, saena_matrix_h *, const value_t *, int, int, int, value_t, int, value_t *, value_t *, value_t *, int *) { return no_gpu(); }
 #else
 static int gchk(int s) { if (s != 0) { h_err = sgpu_last_error(); } return s; }
 static void drop_device(saena_amg_h *S) {
@@ -542,6 +543,31 @@ int saena_amg_eigs(saena_amg_h *S, const value_t *x0_host, int K, int nev, int m
     if (!lambda || !x_host) { h_err = "saena_amg_eigs: null argument"; return -1; }
     const size_t n = S->H.dist.empty() ? (size_t)S->H.levels[0].A->M : (size_t)S->H.dist[0].A.M;
     return gchk(eigs_host_arrays(S->damg, n, x0_host, K, nev, max_iter, tol, precond, lambda, x_host, res, iters));
+}
+
+// sgpu_eigs_LOBPCG_gen the same way: A x = lambda B x, B an assembled matrix of A's size.  Its device operator is made for the call
+// from the matrix's layout (as saena_matrix_estimate_eig makes one) and destroyed before the call returns: the solver keeps no
+// pointer to it.  A lumped (diagonal) B must be assembled with saena_matrix_set_remove_boundary(B, 0): see the refusal below
+int saena_amg_eigs_gen(saena_amg_h *S, saena_matrix_h *B, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
+                       value_t *lambda, value_t *x_host, value_t *res, int *iters) {
+    if (!S || !S->damg) { h_err = "saena_amg_to_device has not been called"; return -1; }
+    if (!B) { h_err = "saena_amg_eigs_gen: B is null (saena_amg_eigs solves the standard problem)"; return -1; }
+    if (K != 2 && K != 4 && K != 8) { h_err = "saena_amg_eigs_gen: a block holds 2, 4 or 8 columns"; return -1; }
+    if (!lambda || !x_host) { h_err = "saena_amg_eigs_gen: null argument"; return -1; }
+    const size_t n = S->H.dist.empty() ? (size_t)S->H.levels[0].A->M : (size_t)S->H.dist[0].A.M;
+    sgpu_op_desc d; sgpu_op *o = nullptr;
+    if (saena_matrix_get_desc(B, &d)) return -1;
+    if ((size_t)d.M != n) {      // most often a lumped (diagonal) B: assemble() takes every single-entry row for a boundary node and removes it
+        h_err = "saena_amg_eigs_gen: B has " + std::to_string(d.M) + " rows, the matrix of the hierarchy " + std::to_string(n) +
+                "; both must have the same size.  A diagonal (lumped) B loses its rows to the boundary removal of assemble(): call "
+                "saena_matrix_set_remove_boundary(B, 0) before assembling it";
+        return -1;
+    }
+    d.halo_fp32 = 0;
+    if (gchk(sgpu_op_create(&d, &o))) return -2;
+    const int s = gchk(eigs_host_arrays(S->damg, n, x0_host, K, nev, max_iter, tol, precond, lambda, x_host, res, iters, o));
+    sgpu_op_destroy(o);
+    return s;
 }
 #endif
 

@@ -13,6 +13,8 @@
 //     source and Add.  It serves the Rayleigh-Ritz updates, both orthonormalisation steps and the start-up rotation.
 //   * k_eig_residual<K>: R = AX - X diag(lambda), lambda from device memory, and the partial sums of ||r_j||^2 in the same pass,
 //     in k_dot_block_partial's order (reduce with k_reduce_partials_block): the norms have the bits of the block dot of R with itself.
+//   * k_geig_residual<K>: the same for A x = lambda B x (sgpu_eigs_LOBPCG_gen): R = AX - BX diag(lambda), and ||r_j||^2 and
+//     ||(BX)_j||^2 from one pass.
 #pragma once
 #include "kernels_block.hip.h"
 
@@ -135,6 +137,43 @@ __global__ __launch_bounds__(BLOCK) void k_eig_residual(const double *__restrict
     for (int j = 0; j < K; ++j) {
         const double t = block_sum(s[j], sh);
         if (threadIdx.x == 0) partial[(size_t)blockIdx.x * K + j] = t;
+    }
+}
+
+// the residual of the generalised problem (sgpu_geig.hip.inc): R = AX - BX diag(lambda) with the bits of k_eig_residual called with
+// BX in X's place, and in the same pass the partial sums of ||r_j||^2 (partial_r) AND of ||(BX)_j||^2 (partial_b), both in
+// k_dot_block_partial's order: the bits of the block dot of R with R and of BX with BX.  Launch it on the dot's grid;
+// partial_*[block * K + j].  It moves 24 n K bytes (two block vectors read, one written).
+template <int K>
+__global__ __launch_bounds__(BLOCK) void k_geig_residual(const double *__restrict__ ax, const double *__restrict__ bx, const double *__restrict__ lambda,
+                                                         double *__restrict__ r, size_t n, double *__restrict__ partial_r, double *__restrict__ partial_b) {
+    static_assert(K == 2 || K == 4 || K == 8, "K");
+    __shared__ double sh[BLOCK / 64];
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    double lam[K], s[K], sb[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { lam[j] = lambda[j]; s[j] = 0.0; sb[j] = 0.0; }
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        double av[K], bv[K];
+        block_load_row<K>(ax, i, av);
+        block_load_row<K>(bx, i, bv);
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            av[j] = av[j] - bv[j] * lam[j];
+            s[j] += av[j] * av[j];
+            sb[j] += bv[j] * bv[j];
+        }
+        block_store_row<K>(r, i, av);
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double t = block_sum(s[j], sh);
+        if (threadIdx.x == 0) partial_r[(size_t)blockIdx.x * K + j] = t;
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double t = block_sum(sb[j], sh);
+        if (threadIdx.x == 0) partial_b[(size_t)blockIdx.x * K + j] = t;
     }
 }
 

@@ -136,6 +136,38 @@ bool eig_ortho_factor(const double *G, int K, const std::vector<int> &act, doubl
     return true;
 }
 
+// The Rayleigh-Ritz step on the host, shared by the standard and the generalised solve: from the downloaded Gram blocks (hgram;
+// slotS[a][b] / slotA[a][b], a <= b < nb3: the slots of S_a^T (B) S_b and S_a^T A S_b) the two matrices of order m = K + na (nb3 - 1)
+// over X and the active columns of W (and P) -- the lower block triangle mirrored, both symmetrised --, the dense generalised problem,
+// and the K smallest Ritz vectors scattered into E.hmix as C_X | C_W | C_P (rows of inactive columns zero).
+// -> dense_sym_geig's status (< 0: no coefficients were written); theta[0 .. m) ascending
+int eig_rayleigh_ritz(AmgEig &E, const double *hgram, const int (&slotS)[3][3], const int (&slotA)[3][3], int nb3, const std::vector<int> &act,
+                      double *theta, int *m_out) {
+    const int K = E.K, KK = K * K, na = (int)act.size();
+    const int m = K + na * (nb3 - 1);
+    *m_out = m;
+    std::vector<int> blk((size_t)m), col((size_t)m);
+    for (int i = 0; i < K; ++i) { blk[(size_t)i] = 0; col[(size_t)i] = i; }
+    for (int b = 1; b < nb3; ++b)
+        for (int i = 0; i < na; ++i) { blk[(size_t)(K + (b - 1) * na + i)] = b; col[(size_t)(K + (b - 1) * na + i)] = act[(size_t)i]; }
+    std::vector<double> GS((size_t)m * m), GA((size_t)m * m), Vm((size_t)m * m);
+    auto entry = [&](const int (&slot)[3][3], int i, int j) {
+        const int bi = blk[(size_t)i], bj = blk[(size_t)j];
+        return bi <= bj ? hgram[slot[bi][bj] * KK + col[(size_t)i] * K + col[(size_t)j]] : hgram[slot[bj][bi] * KK + col[(size_t)j] * K + col[(size_t)i]];
+    };
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) {
+            GS[(size_t)i * m + j] = 0.5 * (entry(slotS, i, j) + entry(slotS, j, i));
+            GA[(size_t)i * m + j] = 0.5 * (entry(slotA, i, j) + entry(slotA, j, i));
+        }
+    const int st = saena_host::dense_sym_geig(m, GA.data(), GS.data(), theta, Vm.data());
+    if (st < 0) return st;
+    std::fill(E.hmix.get(), E.hmix + 3 * KK, 0.0);
+    for (int i = 0; i < m; ++i)
+        for (int b = 0; b < K; ++b) E.hmix[blk[(size_t)i] * KK + col[(size_t)i] * K + b] = Vm[(size_t)i * m + b];
+    return st;
+}
+
 } // namespace
 
 extern "C" {
@@ -169,15 +201,17 @@ int sgpu_debug_eig_residual(sgpu_amg *h, const value_t *AX, const value_t *X, co
     return eig_residual(*E, AX, X, lambda_dev, R, n, rr_dev);
 }
 
-// a copy of one of the solver's own block vectors after a solve (which: 0 AX, 1 R, 2 W, 3 AW, 4 P, 5 AP) into dst (device, n K doubles)
+// a copy of one of the solver's own block vectors after a solve (which: 0 AX, 1 R, 2 W, 3 AW, 4 P, 5 AP; after a generalised solve
+// also 6 BX, 7 BW, 8 BP) into dst (device, n K doubles)
 int sgpu_debug_eig_vector(sgpu_amg *h, int K, int which, value_t *dst) {
     CHK(need_ctx());
     if (!h || !dst) return fail(SGPU_ERR_ARG, "debug_eig_vector: null argument");
     CHK(block_check(nullptr, K, "debug_eig_vector"));
     AmgEig *E = h->eigs[block_slot(K)].get();
     if (!E) return fail(SGPU_ERR_STATE, "debug_eig_vector: no sgpu_eigs_LOBPCG has run on this hierarchy with K = %d", K);
-    if (which < 0 || which > 5) return fail(SGPU_ERR_ARG, "debug_eig_vector: which is 0 .. 5 (got %d)", which);
-    const double *src[6] = {E->AX, E->R, E->W, E->AW, E->P, E->AP};
+    if (which < 0 || which > 8) return fail(SGPU_ERR_ARG, "debug_eig_vector: which is 0 .. 8 (got %d)", which);
+    if (which > 5 && !E->gen) return fail(SGPU_ERR_STATE, "debug_eig_vector: no sgpu_eigs_LOBPCG_gen has run on this hierarchy with K = %d (which = %d is BX, BW or BP)", K, which);
+    const double *src[9] = {E->AX, E->R, E->W, E->AW, E->P, E->AP, E->BX, E->BW, E->BP};
     return sgpu_vec_copy(dst, src[which], (size_t)h->A[0]->M * K);
 }
 
@@ -356,30 +390,13 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
             for (int b = a; b < nb3; ++b) { slotA[a][b] = ns3; CHK(eig_gram_partial(E, Sv[a], ASv[b], n, ns3++)); }
         CHK(eig_gram_reduce(E, n, ns3, cgram));
         CHK(fetch(K + ns3 * KK));
-        const int m = K + na * (nb3 - 1);
-        std::vector<int> blk((size_t)m), col((size_t)m);
-        for (int i = 0; i < K; ++i) { blk[(size_t)i] = 0; col[(size_t)i] = i; }
-        for (int b = 1; b < nb3; ++b)
-            for (int i = 0; i < na; ++i) { blk[(size_t)(K + (b - 1) * na + i)] = b; col[(size_t)(K + (b - 1) * na + i)] = act[(size_t)i]; }
-        std::vector<double> GS((size_t)m * m), GA((size_t)m * m), Vm((size_t)m * m);
-        auto entry = [&](const int (&slot)[3][3], int i, int j) {
-            const int bi = blk[(size_t)i], bj = blk[(size_t)j];
-            return bi <= bj ? hgram[slot[bi][bj] * KK + col[(size_t)i] * K + col[(size_t)j]] : hgram[slot[bj][bi] * KK + col[(size_t)j] * K + col[(size_t)i]];
-        };
-        for (int i = 0; i < m; ++i)
-            for (int j = 0; j < m; ++j) {
-                GS[(size_t)i * m + j] = 0.5 * (entry(slotS, i, j) + entry(slotS, j, i));
-                GA[(size_t)i * m + j] = 0.5 * (entry(slotA, i, j) + entry(slotA, j, i));
-            }
-        const int st = saena_host::dense_sym_geig(m, GA.data(), GS.data(), theta, Vm.data());
+        int m = 0;
+        const int st = eig_rayleigh_ritz(E, hgram, slotS, slotA, nb3, act, theta, &m);
         if (st < 0)
             return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: breakdown at iteration %d: the Rayleigh-Ritz basis of %d vectors is %s", it + 1, m,
                         st == -1 ? "linearly dependent (S^T S is not numerically positive definite)" : "not finite");
         if (!(theta[0] > 0.0)) return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: a Ritz value is %g at iteration %d: the operator is not symmetric positive definite", theta[0], it + 1);
-        // C_X | C_W | C_P: the K smallest Ritz vectors; rows of inactive columns are zero
-        std::fill(E.hmix.get(), E.hmix + 3 * KK, 0.0);
-        for (int i = 0; i < m; ++i)
-            for (int b = 0; b < K; ++b) E.hmix[blk[(size_t)i] * KK + col[(size_t)i] * K + b] = Vm[(size_t)i * m + b];
+        // E.hmix holds C_X | C_W | C_P: the K smallest Ritz vectors; rows of inactive columns are zero
         CHK(send_mix(3));
         if (useP) {
             CHK(eig_mix(K, 2, E.W, cmix + KK, E.P, cmix + 2 * KK, E.P, cmix, nullptr, E.P, n));

@@ -3265,6 +3265,11 @@ struct AmgEig : CapturedGraph {
     PinArr<double> hmix, hlam, hdown;                // pinned: what goes up (coefficients, lambda), what comes down (norms, Gram blocks)
     uint64_t graph_gen = 0, block_gen = 0;
     int debug_stop = -1;                             // sgpu_debug_eig_stop: the iteration a test wants to look into
+    // A x = lambda B x (sgpu_geig.hip.inc): made at the first sgpu_eigs_LOBPCG_gen with this K, never by the standard solve
+    bool gen = false;
+    DevArr<double> BX, BW, BP;                       // B times X, W, P, carried
+    DevArr<double> bpart, bnrm;                      // ||(Bx)_j||^2: partial sums [n_partials][K], the K sums
+    PinArr<double> hbn;                              // pinned mirror of bnrm
 };
 
 struct sgpu_amg {
@@ -3916,6 +3921,7 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 #include "sgpu_block.hip.inc"
 #include "sgpu_gmres.hip.inc"
 #include "sgpu_eig.hip.inc"
+#include "sgpu_geig.hip.inc"
 #include "sgpu_lanczos.hip.inc"
 #include "sgpu_coarse_cg.hip.inc"
 

@@ -106,6 +106,7 @@ HOST_SYMBOLS.update({
     "saena_amg_solve_pCG_block": (C.c_int, [_VP, _PD, _PD, C.c_int, _PI, _PD, C.c_int]),
     "saena_amg_solve_pFGMRES": (C.c_int, [_VP, _PD, _PD, C.c_int, C.c_int, _PI, _PD, C.c_int]),
     "saena_amg_eigs": (C.c_int, [_VP, _PD, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PD, _PI]),
+    "saena_amg_eigs_gen": (C.c_int, [_VP, _VP, _PD, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PD, _PI]),
     "saena_debug_sym_geig": (C.c_int, [C.c_int, _PD, _PD, _PD, _PD]),
     "saena_debug_sym_geig_sweeps": (C.c_int, []),
 })
@@ -610,9 +611,11 @@ class AmgSolver:
             _check(self.L, st)
         return u, [int(v) for v in it], [h[~np.isnan(h)] for h in hist], st == 0
 
-    def eigs(self, K, nev, x0=None, max_iter=100, tol=1e-8, precond=True):
+    def eigs(self, K, nev, x0=None, max_iter=100, tol=1e-8, precond=True, B=None):
         """the nev smallest eigenpairs by LOBPCG on K = 2, 4 or 8 vectors (saena_amg_eigs); x0: (n, K) start vectors or None for the
-        default start -> (lambda[K], X (n, K), res[K], iterations, converged)"""
+        default start.  With B (an assembled Matrix of the same size) the generalised problem A x = lambda B x (saena_amg_eigs_gen):
+        X is B-orthonormal on return.  A lumped (diagonal) B is assembled after B.set_remove_boundary(False), or assemble() removes
+        its single-entry rows as boundary nodes -> (lambda[K], X (n, K), res[K], iterations, converged)"""
         n = self.A.num_local_rows
         p0 = None
         if x0 is not None:
@@ -621,8 +624,12 @@ class AmgSolver:
             p0 = x0.ctypes.data_as(_PD)
         X = np.zeros((n, K), order="F")
         lam, res, it = np.full(K, np.nan), np.full(K, np.nan), C.c_int()
-        st = self.L.saena_amg_eigs(self.h, p0, int(K), int(nev), int(max_iter), float(tol), 1 if precond else 0, lam.ctypes.data_as(_PD),
-                                   X.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it))
+        if B is None:
+            st = self.L.saena_amg_eigs(self.h, p0, int(K), int(nev), int(max_iter), float(tol), 1 if precond else 0, lam.ctypes.data_as(_PD),
+                                       X.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it))
+        else:
+            st = self.L.saena_amg_eigs_gen(self.h, B.h, p0, int(K), int(nev), int(max_iter), float(tol), 1 if precond else 0,
+                                           lam.ctypes.data_as(_PD), X.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it))
         if st not in (0, -6):
             _check(self.L, st)
         return lam, X, res, it.value, st == 0
