@@ -23,6 +23,11 @@ BIG_TRI = 262401             # the partial sums take a second grid-stride trip (
 EARLY_OUT_CASES = (("tri", 1025),)
 CAPPED_CASES = (("tri", 1300), ("band17", 1300))         # CG_coarsest_max_iter = 6
 CAP = 6
+# the smallest caps: 1 is k_dcg_setup's own branch (count 0, 2 launches, no iteration), 2 is k_dcg_dir's `it + 1 == max_iter` rule at its
+# first iteration, 3 and 7 are odd (the last iteration reads the dot's slot 0 / writes slot 1, the reverse of cap 6)
+CAPS = (1, 2, 3, 7)
+CAPS_CASES = (("tri", 1300), ("band17", 1300))
+CAPS_COUNT = {1: 0, 2: 1, 3: 2, 7: 6}                    # solve_coarsest_CG's `i--`: cap - 1 updates, reported as cap - 1
 SMALL_SIZES = (257, 1024)    # at most CG_MAXN rows: value 2 runs k_coarse_cg, value 0's bits
 SET_OPERATOR = (("tri", 1300), ("band17", 1300))
 TWO_LEVEL = (2600, 2)        # solver_ref.tri_two_level: 1 300 coarse rows
@@ -58,6 +63,37 @@ def case(family, n):
             a.setflags(write=False)
         _cache[(family, n)] = dict(A=A, dense=D, rhs=b, x=x, resid=resid, cond=float(np.linalg.cond(D)))
     return _cache[(family, n)]
+
+
+def sparse_case(A, rhs):
+    """a case dict for check_contracts of a symmetric scipy matrix too large for solver_ref.case's dense algebra (a coarsest level
+    of thousands of rows): x by a sparse LU and three rounds of refinement on a longdouble residual -- solve_hp's scheme --, cond as
+    max |lambda| / min |lambda|, which is the 2-norm condition number np.linalg.cond gives for a symmetric matrix, definite or not.
+    The asymmetry rounding leaves in a Galerkin product is checked to be far below min |lambda|.  eig_ends: the smallest
+    eigenvalue, the one nearest zero, the largest."""
+    import scipy.sparse.linalg as sla
+    A = A.tocsr()
+    rhs = np.asarray(rhs, np.float64)
+    lu = sla.splu(A.tocsc())
+    x = lu.solve(rhs).astype(np.longdouble)
+    Al, idx, bl = A.data.astype(np.longdouble), A.indices, rhs.astype(np.longdouble)
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+
+    def resid(x):
+        Ax = np.zeros(A.shape[0], np.longdouble)
+        np.add.at(Ax, rows, Al * x[idx])
+        return bl - Ax
+    for _ in range(3):
+        x = x + lu.solve(resid(x).astype(np.float64)).astype(np.longdouble)
+    r = resid(x)
+    Asym = ((A + A.T) * 0.5).tocsc()
+    asym = float(abs(A - A.T).sum(axis=1).max())                                  # the infinity norm bounds the 2-norm
+    ends = [float(sla.eigsh(Asym, k=1, which=w, return_eigenvectors=False, tol=1e-10)[0]) for w in ("LA", "SA")]
+    near0 = float(sla.eigsh(Asym, k=1, sigma=0.0, which="LM", return_eigenvectors=False, tol=1e-10)[0])
+    lmax, lmin = max(abs(e) for e in ends), abs(near0)
+    assert lmin > 0.0 and asym <= 1e-10 * lmin, (lmin, asym)
+    return dict(A=A, rhs=rhs, x=x.astype(np.float64), resid=float(np.sqrt(np.sum(r * r)) / np.sqrt(np.sum(bl * bl))), cond=lmax / lmin,
+                eig_ends=(ends[1], near0, ends[0]))
 
 
 def check_contracts(c, u, it, u_o, it_o):

@@ -57,6 +57,28 @@ def test_the_cap(case):
     assert sr.rel(u_o, c["x"]) > 1e-6                                    # (the cap ended it, not the tolerance)
 
 
+@pytest.mark.parametrize("cap", dr.CAPS)
+@pytest.mark.parametrize("case", dr.CAPS_CASES, ids=IDS)
+def test_the_smallest_and_the_odd_caps(case, cap):
+    """caps 1, 2, 3 and 7 past 1 024 rows: coarsest_cg's count (cap - 1: the cap ended it), its iterate, every launch of the sequence
+    at work; at cap 1 nothing touches u, a -0.0 included"""
+    c = dr.case(*case)
+    n = case[1]
+    u0 = np.linspace(-1.0, 1.0, n)
+    u0[0] = -0.0
+    u_o, it_o = sr.coarsest_cg(c["A"], c["rhs"], u0, max_iter=cap)
+    u, it, worked = dr.device_cg(c["A"], c["rhs"], u0, max_iter=cap)
+    print(f"cap {cap}: it {it} (coarsest_cg {it_o}), {worked} launches, rel {sr.rel(u, u_o):.2e}")
+    assert it == it_o == dr.CAPS_COUNT[cap]
+    assert worked == dr.launches(cap) == 2 + 3 * (cap - 1)
+    assert sr.rel(u, u_o) <= dr.REL_ORACLE
+    if cap == 1:
+        assert np.array_equal(u.view(np.uint64), u0.view(np.uint64)) and np.array_equal(u_o.view(np.uint64), u0.view(np.uint64))
+    else:
+        assert not np.array_equal(u, u0)
+        assert sr.rel(sr.coarsest_cg(c["A"], c["rhs"], max_iter=cap)[0], c["x"]) > 1e-6      # (the cap ended it, not the tolerance)
+
+
 @pytest.mark.parametrize("max_iter", [0, 1, 2, 3])
 def test_the_count_at_the_smallest_caps(max_iter):
     """solve_coarsest_CG's convention where the loop runs not at all, or once"""

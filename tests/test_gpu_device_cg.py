@@ -5,7 +5,8 @@ the solve phase to the host, so the V-cycle is one captured graph and the block,
 Cases, the numpy restatement and the restated bounds come from tests/device_cg_ref.py; tests/test_device_cg_ref.py shows on the CPU that
 the restatement stays inside every bound asserted here.  Shapes are the smallest at which the kernels can go wrong: 1 025 rows (the
 first size on the new path, a last workgroup that is not full) with 3, 17, 49 and 1 025 entries in a row (1, 4 and 16 lanes per row),
-1 100 dense rows (a wave per row), 262 401 rows (the partial sums' second grid-stride trip).
+1 100 dense rows (a wave per row), 262 401 rows (the partial sums' second grid-stride trip).  Caps: 150, 6, and 1, 2, 3, 7 -- the
+setup kernel's own branch, the cap rule at its first iteration, odd caps; sgpu_amg_create refuses no cap.
 """
 import numpy as np
 import pytest
@@ -105,6 +106,34 @@ def test_the_cap(capi, case):
     assert it == 5 and it_o == 5 and launches == dr.launches(dr.CAP) == 17
     assert sr.rel(u, u_o) <= dr.REL_ORACLE
     assert sr.rel(u_o, c["x"]) > 1e-6                           # (the cap ended it, not the tolerance)
+
+
+@pytest.mark.parametrize("cap", dr.CAPS)
+@pytest.mark.parametrize("case", dr.CAPS_CASES, ids=IDS)
+def test_the_smallest_and_the_odd_caps(capi, case, cap):
+    """CG_coarsest_max_iter = 1, 2, 3, 7 (sgpu_amg_create refuses none of them): the oracle's count 0, 1, 2, 6 and its iterate,
+    2, 5, 8, 20 launches.  At cap 1 no kernel touches u: a non-zero start keeps its bits.  A second solve on the same handle has the
+    first one's bits: no flag of a capped run outlives it"""
+    c = dr.case(*case)
+    n = case[1]
+    O, G, _ = one_level(capi, c["A"], "device_cg", cg_max_iter=cap)
+    u_o, it_o = O.coarsest_cg(c["rhs"])
+    u, it, launches = coarsest(capi, G, n, np.zeros(n), c["rhs"])
+    print(f"cap {cap}: it {it} (oracle {it_o}), {launches} launches, rel oracle {sr.rel(u, u_o) if cap > 1 else 0.0:.2e}")
+    assert it == it_o == dr.CAPS_COUNT[cap]
+    assert launches == dr.launches(cap) == 2 + 3 * (cap - 1)
+    if cap == 1:
+        assert not np.any(u) and not np.any(u_o)
+        u0 = inputs.v2(n)
+        u0[0] = -0.0
+        u1, it1, l1 = coarsest(capi, G, n, u0, c["rhs"])
+        assert it1 == 0 and l1 == 2
+        assert np.array_equal(bits(u1), bits(u0))
+    else:
+        assert sr.rel(u, u_o) <= dr.REL_ORACLE
+        assert sr.rel(u_o, c["x"]) > 1e-6                       # (the cap ended it, not the tolerance)
+    u2, it2, l2 = coarsest(capi, G, n, np.zeros(n), c["rhs"])
+    assert it2 == it and l2 == launches and np.array_equal(bits(u2), bits(u))
 
 
 @pytest.mark.parametrize("n", dr.SMALL_SIZES)

@@ -7,6 +7,8 @@ What is held, every comparison bit for bit unless a bound is named:
     sgpu_amg_set_operator, V-cycle and pCG history are those of a second device hierarchy built by hand from the updated host levels
     (level_layout -> sgpu_op_create -> sgpu_amg_create) -- both smoothers, both coarsest solvers; the refreshed dense inverse solves
     the NEW coarsest operator within tests/solver_ref.py's bound for the direct solve;
+  * the same through a hierarchy whose coarsest level takes the device-resident CG (coarse_solver = "device_cg", 5 324 rows): the
+    kept work space, a V-cycle captured again, the coarsest-CG contract on the new coarsest operator;
   * no captured graph survives an update: scalar V-cycle, block V-cycle, FGMRES and LOBPCG, each captured before the update, give the
     hand-built hierarchy's results after it -- compared while the old operators are still alive, so that a stale graph is a failed
     comparison and not a read of freed memory -- and the same again once the old operators are destroyed;
@@ -217,6 +219,68 @@ def test_an_update_through_set_operator_with_the_cg_coarsest_solver(capi, host, 
         same(a, b, f"mode {mode} {smoother}: {what}")
     assert got[3] == want[3] and not np.array_equal(got[0], before[0])
     check_coarsest(capi, G, S, direct=False)
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_saena_amg_update_under_the_device_cg(capi, host, mode, monkeypatch):
+    """coarse_solver = "device_cg" through saena_amg_update: Poisson 24^3 cut at max_level = 1, 5 324 coarse rows.  The update keeps
+    the device CG's work space, drops the captured V-cycles and captures again over the new coarsest operator.  Held: V-cycle, pCG
+    solution, history and count are those of a hand-built hierarchy over the refreshed levels under "device_cg", bit for bit (the
+    standard of the test above; SAENA_NO_AUTOTUNE for the same reason); they differ from the ones before the update; the second
+    V-cycle after the update is one launch; sgpu_coarsest_solve on the updated handle meets the four contracts of
+    tests/device_cg_ref.py on the coarsest operator the host now holds.  (update_ref.variant(A, "perturb") of this operator has one
+    negative eigenvalue, and so has its Galerkin product under mode 2: the condition number of the contracts is
+    max |lambda| / min |lambda|, and the numpy CG -- the oracle here -- converges on it as the kernels must.)"""
+    import scipy.sparse as sp
+    from tests import device_cg_ref as dr
+    from tests.test_gpu_solver_layer import Padded
+    monkeypatch.setenv("SAENA_NO_AUTOTUNE", "1")
+    L = host.load("gpu")
+    A = host.Matrix(host.Comm("gpu", "rccl")).laplacian3D(24).assemble()
+    S = host.AmgSolver(A, host.options(L, **dict(host.OPTIONS001, dynamic_levels=0, max_level=1)), coarse_solver="device_cg").to_device()
+    assert S.num_levels == 2 and S.level_info(1)["rows"] == 5324 > sr.CG_MAXN
+    n = A.num_local_rows
+    rhs = rhs_of(n)
+    G = device_view(capi, S)
+    before = run_scalar(capi, G, rhs)                       # one V-cycle, one pCG solve: their graphs are captured
+    du, drhs = capi.DeviceVector(n, np.zeros(n)), capi.DeviceVector(n, rhs)
+    G.vcycle(du, drhs)
+    l0 = capi.launch_count(); G.vcycle(du, drhs); replay = capi.launch_count() - l0
+    assert replay == 1
+    S.update(update_ref.matrix_from(*update_ref.variant(A, "perturb"), which="gpu", kind="rccl"), mode)
+    G = device_view(capi, S)
+    # recaptured: the first V-cycle on the vectors of the old graph launches the whole sequence, the second is one launch
+    du.upload(np.zeros(n))
+    l0 = capi.launch_count(); G.vcycle(du, drhs); first = capi.launch_count() - l0
+    v1 = du.download()
+    du.upload(np.zeros(n))
+    l0 = capi.launch_count(); G.vcycle(du, drhs); second = capi.launch_count() - l0
+    print(f"mode {mode}: first V-cycle after the update {first} launches, second {second}")
+    assert first > dr.launches(sr.CG_MAX_ITER), f"the first V-cycle after the update launched {first} times: it replayed a graph"
+    assert second == 1
+    same(du.download(), v1, f"mode {mode}: replay of the recaptured V-cycle")
+    G2, *_keep = hand_built(capi, S, "jacobi", "device_cg", pinned=False)
+    for mine, theirs in zip(G.A + G.P + G.R, G2.A + G2.P + G2.R):
+        assert (mine.variant(), mine.info()["lanes_per_row"]) == (theirs.variant(), theirs.info()["lanes_per_row"])
+    got, want = run_scalar(capi, G, rhs), run_scalar(capi, G2, rhs)
+    for a, b, what in zip(got, want, ("V-cycle", "pCG solution", "pCG history")):
+        same(a, b, f"mode {mode}: {what}")
+    print(f"mode {mode}: {got[3]} iterations (hand-built {want[3]}, before the update {before[3]})")
+    assert got[3] == want[3]
+    for a, b, what in zip(got, before, ("V-cycle", "pCG solution", "pCG history")):
+        assert not np.array_equal(a, b), f"mode {mode}: the update did not change the {what}"
+    # the coarsest solve of the updated handle, on the coarsest operator the host holds now, stored order kept
+    d = S.level_layout(1, 0)
+    nc = d["M"]
+    Ac = sp.csr_matrix((d["val_local"], d["col_local"], np.concatenate([[0], np.cumsum(d["nnzPerRow_local"])])), shape=(nc, nc))
+    c = dr.sparse_case(Ac, sr.rhs_for(nc))
+    assert c["resid"] <= 1e-15
+    u_o, it_o = sr.coarsest_cg(Ac, c["rhs"])
+    dcu, dcr = Padded(capi, np.zeros(nc)), capi.DeviceVector(nc, c["rhs"])
+    l0 = capi.launch_count(); it = G.coarsest_solve(dcu, dcr); launches = capi.launch_count() - l0
+    print(f"mode {mode}: coarsest operator cond {c['cond']:.4g}, eigenvalues {c['eig_ends']}, {launches} launches")
+    dr.check_contracts(c, dcu.head(), it, u_o, it_o)
+    assert launches == dr.launches(sr.CG_MAX_ITER)
 
 
 # ---- stale graphs -------------------------------------------------------------------------------------------------------
