@@ -306,6 +306,17 @@ public:
     // assembled after B.set_remove_boundary(false): assemble() otherwise takes every single-entry row for a boundary node and removes
     // it, and eigs_gen refuses the B that is left for its size, with a message that says so.
     int eigs_gen(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B, saena::options *opts, int K, int nev, const value_t *x0 = nullptr, bool precondition = true);
+    // More than K eigenpairs (sgpu_eigs_LOBPCG_many, one rank): the nev <= 64 smallest pairs of A x = lambda x, or of A x = lambda B x
+    // with B given, by sweeps of the block solve on K = 2, 4 or 8 vectors; converged vectors are locked and the block iterates in
+    // the B-orthogonal complement of what is locked.  A sweep asks for sweep_nev pairs (0: K / 2, half the block as guard vectors).
+    // opts->get_max_iter() caps the TOTAL iterations over all sweeps (the default of 100 is small for this: 20 pairs take about 70),
+    // opts->get_tol() is the tolerance as in eigs / eigs_gen.  x0: column-major size x K start vectors, or nullptr for generated ones.
+    // q (allocated size * nev when null) receives the eigenvectors, column-major, B-orthonormal, in ascending order of lambda;
+    // lambda and eig_residuals() are resized to the pairs found: nev, or fewer when the call returns 1 (the iterations ran out; the
+    // pairs found so far are valid).  last_iterations() is the total, eig_sweeps() the number of sweeps.
+    int eigs_many(value_t *&q, std::vector<value_t> &lambda, saena::options *opts, int nev, int K = 8, int sweep_nev = 0, saena::matrix *B = nullptr,
+                  const value_t *x0 = nullptr, bool precondition = true);
+    int eig_sweeps() const { return eig_sweeps_; }
     const std::vector<value_t> &eig_residuals() const { return eig_res_; }
     comm get_orig_comm();
 
@@ -341,7 +352,8 @@ private:
     std::vector<value_t> rhs_blk_;                 // set_rhs_block: column-major size x nrhs_
     int nrhs_ = 0;
     std::vector<std::vector<value_t>> hist_blk_;   // per column of the last solve_pCG_block
-    std::vector<value_t> eig_res_;                 // of the last eigs / eigs_gen
+    std::vector<value_t> eig_res_;                 // of the last eigs / eigs_gen / eigs_many
+    int eig_sweeps_ = 0;                           // of the last eigs_many
     int eigs_common(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B, saena::options *opts, int K, int nev, const value_t *x0,
                     bool precondition, const char *what);
     bool dynamic_levels_ = true;

@@ -221,6 +221,14 @@ int   saena_amg_eigs(saena_amg_h *S, const value_t *x0_host, int K, int nev, int
  * single-entry row for a boundary node and removes it; a B whose rows differ from A's is refused (-1) with a message that says so */
 int   saena_amg_eigs_gen(saena_amg_h *S, saena_matrix_h *B, const value_t *x0_host, int K, int nev, int max_iter, value_t tol, int precond,
                          value_t *lambda, value_t *x_host, value_t *res, int *iters);
+/* [GPU] more than K eigenpairs (sgpu_eigs_LOBPCG_many; one rank): the nev <= 64 smallest pairs of A x = lambda x (B NULL) or
+ * A x = lambda B x (B as in saena_amg_eigs_gen) by sweeps of the block solve on K = 2, 4 or 8 vectors with converged vectors locked.
+ * sweep_nev: pairs asked of one sweep, 1..K, or 0 for K / 2.  x0_host: column-major n x K start vectors, or NULL for generated ones.
+ * max_iter bounds the TOTAL iterations over all sweeps; *iters is that total, *sweeps the number of sweeps.  lambda[nev] ascending,
+ * q_host column-major n x nev (B-orthonormal), res[nev] (may be NULL) the recomputed residual norms at locking time; *nlocked pairs
+ * are written: nev, or fewer with SGPU_ERR_NOCONV (the pairs locked so far are valid) */
+int   saena_amg_eigs_many(saena_amg_h *S, saena_matrix_h *B, int nev, int K, int sweep_nev, const value_t *x0_host, int max_iter, value_t tol,
+                          int precond, value_t *lambda, value_t *q_host, value_t *res, int *iters, int *nlocked, int *sweeps);
 
 /* ---- tests: the dense generalised symmetric eigenproblem of the Rayleigh-Ritz step (host/dense_eig.cpp) ----
  * A v = w B v for symmetric A and symmetric positive definite B of order 1 <= n <= 24, row-major: w[n] ascending, V[i * n + k] =

@@ -406,6 +406,38 @@ int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, in
                          value_t *lambda /*[K] host*/, value_t *res /*[K] host: recomputed ||A x_j - lambda_j B x_j||*/, int *iters,
                          value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
 
+/* ---- LOBPCG with hard locking: more than K eigenpairs ---------------------------
+ * sgpu_eigs_LOBPCG_locked is the block solve above constrained to the B-orthogonal complement of `nlocked` <= 64 locked vectors: the
+ * standard problem with B = NULL, the generalised one otherwise.  The locked set is COLUMN-MAJOR on the device, column l at
+ * Q + l * ld, ld >= n and even; BQ (read only when B is given) holds B Q the same way.  The loop is the unconstrained one with two
+ * additions: X <- X - Q (Z^T X) twice before the start orthonormalisation, and W <- W - Q (Z^T W) once right after W = M R (Z = Q, or
+ * BQ); the convergence rule, soft locking, the recomputed norms at the end, the breakdown handling and the three host
+ * synchronisations per iteration are unchanged (the coefficients Z^T W never visit the host).  *leading (may be NULL): how many
+ * leading columns 0 .. leading-1 are converged on the recomputed norms; 0 when the solve ended without recomputing them.
+ * With nlocked = 0 no lock kernel is launched and X, lambda, res, iters, res_hist have the bits of sgpu_eigs_LOBPCG (B = NULL) or
+ * sgpu_eigs_LOBPCG_gen.  The V-cycle runs through the same captured graph; a locked call neither drops nor recaptures it.
+ * SGPU_ERR_ARG, besides what those two refuse: nlocked outside 0..64, ld < n or odd, a null Q with nlocked > 0, a null BQ with B given
+ * and nlocked > 0, n < nlocked + 3 K.
+ *
+ * sgpu_eigs_LOBPCG_many sweeps it: while fewer than nev (1..64) pairs are locked, a constrained solve for min(sweep_nev, nev - locked)
+ * pairs (1 <= sweep_nev <= K; 0: K / 2, half the block as guard vectors); ALL leading converged columns are locked (copied into Q,
+ * and their B x into an array the driver owns), the others stay in the block as the next start vectors, the freed columns are
+ * refilled from a deterministic generator on the device.  X0: K start columns (block vector, device), or NULL for generated ones.
+ * max_iter bounds the TOTAL iterations over all sweeps, *iters reports that total.  On return lambda[nev], res[nev] (may be NULL; the
+ * recomputed norms at locking time) and the columns of Q (device, nev columns of ld) are in ascending order of lambda (a stable sort;
+ * Q is permuted on the device) and Q is B-orthonormal.  There is no locking inside a sweep and no final Rayleigh-Ritz over Q.
+ * SGPU_ERR_NOCONV: max_iter ran out (or a sweep broke down); the *nlocked_out pairs locked so far are valid, sorted among themselves.
+ * SGPU_ERR_ARG: nev outside 1..64, sweep_nev outside 0..K, ld < n or odd, n < nev + 3 K, and what the block solves refuse.
+ * Work space: the lock partial sums and the coefficient buffer (about 4 MiB) are made at the first locked call and freed with the
+ * hierarchy; the driver's block, B Q and permutation copy are freed at return.  A process that calls neither allocates none of it. */
+int sgpu_eigs_LOBPCG_locked(sgpu_amg *h, sgpu_op *B /*or NULL*/, const value_t *Q, const value_t *BQ, size_t ld, int nlocked,
+                            value_t *X, int K, int nev, int max_iter, value_t tol, int precond,
+                            value_t *lambda /*[K] host*/, value_t *res /*[K] host*/, int *iters,
+                            value_t *res_hist /*[K][hist_cap]*/, int hist_cap, int *leading);
+int sgpu_eigs_LOBPCG_many(sgpu_amg *h, sgpu_op *B /*or NULL*/, value_t *Q /*device, nev columns of ld*/, size_t ld, int nev, int K,
+                          int sweep_nev, const value_t *X0 /*device block vector, or NULL*/, int max_iter, value_t tol, int precond,
+                          value_t *lambda /*[nev] host*/, value_t *res /*[nev] host*/, int *iters, int *nlocked_out, int *sweeps_out);
+
 /* ---- measurement -----------------------------------------------------------
  * Runs `reps` back-to-back launches of one kernel on the compute stream,
  * bracketed by hipEvents recorded on that same stream; *ms_per_launch is the

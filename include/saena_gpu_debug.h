@@ -153,6 +153,18 @@ int sgpu_debug_geig_residual(sgpu_amg *h, const value_t *AX, const value_t *BX, 
                              value_t *rr_dev, value_t *bb_dev);
 int sgpu_debug_time_geig(sgpu_amg *h, const value_t *AX, const value_t *BX, value_t *R, size_t n, int K, int reps, float *ms_per_run);
 
+/* tests (tests/test_gpu_eig_lock_kernels.py): the launch helpers of hard locking (sgpu_eigs_LOBPCG_locked) on the caller's device
+ * arrays.  Z and Q: L <= 64 column-major columns, column l at Z + l * ld, ld even and >= n; Y and W: block vectors, 16-byte aligned.
+ *   lock_gram: out_dev[l * K + b] = Z[:, l] . Y[:, b] (L K doubles), through the hierarchy's lock partial sums
+ *   lock_project: W <- W - Q C, C_dev (L x K, row-major) in device memory
+ *   block_refill: column col of X from the refill generator with this counter value
+ *   time_lock (tests/perf_eig_many.py): ms per run of `reps` back-to-back runs, kind 0: lock_gram of (Q, Y), 1: lock_project of Q
+ *   into Y with zero coefficients. */
+int sgpu_debug_lock_gram(sgpu_amg *h, const value_t *Z, size_t ld, int L, const value_t *Y, size_t n, int K, value_t *out_dev);
+int sgpu_debug_lock_project(const value_t *Q, size_t ld, const value_t *C_dev, int L, value_t *W, size_t n, int K);
+int sgpu_debug_block_refill(value_t *X, size_t n, int K, int col, unsigned counter);
+int sgpu_debug_time_lock(sgpu_amg *h, int kind, const value_t *Q, size_t ld, int L, value_t *Y, size_t n, int K, int reps, float *ms_per_run);
+
 /* tests (tests/test_gpu_lanczos.py): begin = 1 opens a capture on the compute stream (thread-local mode), begin = 0 ends it and
  * discards the graph -- for the entry points that must refuse to run inside a capture.  Nothing is launched in between by the tests. */
 int sgpu_debug_capture(int begin);

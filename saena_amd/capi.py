@@ -136,6 +136,14 @@ SYMBOLS = {
     "sgpu_debug_time_gs": (C.c_int, [C.c_int, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_eigs_LOBPCG": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PI, _PD, C.c_int]),
     "sgpu_eigs_LOBPCG_gen": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PI, _PD, C.c_int]),
+    "sgpu_eigs_LOBPCG_locked": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD,
+                                          _PI, _PD, C.c_int, _PI]),
+    "sgpu_eigs_LOBPCG_many": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_double, C.c_int, _PD, _PD, _PI, _PI,
+                                        _PI]),
+    "sgpu_debug_lock_gram": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t, C.c_int, _VP]),
+    "sgpu_debug_lock_project": (C.c_int, [_VP, C.c_size_t, _VP, C.c_int, _VP, C.c_size_t, C.c_int]),
+    "sgpu_debug_block_refill": (C.c_int, [_VP, C.c_size_t, C.c_int, C.c_int, C.c_uint]),
+    "sgpu_debug_time_lock": (C.c_int, [_VP, C.c_int, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_geig_residual": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP, _VP]),
     "sgpu_debug_time_geig": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "sgpu_debug_block_gram": (C.c_int, [_VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
@@ -701,6 +709,50 @@ class Amg:
             check(st)
         return lam, res, it.value, [h[~np.isnan(h)] for h in hist], st == 0
 
+    def lobpcg_locked(self, X, nev, Q=None, ld=None, nlocked=0, BQ=None, B=None, max_iter=100, tol=1e-8, precond=True, cap=512):
+        """sgpu_eigs_LOBPCG_locked: lobpcg() constrained to the B-orthogonal complement of the first nlocked columns of Q (anything
+        with .ptr: column-major on the device, column l at l * ld; BQ = B Q the same way, read when B is given)
+        -> (lambda[K], res[K], iterations, [history of column j], converged, leading)"""
+        K = X.K
+        lam, res, it, lead = np.full(K, np.nan), np.full(K, np.nan), C.c_int(), C.c_int()
+        hist = np.full((K, cap), np.nan)
+        st = lib().sgpu_eigs_LOBPCG_locked(self.h, B.h if B is not None else None, Q.ptr if Q is not None else None,
+                                           BQ.ptr if BQ is not None else None, int(ld), int(nlocked), X.ptr, K, int(nev), int(max_iter), float(tol),
+                                           1 if precond else 0, lam.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it),
+                                           hist.ctypes.data_as(_PD), cap, C.byref(lead))
+        if st not in (0, -6):
+            check(st)
+        return lam, res, it.value, [h[~np.isnan(h)] for h in hist], st == 0, lead.value
+
+    def lobpcg_many(self, n, nev, K, sweep_nev=0, X0=None, B=None, max_iter=400, tol=1e-8, precond=True, ld=None, nan_padding=False):
+        """sgpu_eigs_LOBPCG_many: the nev <= 64 smallest eigenpairs of the level-0 operator of n rows (of A x = lambda B x with B) by
+        sweeps of the locked block solve on K columns.  X0: a block vector of K start columns (anything with .ptr), or None for generated ones
+        -> (lambda[nlocked], res[nlocked], Q (n, nlocked) host array, total iterations, sweeps, converged)"""
+        n = int(n)
+        ld = int(ld) if ld is not None else n + (n & 1)
+        dQ = DeviceVector(max(1, nev * ld))
+        if nan_padding:
+            dQ.fill(float("nan"))
+        lam, res = np.full(nev, np.nan), np.full(nev, np.nan)
+        it, nl, sw = C.c_int(), C.c_int(), C.c_int()
+        st = lib().sgpu_eigs_LOBPCG_many(self.h, B.h if B is not None else None, dQ.ptr, ld, int(nev), int(K), int(sweep_nev),
+                                         X0.ptr if X0 is not None else None, int(max_iter), float(tol), 1 if precond else 0,
+                                         lam.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it), C.byref(nl), C.byref(sw))
+        if st not in (0, -6):
+            check(st)
+        L = nl.value
+        Q = dQ.download().reshape(nev, ld)[:L, :n].T.copy() if nev * ld else np.zeros((n, 0))
+        return lam[:L], res[:L], Q, it.value, sw.value, st == 0
+
+    # the launch helpers of hard locking on the caller's device arrays (sgpu_debug_lock_gram / _lock_project / _block_refill)
+    def debug_lock_gram(self, Z, ld, L, Y, n, K, out):
+        check(lib().sgpu_debug_lock_gram(self.h, Z.ptr, int(ld), int(L), Y.ptr, int(n), int(K), out.ptr))
+
+    def time_lock(self, kind, Q, ld, L, Y, n, K, reps):
+        ms = C.c_float()
+        check(lib().sgpu_debug_time_lock(self.h, int(kind), Q.ptr, int(ld), int(L), Y.ptr, int(n), int(K), int(reps), C.byref(ms)))
+        return ms.value
+
     # the LOBPCG launch helpers on the caller's device vectors (sgpu_debug_block_gram / _block_mix / _eig_residual)
     def debug_block_gram(self, X, Y, n, K, out):
         check(lib().sgpu_debug_block_gram(self.h, X.ptr, Y.ptr, int(n), int(K), out.ptr))
@@ -830,6 +882,16 @@ def live_bytes():
     st = lib().sgpu_debug_op_storage(None, C.byref(m), C.byref(b))
     check(st)
     return b.value
+
+
+def lock_project(K, Q, ld, Cm, L, W, n):
+    """W <- W - Q C on a block vector of n rows (sgpu_debug_lock_project); Q: L column-major columns of ld, Cm: device, L x K"""
+    check(lib().sgpu_debug_lock_project(Q.ptr, int(ld), Cm.ptr, int(L), W.ptr, int(n), int(K)))
+
+
+def block_refill(X, n, K, col, counter):
+    """column col of the block vector X from the refill generator (sgpu_debug_block_refill)"""
+    check(lib().sgpu_debug_block_refill(X.ptr, int(n), int(K), int(col), int(counter)))
 
 
 def launch_count():

@@ -48,6 +48,33 @@ inline int eigs_host_arrays(sgpu_amg *h, size_t n, const value_t *x0_host, int K
     sgpu_vec_free(cm); sgpu_vec_free(x);
     return s;
 }
+
+// what saena_amg_eigs_many and saena::amg::eigs_many share: x0_host (column-major n x K, or null: the driver generates its start block
+// on the device) up and packed, sgpu_eigs_LOBPCG_many on a device Q of nev columns (leading dimension n rounded up to even), and the
+// *nlocked columns it locked back into q_host (column-major n x nev; the columns past *nlocked are not written).
+// -> the sgpu status (SGPU_ERR_NOCONV: lambda, res and q_host hold the *nlocked pairs locked so far)
+inline int eigs_many_host_arrays(sgpu_amg *h, size_t n, sgpu_op *B, int nev, int K, int sweep_nev, const value_t *x0_host, int max_iter, value_t tol,
+                                 int precond, value_t *lambda, value_t *q_host, value_t *res, int *iters, int *nlocked, int *sweeps) {
+    const size_t ld = n + (n & 1);
+    int locked = 0;
+    value_t *cm = nullptr, *x = nullptr, *q = nullptr;
+    int s = sgpu_vec_alloc(&q, ld * (size_t)(nev > 0 ? nev : 1));
+    if (s == SGPU_OK && x0_host && (K == 2 || K == 4 || K == 8)) {
+        s = sgpu_vec_alloc(&cm, n * K);
+        if (s == SGPU_OK) s = sgpu_vec_alloc(&x, n * K);
+        if (s == SGPU_OK) s = sgpu_vec_upload(cm, x0_host, n * K);
+        if (s == SGPU_OK) s = sgpu_block_pack(cm, x, n, K);
+    }
+    if (s == SGPU_OK) s = sgpu_eigs_LOBPCG_many(h, B, q, ld, nev, K, sweep_nev, x, max_iter, tol, precond, lambda, res, iters, &locked, sweeps);
+    if (s == SGPU_OK || s == SGPU_ERR_NOCONV)
+        for (int l = 0; l < locked; ++l) {
+            const int s2 = sgpu_vec_download(q_host + (size_t)l * n, q + (size_t)l * ld, n);
+            if (s2 != SGPU_OK) { s = s2; break; }
+        }
+    if (nlocked) *nlocked = locked;
+    sgpu_vec_free(cm); sgpu_vec_free(x); sgpu_vec_free(q);
+    return s;
+}
 #endif
 
 } // namespace saena_host

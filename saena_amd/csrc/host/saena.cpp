@@ -501,6 +501,35 @@ int amg::eigs_common(value_t *&x, std::vector<value_t> &lambda, saena::matrix *B
     if (st != SGPU_OK && st != SGPU_ERR_NOCONV) gchk(st, B ? "eigs_gen" : "eigs");
     return st == SGPU_OK ? 0 : 1;
 }
+// sgpu_eigs_LOBPCG_many on column-major host arrays (host/eigs_device.h, shared with saena_amg_eigs_many)
+int amg::eigs_many(value_t *&q, std::vector<value_t> &lambda, saena::options *opts, int nev, int K, int sweep_nev, saena::matrix *B, const value_t *x0,
+                   bool precondition) {
+    if (!damg_) throw std::runtime_error("saena::amg: set_matrix first");
+    if (K != 2 && K != 4 && K != 8) throw std::runtime_error("saena::amg::eigs_many: a block holds 2, 4 or 8 vectors");
+    if (nev < 1 || nev > 64) throw std::runtime_error("saena::amg::eigs_many: nev must be in 1..64");
+    const size_t n = (size_t)A_->get_num_local_rows();
+    if (B && (size_t)B->get_num_local_rows() != n)
+        throw std::runtime_error("saena::amg::eigs_many: B has " + std::to_string(B->get_num_local_rows()) + " rows, the matrix of set_matrix " +
+                                 std::to_string(n) + "; both must have the same size.  A diagonal (lumped) B loses its rows to the boundary removal of "
+                                 "assemble(): call B.set_remove_boundary(false) before assembling it");
+    int max_iter = 100;
+    double tol = 1e-8;
+    if (opts) {
+        gchk(sgpu_amg_set_solve_params(damg_, opts->get_max_iter(), opts->get_tol(), opts->get_smoother() == "jacobi" ? 0 : 1,
+                                       opts->get_preSmooth(), opts->get_postSmooth()), "set_solve_params");
+        max_iter = opts->get_max_iter(); tol = opts->get_tol();
+    }
+    lambda.assign((size_t)nev, 0.0);
+    eig_res_.assign((size_t)nev, 0.0);
+    if (!q) q = static_cast<value_t *>(std::malloc(std::max<size_t>(1, n * (size_t)nev) * sizeof(value_t)));
+    int locked = 0;
+    const int st = saena_host::eigs_many_host_arrays(damg_, n, B ? B->device_op() : nullptr, nev, K, sweep_nev, x0, max_iter, tol, precondition ? 1 : 0,
+                                                     lambda.data(), q, eig_res_.data(), &iters_, &locked, &eig_sweeps_);
+    if (st != SGPU_OK && st != SGPU_ERR_NOCONV) gchk(st, "eigs_many");
+    lambda.resize((size_t)locked);
+    eig_res_.resize((size_t)locked);
+    return st == SGPU_OK ? 0 : 1;
+}
 int amg::set_scale(bool sc) {
     if (sc) throw std::runtime_error("saena::amg::set_scale(true): symmetric scaling is not on the GPU path (false in the reference's drivers)");
     return 0;

@@ -383,6 +383,7 @@ int saena_amg_solve_pCG_block(saena_amg_h *, const value_t *, value_t *, int, in
 int saena_amg_solve_pFGMRES(saena_amg_h *, const value_t *, value_t *, int, int, int *, value_t *, int) { return no_gpu(); }
 int saena_amg_eigs(saena_amg_h *, const value_t *, int, int, int, value_t, int, value_t *, value_t *, value_t *, int *) { return no_gpu(); }
 int saena_amg_eigs_gen(saena_amg_h *, saena_matrix_h *, const value_t *, int, int, int, value_t, int, value_t *, value_t *, value_t *, int *) { return no_gpu(); }
+int saena_amg_eigs_many(saena_amg_h *, saena_matrix_h *, int, int, int, const value_t *, int, value_t, int, value_t *, value_t *, value_t *, int *, int *, int *) { return no_gpu(); }
 #else
 static int gchk(int s) { if (s != 0) { h_err = sgpu_last_error(); } return s; }
 static void drop_device(saena_amg_h *S) {
@@ -567,6 +568,33 @@ int saena_amg_eigs_gen(saena_amg_h *S, saena_matrix_h *B, const value_t *x0_host
     if (gchk(sgpu_op_create(&d, &o))) return -2;
     const int s = gchk(eigs_host_arrays(S->damg, n, x0_host, K, nev, max_iter, tol, precond, lambda, x_host, res, iters, o));
     sgpu_op_destroy(o);
+    return s;
+}
+
+// sgpu_eigs_LOBPCG_many the same way (host/eigs_device.h, shared with saena::amg::eigs_many); B may be null: the standard problem
+int saena_amg_eigs_many(saena_amg_h *S, saena_matrix_h *B, int nev, int K, int sweep_nev, const value_t *x0_host, int max_iter, value_t tol,
+                        int precond, value_t *lambda, value_t *q_host, value_t *res, int *iters, int *nlocked, int *sweeps) {
+    if (nlocked) *nlocked = 0;
+    if (!S || !S->damg) { h_err = "saena_amg_to_device has not been called"; return -1; }
+    if (K != 2 && K != 4 && K != 8) { h_err = "saena_amg_eigs_many: a block holds 2, 4 or 8 columns"; return -1; }
+    if (nev < 1 || nev > 64) { h_err = "saena_amg_eigs_many: nev must be in 1..64"; return -1; }
+    if (!lambda || !q_host) { h_err = "saena_amg_eigs_many: null argument"; return -1; }
+    const size_t n = S->H.dist.empty() ? (size_t)S->H.levels[0].A->M : (size_t)S->H.dist[0].A.M;
+    sgpu_op *o = nullptr;
+    if (B) {
+        sgpu_op_desc d;
+        if (saena_matrix_get_desc(B, &d)) return -1;
+        if ((size_t)d.M != n) {
+            h_err = "saena_amg_eigs_many: B has " + std::to_string(d.M) + " rows, the matrix of the hierarchy " + std::to_string(n) +
+                    "; both must have the same size.  A diagonal (lumped) B loses its rows to the boundary removal of assemble(): call "
+                    "saena_matrix_set_remove_boundary(B, 0) before assembling it";
+            return -1;
+        }
+        d.halo_fp32 = 0;
+        if (gchk(sgpu_op_create(&d, &o))) return -2;
+    }
+    const int s = gchk(eigs_many_host_arrays(S->damg, n, o, nev, K, sweep_nev, x0_host, max_iter, tol, precond, lambda, q_host, res, iters, nlocked, sweeps));
+    if (o) sgpu_op_destroy(o);
     return s;
 }
 #endif

@@ -16,6 +16,12 @@
 // runs for a residual that only confirms convergence).
 namespace {
 
+// the locked set of a constrained solve (sgpu_eig_lock.hip.inc): L columns, column l at Q + l * ld; Z = Q for the standard problem,
+// B Q for the generalised one.  A null pointer or L = 0: no constraint, and neither lock kernel is launched
+struct EigLock { const double *Q, *Z; size_t ld; int L; };
+// V <- V - Q (Z^T V) on a block vector of n rows and K columns: the coefficients stay on the device, no host synchronisation
+int eig_lock_project(sgpu_amg *h, const EigLock &lk, double *V, size_t n, int K);
+
 // partial sums of G = X^T Y into Gram slot `slot`
 int eig_gram_partial(AmgEig &E, const double *X, const double *Y, size_t n, int slot) {
     const int nb = dot_nblocks(n), K = E.K;
@@ -250,8 +256,11 @@ int sgpu_debug_time_eig(sgpu_amg *h, int kind, int ns, const value_t *X, const v
     return SGPU_OK;
 }
 
-int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda, value_t *res, int *iters,
-                     value_t *res_hist, int hist_cap) {
+// sgpu_eigs_LOBPCG's loop, and with a locked set sgpu_eigs_LOBPCG_locked's: X is projected twice before the start orthonormalisation
+// and W once right after W = M R.  *leading (may be null): the leading columns converged on recomputed norms
+static int eig_lobpcg_run(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda, value_t *res, int *iters,
+                          value_t *res_hist, int hist_cap, const EigLock *lk, int *leading) {
+    if (leading) *leading = 0;
     CHK(need_ctx());
     if (!h || !X || !lambda) return fail(SGPU_ERR_ARG, "eigs_LOBPCG: null argument");
     CHK(lobpcg_check(h, K, "eigs_LOBPCG"));
@@ -288,6 +297,8 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
     std::vector<int> all((size_t)K);
     for (int j = 0; j < K; ++j) all[(size_t)j] = j;
 
+    const bool locked = lk && lk->L > 0;
+    if (locked) for (int pass = 0; pass < 2; ++pass) CHK(eig_lock_project(h, *lk, X, n, K));     // X <- X - Q (Z^T X), twice
     // ---- start: orthonormalise X, Rayleigh-Ritz on X alone ----
     CHK(eig_gram_partial(E, X, X, n, 0));
     CHK(eig_gram_reduce(E, n, 1, cgram));
@@ -323,6 +334,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
         CHK(eig_residual(E, E.AX, X, clam, E.R, n, cnrm));
         auto precondition_and_project = [&]() -> int {                 // W = M R and X^T W
             if (precond) CHK(eig_precondition(h, *Bp, E)); else CHK(sgpu_vec_copy(E.W, E.R, nK));
+            if (locked) CHK(eig_lock_project(h, *lk, E.W, n, K));
             CHK(eig_gram_partial(E, X, E.W, n, 0));
             return eig_gram_reduce(E, n, 1, cgram);
         };
@@ -342,6 +354,7 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
         if (!finite) return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: a residual norm is not finite at iteration %d", it);
         if (conv || it >= max_iter) {
             if (fresh_AX) {                    // these norms come from a recomputed AX: they decide
+                if (leading) *leading = act.empty() ? K : act[0];
                 if (conv) return SGPU_OK;
                 return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG: %d of the %d wanted pairs are above the tolerance after %d iterations", (int)std::count_if(act.begin(), act.end(), [&](int j) { return j < nev; }), nev, it);
             }
@@ -411,6 +424,11 @@ int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, valu
         hasP = true;
         ++it;
     }
+}
+
+int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda, value_t *res, int *iters,
+                     value_t *res_hist, int hist_cap) {
+    return eig_lobpcg_run(h, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, nullptr, nullptr);
 }
 
 } // extern "C"

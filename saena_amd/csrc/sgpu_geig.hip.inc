@@ -83,8 +83,10 @@ int sgpu_debug_time_geig(sgpu_amg *h, const value_t *AX, const value_t *BX, valu
     return SGPU_OK;
 }
 
-int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda,
-                         value_t *res, int *iters, value_t *res_hist, int hist_cap) {
+// sgpu_eigs_LOBPCG_gen's loop, and with a locked set (Z = B Q) sgpu_eigs_LOBPCG_locked's: see eig_lobpcg_run
+static int geig_lobpcg_run(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda,
+                           value_t *res, int *iters, value_t *res_hist, int hist_cap, const EigLock *lk, int *leading) {
+    if (leading) *leading = 0;
     CHK(need_ctx());
     if (!h || !X || !lambda) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_gen: null argument");
     if (!B) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_gen: B is null (sgpu_eigs_LOBPCG solves the standard problem)");
@@ -129,6 +131,8 @@ int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, in
     std::vector<int> all((size_t)K);
     for (int j = 0; j < K; ++j) all[(size_t)j] = j;
 
+    const bool locked = lk && lk->L > 0;
+    if (locked) for (int pass = 0; pass < 2; ++pass) CHK(eig_lock_project(h, *lk, X, n, K));     // X <- X - Q ((B Q)^T X), twice
     // ---- start: B-orthonormalise X, Rayleigh-Ritz on X alone (X^T B X = I: the standard dense problem) ----
     CHK(apply_B(X, E.BX));
     CHK(eig_gram_partial(E, X, E.BX, n, 0));
@@ -167,6 +171,7 @@ int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, in
         CHK(geig_residual(K, E.AX, E.BX, clam, E.R, n, E.rpart, E.bpart, cnrm, E.bnrm));
         auto precondition_and_project = [&]() -> int {                 // W = M R and (BX)^T W
             if (precond) CHK(eig_precondition(h, *Bp, E)); else CHK(sgpu_vec_copy(E.W, E.R, nK));
+            if (locked) CHK(eig_lock_project(h, *lk, E.W, n, K));
             CHK(eig_gram_partial(E, E.BX, E.W, n, 0));
             return eig_gram_reduce(E, n, 1, cgram);
         };
@@ -186,6 +191,7 @@ int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, in
         if (!finite) return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG_gen: a residual norm or ||B x_j|| is not finite at iteration %d", it);
         if (conv || it >= max_iter) {
             if (fresh_AX) {                    // these norms come from a recomputed AX and BX: they decide
+                if (leading) *leading = act.empty() ? K : act[0];
                 if (conv) return SGPU_OK;
                 return fail(SGPU_ERR_NOCONV, "eigs_LOBPCG_gen: %d of the %d wanted pairs are above the tolerance after %d iterations", (int)std::count_if(act.begin(), act.end(), [&](int j) { return j < nev; }), nev, it);
             }
@@ -257,6 +263,11 @@ int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, in
         hasP = true;
         ++it;
     }
+}
+
+int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda,
+                         value_t *res, int *iters, value_t *res_hist, int hist_cap) {
+    return geig_lobpcg_run(h, B, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, nullptr, nullptr);
 }
 
 } // extern "C"

@@ -11,6 +11,8 @@
 #include "kernels_block.hip.h"
 #include "kernels_gmres.hip.h"
 #include "kernels_eig.hip.h"
+#include "kernels_eig_lock.hip.h"
+#include "eig_lock_plan.h"
 #include "kernels_lanczos.hip.h"
 #include "kernels_coarse_cg.hip.h"
 #include "dispatch.h"
@@ -3272,6 +3274,13 @@ struct AmgEig : CapturedGraph {
     PinArr<double> hbn;                              // pinned mirror of bnrm
 };
 
+// what hard locking adds to LOBPCG (sgpu_eig_lock.hip.inc): made at the first locked solve with a locked column (or the first
+// sgpu_eigs_LOBPCG_many), never by the unconstrained solves; shared by every K
+struct AmgLock {
+    DevArr<double> part;                             // the lock Gram's partial sums: LOCK_MAX / LOCK_C passes of [n_partials][LOCK_C * 8]
+    DevArr<double> coef;                             // C = Z^T Y: LOCK_MAX * 8 doubles, device only
+};
+
 struct sgpu_amg {
     int nlevels = 0;
     std::vector<sgpu_op *> A, P, R;
@@ -3302,6 +3311,7 @@ struct sgpu_amg {
     std::unique_ptr<AmgBlock> blk[3];  // K = 2, 4, 8
     std::unique_ptr<AmgGmres> gm;      // sgpu_solve_FGMRES
     std::unique_ptr<AmgEig> eigs[3];   // sgpu_eigs_LOBPCG, K = 2, 4, 8
+    std::unique_ptr<AmgLock> lock;     // sgpu_eigs_LOBPCG_locked / _many
     void drop_graphs() {
         for (auto &b : blk) if (b) b->drop_graphs();
         if (gm) gm->drop_graph();
@@ -3922,6 +3932,7 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 #include "sgpu_gmres.hip.inc"
 #include "sgpu_eig.hip.inc"
 #include "sgpu_geig.hip.inc"
+#include "sgpu_eig_lock.hip.inc"
 #include "sgpu_lanczos.hip.inc"
 #include "sgpu_coarse_cg.hip.inc"
 

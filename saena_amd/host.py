@@ -107,6 +107,7 @@ HOST_SYMBOLS.update({
     "saena_amg_solve_pFGMRES": (C.c_int, [_VP, _PD, _PD, C.c_int, C.c_int, _PI, _PD, C.c_int]),
     "saena_amg_eigs": (C.c_int, [_VP, _PD, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PD, _PI]),
     "saena_amg_eigs_gen": (C.c_int, [_VP, _VP, _PD, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _PD, _PD, _PD, _PI]),
+    "saena_amg_eigs_many": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PD, C.c_int, C.c_double, C.c_int, _PD, _PD, _PD, _PI, _PI, _PI]),
     "saena_debug_sym_geig": (C.c_int, [C.c_int, _PD, _PD, _PD, _PD]),
     "saena_debug_sym_geig_sweeps": (C.c_int, []),
 })
@@ -633,6 +634,28 @@ class AmgSolver:
         if st not in (0, -6):
             _check(self.L, st)
         return lam, X, res, it.value, st == 0
+
+    def eigs_many(self, nev, K=8, sweep_nev=0, x0=None, max_iter=400, tol=1e-8, precond=True, B=None):
+        """more than K eigenpairs (saena_amg_eigs_many): the nev <= 64 smallest pairs of A x = lambda x, or of A x = lambda B x with B (an
+        assembled Matrix of the same size, as in eigs), by sweeps of LOBPCG on K = 2, 4 or 8 vectors with converged vectors locked; a
+        sweep asks for sweep_nev pairs (0: K / 2).  max_iter bounds the total over all sweeps; x0: (n, K) start vectors or None for
+        generated ones -> (lambda[found], Q (n, found), res[found], total iterations, sweeps, converged); found = nev when converged"""
+        n = self.A.num_local_rows
+        p0 = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, np.float64)
+            assert x0.shape == (n, K), x0.shape
+            p0 = x0.ctypes.data_as(_PD)
+        Q = np.zeros((n, max(1, nev)), order="F")
+        lam, res = np.full(max(1, nev), np.nan), np.full(max(1, nev), np.nan)
+        it, nl, sw = C.c_int(), C.c_int(), C.c_int()
+        st = self.L.saena_amg_eigs_many(self.h, B.h if B is not None else None, int(nev), int(K), int(sweep_nev), p0, int(max_iter), float(tol),
+                                        1 if precond else 0, lam.ctypes.data_as(_PD), Q.ctypes.data_as(_PD), res.ctypes.data_as(_PD), C.byref(it),
+                                        C.byref(nl), C.byref(sw))
+        if st not in (0, -6):
+            _check(self.L, st)
+        L = nl.value
+        return lam[:L], Q[:, :L], res[:L], it.value, sw.value, st == 0
 
     def free(self):
         if self.h:
