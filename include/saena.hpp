@@ -256,6 +256,14 @@ public:
     // the hierarchy.  Any other name throws.  SAENA_COARSE_SOLVER=direct|cg|device_cg in the environment, read by set_matrix,
     // overrides it for drivers compiled unchanged.
     void set_coarse_solver(const std::string &name);
+    // NOT in the reference, before set_matrix, one rank: "constant" tells the solver that the matrix annihilates constants (pure Neumann
+    // or periodic Poisson, a graph Laplacian; assemble it after matrix::set_remove_boundary(false)).  The solves then solve
+    // A u = rhs - mean(rhs) and return the solution of zero mean, whatever the mean of the right-hand side; eigs returns the nev
+    // smallest NONZERO eigenpairs (the constant vector is locked: the first is the Fiedler vector).  set_matrix throws when the matrix
+    // or the coarsest operator has max|A 1| / max|a_ii| > 1e-10 (a pinned row, a reaction term) or with more than one rank;
+    // solve_pFGMRES, eigs_gen and eigs_many throw on such a solver.  "none" (the default) is the solver as it always was; any other
+    // name throws.  Null spaces other than constants and nonsymmetric singular matrices are not covered.
+    void set_null_space(const std::string &name);
     int update1(saena::matrix *A_new);
     int update2(saena::matrix *A_new);
     int set_rhs(saena::vector &rhs);                          // note: this function copies the rhs
@@ -362,6 +370,7 @@ private:
     int max_level_override_ = -1;
     bool device_eig_ = false;
     int coarse_solver_ = 1;
+    int null_space_ = 0;
     void drop_device();
     int update(saena::matrix *A_new, int mode);
     // which: 0 solve, 1 solve_pCG, 2 solve_CG, 3 solve_smoother, 4 solve_pFGMRES (the only one that reads restart / precondition)

@@ -184,6 +184,13 @@ int   saena_amg_set_device_eig(saena_amg_h *S, int on);
  * the environment, read by saena_amg_to_device, overrides it for drivers compiled unchanged.  Exported like every other symbol
  * (host/exports.map hides the operator new wrappers only). */
 int   saena_amg_set_coarse_solver(saena_amg_h *S, const char *name);
+/* Before saena_amg_to_device, one rank: name "constant" makes the device hierarchy one that knows the constant null space
+ * (sgpu_amg_create_null_space with 1, include/saena_gpu.h): the solves solve A u = rhs - mean(rhs) and return the solution of zero
+ * mean; saena_amg_eigs returns the smallest nonzero pairs (the normalised constant vector is locked); saena_amg_eigs_gen,
+ * saena_amg_eigs_many and saena_amg_solve_pFGMRES pass the library's refusal through, and saena_amg_to_device its refusal of an
+ * operator that does not annihilate constants or of more than one rank.  "none" (the default) is the hierarchy as it always was; any
+ * other name is refused (-1).  Assemble such a matrix after saena_matrix_set_remove_boundary(A, 0). */
+int   saena_amg_set_null_space(saena_amg_h *S, const char *name);
 int   saena_amg_num_levels(saena_amg_h *S);                               /* max_level + 1 */
 /* coarse id of every fine row of `level` (the reference's `aggregate` after aggregate_index_update, src/saena_object_setup1.cpp:
  * 2103-2260); one-rank setups keep it, for the pins of the setup (tests/test_sa_pins.py).  out: rows of that level */

@@ -71,6 +71,12 @@ int sgpu_vec_copy(value_t *dst, const value_t *src, size_t n);
 int sgpu_vec_axpby(value_t a, const value_t *x, value_t b, value_t *y, size_t n);
 /* dotProduct (aux_functions.h:116-123): local dot on the GPU + all-reduce over ranks */
 int sgpu_dot(const value_t *x, const value_t *y, size_t n, value_t *out);
+/* y = x - mean(x) over n rows; y may be x.  The sum has sgpu_dot's order of summation (the dot of x with a vector of ones), one
+ * division forms the mean, one subtraction per row: three launches, no atomics, the same bits from call to call.  Without mean_host
+ * nothing comes down and the call can be captured; with it one host synchronisation returns the mean that was subtracted -- how a
+ * caller learns how inconsistent the right-hand side of a singular system is (sgpu_amg_create_null_space).  One rank: with more the
+ * mean would be this rank's alone, SGPU_ERR_ARG.  n = 0: nothing is launched, *mean_host = 0. */
+int sgpu_vec_center(const value_t *x, value_t *y, size_t n, value_t *mean_host /*may be NULL*/);
 
 /* ---- distributed sparse operator ----------------------------------------
  * One descriptor carries, for THIS rank, exactly the arrays the reference
@@ -272,8 +278,40 @@ int sgpu_amg_default_params(sgpu_amg_params *p);
 /* eig_max[l] = eig_max_of_invdiagXA of A[l] (only read for chebyshev; may be NULL) */
 int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *const *R,
                     const value_t *eig_max, const sgpu_amg_params *params, sgpu_amg **out);
+/* A hierarchy that knows its null space.  null_space 0 is sgpu_amg_create (which is this call with 0: every bit and every launch as
+ * before).  null_space 1, "constants": every level's operator is symmetric and annihilates the constant vector -- a pressure
+ * Poisson problem with Neumann or periodic boundaries, a graph Laplacian.  Such a hierarchy solves A u = rhs - mean(rhs) and returns
+ * the solution of zero mean, whatever the mean of rhs is (a caller learns it from sgpu_vec_center).  One rank, fp64.  The property is
+ * fixed for the life of the hierarchy: sgpu_amg_params does not change and there is no setter.
+ *   coarsest level, coarse_solver 1: the host stores the pseudo-inverse instead of the inverse -- the same Gauss-Jordan elimination
+ *     on A_c + (s / n) 1 1^T, s the mean of A_c's diagonal, then every column and then every row of the result centred -- and the
+ *     dense solve kernels run as they are, without an extra launch;
+ *   coarsest level, the CG solvers (coarse_solver 0 and 2, and 1's fallback past 1 024 rows): the coarse right-hand side is centred
+ *     first (three small launches; in the level's own buffer, or into a work vector where the right-hand side is the caller's).  CG
+ *     from a zero iterate stays in the complement of constants, so nothing is centred after it;
+ *   sgpu_solve, sgpu_solve_pCG, sgpu_solve_CG, sgpu_solve_smoother, sgpu_solve_pCG_block iterate on the centred right-hand side:
+ *     res_hist[0] = ||rhs - mean(rhs)|| and the threshold is relative to it; u is centred once before they return.  Nothing is
+ *     centred per iteration on level 0;
+ *   sgpu_vcycle and sgpu_vcycle_block centre only at the coarsest level: they are the preconditioner, not a solve of the singular
+ *     system, and return whatever mean the smoothers leave;
+ *   sgpu_solve_FGMRES is refused (SGPU_ERR_ARG, "symmetric solvers only"), as are sgpu_eigs_LOBPCG, sgpu_eigs_LOBPCG_gen and
+ *     sgpu_eigs_LOBPCG_many (lambda = 0 is in the spectrum).  sgpu_eigs_LOBPCG_locked is accepted and unchanged: with the normalised
+ *     constant vector as its one locked column it returns the smallest nonzero pairs;
+ *   sgpu_amg_set_operator repeats the check below for a new operator of level 0 or of the coarsest level and recomputes the
+ *     pseudo-inverse.
+ * Creation with 1 is refused with SGPU_ERR_ARG when the context has more than one rank ("one rank"), and when the operator of level 0
+ * or of the coarsest level has max_i |(A 1)_i| / max_i |a_ii| > 1e-10 (computed once through sgpu_spmv on a vector of ones and a
+ * download; the message names the level and the value).  The smoothed-aggregation setup keeps constants on every level to 1e-14; a
+ * pinned row or a reaction term is orders above the threshold.  Any other value of null_space is SGPU_ERR_ARG.  Not covered: more than
+ * one rank, null spaces other than constants (a disconnected graph passes the check above and is NOT detected), nonsymmetric singular operators, a right-hand side that is constant (zero after
+ * centring). */
+int sgpu_amg_create_null_space(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *const *R,
+                               const value_t *eig_max, const sgpu_amg_params *params, int null_space, sgpu_amg **out);
+/* kind: the null_space the hierarchy was created with (0 for sgpu_amg_create) */
+int sgpu_amg_get_null_space(const sgpu_amg *h, int *kind);
 int sgpu_amg_destroy(sgpu_amg *h);       /* does not destroy the operators */
-/* saena_object::vcycle (saena_object_solve.cpp:961-1431) on level 0 */
+/* saena_object::vcycle (saena_object_solve.cpp:961-1431) on level 0.  On a hierarchy created with null_space 1 only the coarsest
+ * solve is restricted to the complement of constants: neither rhs nor u is centred on level 0 */
 int sgpu_vcycle(sgpu_amg *h, value_t *u, const value_t *rhs);
 /* saena_object::solve (saena_object_solve.cpp:1883-2014): u is zeroed, then V-cycles until
  * ||r||^2 < ||r0||^2 tol^2.  res_hist[k] = ||r_k||, k = 0..iters (capacity hist_cap). */
@@ -324,6 +362,10 @@ int sgpu_coarsest_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters)
  * the block kernel reads the plain CSR arrays every operator keeps. */
 int sgpu_block_pack(const value_t *cols_colmajor, value_t *blk, size_t n, int K);
 int sgpu_block_unpack(const value_t *blk, value_t *cols_colmajor, size_t n, int K);
+/* sgpu_vec_center per column of an interleaved block vector: Y = X - the column means of X, Y may be X; column j gets the bits of
+ * sgpu_vec_center on that column alone.  Device only, capturable; one rank.  X and Y must be 16-byte aligned (what sgpu_vec_alloc
+ * returns is): the kernels move pairs of columns; anything else is SGPU_ERR_ARG. */
+int sgpu_block_center(const value_t *X, value_t *Y, size_t n, int K);
 /* lanes per row of the block kernel: 0 = from the operator's mean row length (the default), or 1, 4, 16, 64.
  * (sgpu_op_set_lanes_per_row steers the scalar forms and does not reach the block kernel, nor this the scalar forms.) */
 int sgpu_op_set_block_lanes(sgpu_op *op, int lanes);
@@ -335,7 +377,8 @@ int sgpu_chebyshev_block(sgpu_op *op, int iter, value_t eig_max, value_t *U, con
 int sgpu_prolong_correct_block(sgpu_op *P, const value_t *E_coarse, value_t *U, int K);
 /* sgpu_vcycle on K columns: the same steps on block vectors (work vectors made at the first call with this K, freed with
  * the hierarchy; with use_graph captured once per (U, RHS, K)).  A hierarchy whose coarsest level needs the host-driven CG
- * (more rows than the LDS-resident solvers hold) is refused with SGPU_ERR_ARG. */
+ * (more rows than the LDS-resident solvers hold) is refused with SGPU_ERR_ARG.  As sgpu_vcycle, a hierarchy created with
+ * null_space 1 centres only at the coarsest level (every column on its own). */
 int sgpu_vcycle_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K);
 /* sgpu_solve_pCG's recurrence on K columns in lockstep, every column with its own scalars and threshold.  A column stops
  * at the iteration at which its ||r||^2 drops below its own threshold and is not written again; iters[j] and

@@ -62,6 +62,8 @@ SYMBOLS = {
     "sgpu_vec_copy": (C.c_int, [_VP, _VP, C.c_size_t]),
     "sgpu_vec_axpby": (C.c_int, [C.c_double, _VP, C.c_double, _VP, C.c_size_t]),
     "sgpu_dot": (C.c_int, [_VP, _VP, C.c_size_t, _PD]),
+    "sgpu_vec_center": (C.c_int, [_VP, _VP, C.c_size_t, _PD]),
+    "sgpu_block_center": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int]),
     "sgpu_op_create": (C.c_int, [C.POINTER(OpDesc), C.POINTER(_VP)]),
     "sgpu_op_destroy": (C.c_int, [_VP]),
     "sgpu_op_info": (C.c_int, [_VP, _PI, _PI, C.POINTER(C.c_long), C.POINTER(C.c_long), _PI, _PI]),
@@ -96,6 +98,9 @@ SYMBOLS = {
     "sgpu_chebyshev_host": (C.c_int, [_VP, C.c_int, C.c_double, _PD, _PD]),
     "sgpu_amg_default_params": (C.c_int, [C.POINTER(AmgParams)]),
     "sgpu_amg_create": (C.c_int, [C.c_int, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), _PD, C.POINTER(AmgParams), C.POINTER(_VP)]),
+    "sgpu_amg_create_null_space": (C.c_int, [C.c_int, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), _PD, C.POINTER(AmgParams), C.c_int,
+                                             C.POINTER(_VP)]),
+    "sgpu_amg_get_null_space": (C.c_int, [_VP, _PI]),
     "sgpu_amg_destroy": (C.c_int, [_VP]),
     "sgpu_vcycle": (C.c_int, [_VP, _VP, _VP]),
     "sgpu_solve": (C.c_int, [_VP, _VP, _VP, _PI, _PD, C.c_int]),
@@ -594,11 +599,22 @@ def coarse_solver_code(name):
     return {"direct": 1, "device_cg": 2}.get(name, 0)
 
 
+def null_space_code(name):
+    """sgpu_amg_create_null_space's null_space of a name: "none" 0, "constant" 1; an int is passed through"""
+    if isinstance(name, str):
+        if name not in ("none", "constant"):
+            raise ValueError(f'null_space is "none" or "constant", not {name!r}')
+        return {"none": 0, "constant": 1}[name]
+    return int(name)
+
+
 class Amg:
     """sgpu_amg over Operators A[l], P[l], R[l]."""
 
     def __init__(self, A, P, R, eig_max=None, pre=3, post=3, smoother="jacobi", max_iter=100, tol=1e-8, use_graph=True, coarse_solver="direct",
-                 cg_max_iter=150, cg_tol=1e-12):
+                 cg_max_iter=150, cg_tol=1e-12, null_space=None):
+        """null_space: None / "none" -> sgpu_amg_create, as ever; "constant" -> sgpu_amg_create_null_space(..., 1, ...): the operators
+        annihilate constants, the solvers solve A u = rhs - mean(rhs) and return the solution of zero mean; an int is passed through"""
         self.A, self.P, self.R = list(A), list(P), list(R)
         n = len(A)
         prm = AmgParams()
@@ -616,8 +632,19 @@ class Amg:
         if eig_max is not None:
             eig = _ad(eig_max)
         h = _VP()
-        check(lib().sgpu_amg_create(n, HA, HP, HR, eig.ctypes.data_as(_PD) if eig is not None else None, C.byref(prm), C.byref(h)))
+        pe = eig.ctypes.data_as(_PD) if eig is not None else None
+        if null_space is None:
+            check(lib().sgpu_amg_create(n, HA, HP, HR, pe, C.byref(prm), C.byref(h)))
+        else:
+            check(lib().sgpu_amg_create_null_space(n, HA, HP, HR, pe, C.byref(prm), null_space_code(null_space), C.byref(h)))
         self.h = h
+
+    @property
+    def null_space(self):
+        """sgpu_amg_get_null_space: 0 none, 1 constants"""
+        k = C.c_int(-1)
+        check(lib().sgpu_amg_get_null_space(self.h, C.byref(k)))
+        return k.value
 
     def vcycle(self, u, rhs):
         check(lib().sgpu_vcycle(self.h, u.ptr, rhs.ptr))
@@ -898,6 +925,18 @@ def launch_count():
     n = C.c_long()
     check(lib().sgpu_debug_launch_count(C.byref(n)))
     return n.value
+
+
+def vec_center(x, y=None, want_mean=False):
+    """sgpu_vec_center: y = x - mean(x) on DeviceVectors (y None: in place) -> the mean that was subtracted when want_mean, else None"""
+    m = C.c_double(float("nan"))
+    check(lib().sgpu_vec_center(x.ptr, (x if y is None else y).ptr, x.n, C.byref(m) if want_mean else None))
+    return m.value if want_mean else None
+
+
+def block_center(X, Y=None):
+    """sgpu_block_center on BlockVectors (Y None: in place)"""
+    check(lib().sgpu_block_center(X.ptr, (X if Y is None else Y).ptr, X.n, X.K))
 
 
 def dot(x, y):

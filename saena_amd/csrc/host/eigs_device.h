@@ -4,6 +4,7 @@
 #pragma once
 #include "../../../include/saena_gpu.h"
 
+#include <cmath>
 #include <cstddef>
 #include <vector>
 
@@ -37,7 +38,19 @@ inline int eigs_host_arrays(sgpu_amg *h, size_t n, const value_t *x0_host, int K
     if (s == SGPU_OK) s = sgpu_vec_alloc(&x, n * K);
     if (s == SGPU_OK) s = sgpu_vec_upload(cm, x0_host, n * K);
     if (s == SGPU_OK) s = sgpu_block_pack(cm, x, n, K);
-    if (s == SGPU_OK)
+    // a hierarchy that knows the constant null space (set_null_space("constant")): lambda = 0 belongs to the spectrum, so the standard
+    // problem is solved with the normalised constant vector locked -- the nev smallest NONZERO pairs, the first of them the Fiedler
+    // vector.  The generalised problem passes the library's refusal through
+    int kind = 0;
+    if (s == SGPU_OK) s = sgpu_amg_get_null_space(h, &kind);
+    if (s == SGPU_OK && kind == 1 && !B && n > 0) {
+        value_t *q = nullptr;
+        const size_t ld = n + (n & 1);
+        s = sgpu_vec_alloc(&q, ld);
+        if (s == SGPU_OK) s = sgpu_vec_fill(q, 1.0 / std::sqrt((value_t)n), ld);
+        if (s == SGPU_OK) s = sgpu_eigs_LOBPCG_locked(h, nullptr, q, nullptr, ld, 1, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0, nullptr);
+        if (q) sgpu_vec_free(q);
+    } else if (s == SGPU_OK)
         s = B ? sgpu_eigs_LOBPCG_gen(h, B, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0)
               : sgpu_eigs_LOBPCG(h, x, K, nev, max_iter, tol, precond, lambda, res, iters, nullptr, 0);
     if (s == SGPU_OK || s == SGPU_ERR_NOCONV) {

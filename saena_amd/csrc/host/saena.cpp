@@ -252,6 +252,10 @@ void amg::set_coarse_solver(const std::string &name) {
     if (c < 0) throw std::runtime_error("saena::amg::set_coarse_solver: \"" + name + "\" is none of direct, cg, device_cg");
     coarse_solver_ = c;
 }
+void amg::set_null_space(const std::string &name) {
+    if (name != "none" && name != "constant") throw std::runtime_error("saena::amg::set_null_space: \"" + name + "\" is neither none nor constant");
+    null_space_ = name == "constant" ? 1 : 0;
+}
 int amg::set_verbose(bool v) { verbose = v; return 0; }
 int amg::set_multigrid_max_level(int m) { max_level_override_ = m; return 0; }
 int amg::get_num_levels() const { return H_ ? H_->max_level + 1 : 0; }
@@ -318,7 +322,8 @@ int amg::set_matrix(saena::matrix *A, saena::options *opts) {
     p.preSmooth = o.preSmooth; p.postSmooth = o.postSmooth; p.smoother = o.smoother == "jacobi" ? 0 : 1;
     p.solver_max_iter = o.solver_max_iter; p.solver_tol = o.relative_tol;
     p.coarse_solver = saena_host::coarse_solver_choice(coarse_solver_);
-    gchk(sgpu_amg_create(n, dA_.data(), dP_.data(), dR_.data(), eig.data(), &p, &damg_), "sgpu_amg_create");
+    // (null_space 1 on more than one rank: refused by the library, "one rank")
+    gchk(sgpu_amg_create_null_space(n, dA_.data(), dP_.data(), dR_.data(), eig.data(), &p, null_space_, &damg_), "sgpu_amg_create_null_space");
     if (verbose && A->get_comm().rank() == 0) {
         printf("_____________________________\n\nnumber of levels = << %d >> (the finest level is 0)\n", n - 1);
         for (int l = 0; l < n; ++l) printf("level %d: rows %d, nnz %ld\n", l, H_->level_rows(l), (long)H_->level_nnzA(l));

@@ -21,6 +21,7 @@ struct saena_amg_h {
     amg_hierarchy H;
     bool set = false;
     int coarse_solver = 1;                    // saena_amg_set_coarse_solver: what to_device passes to sgpu_amg_create
+    int null_space = 0;                       // saena_amg_set_null_space: 0 "none", 1 "constant" (sgpu_amg_create_null_space)
     // device side (libsaena_amd.so only)
     std::vector<sgpu_op *> dA, dP, dR;
     std::vector<double> deig;                 // eig_max of every dA, as the device hierarchy holds it
@@ -324,6 +325,14 @@ int saena_amg_set_coarse_solver(saena_amg_h *S, const char *name) {
     return 0;
 }
 
+int saena_amg_set_null_space(saena_amg_h *S, const char *name) {
+    if (!S || !name) { h_err = "saena_amg_set_null_space: null argument"; return -1; }
+    const std::string s(name);
+    if (s != "none" && s != "constant") { h_err = "saena_amg_set_null_space: \"" + s + "\" is neither none nor constant"; return -1; }
+    S->null_space = s == "constant" ? 1 : 0;
+    return 0;
+}
+
 int saena_amg_num_levels(saena_amg_h *S) { return S->set ? S->H.max_level + 1 : 0; }
 
 int saena_amg_level_split(saena_amg_h *S, int l, index_t *split_out) {
@@ -478,7 +487,8 @@ int saena_amg_to_device(saena_amg_h *S) {
     p.preSmooth = o.preSmooth; p.postSmooth = o.postSmooth; p.smoother = o.smoother == "jacobi" ? 0 : 1;
     p.solver_max_iter = o.solver_max_iter; p.solver_tol = o.relative_tol;
     p.coarse_solver = coarse_solver_choice(S->coarse_solver);
-    return gchk(sgpu_amg_create(n, S->dA.data(), S->dP.data(), S->dR.data(), S->deig.data(), &p, &S->damg));
+    // (null_space 1 on more than one rank: refused by the library, "one rank")
+    return gchk(sgpu_amg_create_null_space(n, S->dA.data(), S->dP.data(), S->dR.data(), S->deig.data(), &p, S->null_space, &S->damg));
 }
 
 sgpu_amg *saena_amg_device_handle(saena_amg_h *S) { return S->damg; }

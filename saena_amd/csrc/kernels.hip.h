@@ -2179,6 +2179,27 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_partials(const double *__restr
     if (threadIdx.x == 0) out[0] = t;
 }
 
+// Centring, y = x - mean(x): what a hierarchy that knows the constant null space (sgpu_amg_create_null_space, kind 1) puts in front
+// of its coarsest solve and around its Krylov loops.  Three launches -- k_sum_partial, k_reduce_partials, k_center -- without
+// atomics and without a host round trip: capturable, and the same bits from call to call.
+// partial[block] = the sum of the block's elements of x in k_dot_partial's order of summation (the dot of x with a vector of ones
+// without the multiply: x_i * 1.0 is x_i, bit for bit); launch it with the dot's grid
+__global__ __launch_bounds__(BLOCK) void k_sum_partial(const double *__restrict__ x, size_t n, double *__restrict__ partial) {
+    __shared__ double sh[BLOCK / 64];
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    double s = 0.0;
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) s += x[i];
+    const double t = block_sum(s, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+// y_i = x_i - S[0] / n: one division, then one subtraction per row.  y may be x (element i is read before it is written, by the
+// thread that writes it): no __restrict__
+__global__ __launch_bounds__(BLOCK) void k_center(const double *S, const double *x, double *y, size_t n) {
+    const double mean = S[0] / (double)n;
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) y[i] = x[i] - mean;
+}
+
 // ---------------------------------------------------------------------------
 // Coarsest-level CG (solve_coarsest_CG, saena_object_solve.cpp:14-114) as ONE
 // workgroup: the <= ~100-row system lives in LDS for the whole solve, so the

@@ -308,6 +308,43 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_partials_block(const double *_
     if (threadIdx.x == 0) out[j] = t;
 }
 
+// ---- centring per column (k_sum_partial / k_center on a block vector): partial[block * K + j] = the block's share of the sum of
+// column j, k_sum_partial's order, so that after k_reduce_partials_block column j has the bits of the scalar kernels on that
+// column alone; then y_ij = x_ij - S[j] / n.  Y may be X ----
+template <int K>
+__global__ __launch_bounds__(BLOCK) void k_sum_block_partial(const double *__restrict__ x, size_t n, double *__restrict__ partial) {
+    __shared__ double sh[BLOCK / 64];
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    double s[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) s[j] = 0.0;
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride)
+#pragma unroll
+        for (int h = 0; h < K / 2; ++h) {
+            const sk_d2v xv = *reinterpret_cast<const sk_d2v *>(x + i * K + 2 * h);
+            s[2 * h] += xv.x; s[2 * h + 1] += xv.y;
+        }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double t = block_sum(s[j], sh);
+        if (threadIdx.x == 0) partial[(size_t)blockIdx.x * K + j] = t;
+    }
+}
+template <int K>
+__global__ __launch_bounds__(BLOCK) void k_center_block(const double *S, const double *x, double *y, size_t n) {
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    double mean[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) mean[j] = S[j] / (double)n;
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride)
+#pragma unroll
+        for (int h = 0; h < K / 2; ++h) {
+            sk_d2v v = *reinterpret_cast<const sk_d2v *>(x + i * K + 2 * h);
+            v.x -= mean[2 * h]; v.y -= mean[2 * h + 1];
+            *reinterpret_cast<sk_d2v *>(y + i * K + 2 * h) = v;
+        }
+}
+
 // ---- the k_axpby_block family: per-column coefficients from device scalars, bit j of `active` = column j takes part;
 // a column that does not is neither read for writing nor written ----
 // pCG update (k_pcg_update_dev per column): alpha_j = num[j] / den[j]; u -= alpha p; r -= alpha h on the active columns;

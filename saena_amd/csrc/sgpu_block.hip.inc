@@ -280,6 +280,23 @@ int block_unpack(const double *blk, double *cols, size_t n, int K) {
     return SGPU_OK;
 }
 
+// Y = X - the column means of X, n rows of K interleaved columns (Y may be X): center_async per column -- the sums on the dot's grid,
+// one workgroup per column for the partial sums, the subtraction.  Column j gets the bits of the scalar kernels on that column alone
+int center_block_async(const double *X, double *Y, size_t n, int K) {
+    if (n == 0) return SGPU_OK;
+    const int nb = dot_nblocks(n), gd = grid_for(2 * n);
+    double *part = g.cblk, *S = g.cblk + (size_t)g.n_partials * 8;
+    if (K == 2) SGPU_LAUNCH(sk::k_sum_block_partial<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
+    else if (K == 4) SGPU_LAUNCH(sk::k_sum_block_partial<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
+    else SGPU_LAUNCH(sk::k_sum_block_partial<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
+    SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)part, nb, K, S, (1u << K) - 1u);
+    if (K == 2) SGPU_LAUNCH(sk::k_center_block<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
+    else if (K == 4) SGPU_LAUNCH(sk::k_center_block<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
+    else SGPU_LAUNCH(sk::k_center_block<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
 // ---- per-(hierarchy, K) state ----
 int amg_block(sgpu_amg *h, int K, AmgBlock **out) {
     const int slot = block_slot(K);
@@ -336,6 +353,8 @@ int coarse_solve_block(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, b
     double *crhs = B.cm, *cu = B.cm + (size_t)n * K;
     CHK(block_unpack(rhs, crhs, (size_t)n, K));
     if (u_zero) CHK(sgpu_vec_fill(cu, 0.0, (size_t)n * K)); else CHK(block_unpack(u, cu, (size_t)n, K));
+    // the constant null space: every unpacked column centred in place by the scalar kernels, as coarse_solve does for one column
+    if (h->null_space == 1) for (int j = 0; j < K; ++j) CHK(center_async(crhs + (size_t)j * n, crhs + (size_t)j * n, (size_t)n));
     // the device CG past CG_MAXN rows (coarse_solver == 2): the scalar solver again, so a column has the bits of its scalar solve
     const bool dev = h->coarse_device_cg && n > sk::CG_MAXN;
     for (int j = 0; j < K; ++j) CHK(dev ? coarse_cg_device(h, A, cu + (size_t)j * n, crhs + (size_t)j * n, nullptr)
@@ -583,6 +602,15 @@ int sgpu_block_unpack(const value_t *blk, value_t *cols_colmajor, size_t n, int 
     return block_unpack(blk, cols_colmajor, n, K);
 }
 
+int sgpu_block_center(const value_t *X, value_t *Y, size_t n, int K) {
+    CHK(need_ctx());
+    if (!X || !Y) return fail(SGPU_ERR_ARG, "sgpu_block_center: null argument");
+    CHK(block_check(nullptr, K, "block_center"));
+    if (((uintptr_t)X | (uintptr_t)Y) & 15u) return fail(SGPU_ERR_ARG, "sgpu_block_center: X and Y must be 16-byte aligned (the kernels move pairs of columns)");
+    if (g.nranks > 1) return fail(SGPU_ERR_ARG, "sgpu_block_center: the means are taken over this rank's rows; one rank only (this context has %d)", g.nranks);
+    return center_block_async(X, Y, n, K);
+}
+
 int sgpu_op_set_block_lanes(sgpu_op *op, int lanes) {
     if (!op) return fail(SGPU_ERR_ARG, "null op");
     if (lanes != 0 && lanes != 1 && lanes != 4 && lanes != 16 && lanes != 64) return fail(SGPU_ERR_ARG, "block lanes per row must be 0 (auto), 1, 4, 16 or 64 (got %d)", lanes);
@@ -675,6 +703,7 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
     };
     CHK(sgpu_vec_fill(U, 0.0, szK));
     { EpiArgs e; e.rhs = RHS; CHK(apply_block(A, sk::EPI_RESIDUAL, U, r, e, K)); }
+    if (h->null_space == 1) CHK(center_block_async(r, r, sz, K));        // r_0 = RHS - its column means; nothing is centred per iteration
     CHK(dot_block(B, r, r, sz, Srr, all));
     CHK(rank_sum_block(B, Srr, all));
     CHK(fetch(Srr));
@@ -716,6 +745,7 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
             std::swap(Sa, Sb);
         }
     }
+    if (h->null_space == 1) CHK(center_block_async(U, U, sz, K));    // every column: the solution of zero mean
     failed = active;                               // still above their thresholds at solver_max_iter
     if (iters) for (int j = 0; j < K; ++j) iters[j] = it[j];
     return failed ? SGPU_ERR_NOCONV : SGPU_OK;

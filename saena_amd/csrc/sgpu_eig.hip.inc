@@ -428,6 +428,7 @@ static int eig_lobpcg_run(sgpu_amg *h, value_t *X, int K, int nev, int max_iter,
 
 int sgpu_eigs_LOBPCG(sgpu_amg *h, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda, value_t *res, int *iters,
                      value_t *res_hist, int hist_cap) {
+    if (h && h->null_space == 1) return fail(SGPU_ERR_ARG, "eigs_LOBPCG: the hierarchy knows the constant null space, so lambda = 0 is in the spectrum and the unconstrained solve breaks down; lock the normalised constant vector and call sgpu_eigs_LOBPCG_locked");
     return eig_lobpcg_run(h, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, nullptr, nullptr);
 }
 

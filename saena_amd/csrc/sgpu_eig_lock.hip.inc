@@ -175,6 +175,7 @@ int sgpu_eigs_LOBPCG_many(sgpu_amg *h, sgpu_op *B, value_t *Q, size_t ld, int ne
     if (sweeps_out) *sweeps_out = 0;
     CHK(need_ctx());
     if (!h || !Q || !lambda) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_many: null argument");
+    if (h->null_space == 1) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_many: the hierarchy knows the constant null space, so lambda = 0 is in the spectrum and the unconstrained solve breaks down; lock the normalised constant vector and call sgpu_eigs_LOBPCG_locked");
     CHK(lobpcg_check(h, K, "eigs_LOBPCG_many"));
     if (nev < 1 || nev > eig_lock::MAX_LOCKED) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_many: nev must be in 1..%d (got %d)", eig_lock::MAX_LOCKED, nev);
     if (sweep_nev < 0 || sweep_nev > K) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_many: sweep_nev must be in 1..K, or 0 for the default K / 2 (sweep_nev = %d, K = %d)", sweep_nev, K);

@@ -267,6 +267,7 @@ static int geig_lobpcg_run(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, 
 
 int sgpu_eigs_LOBPCG_gen(sgpu_amg *h, sgpu_op *B, value_t *X, int K, int nev, int max_iter, value_t tol, int precond, value_t *lambda,
                          value_t *res, int *iters, value_t *res_hist, int hist_cap) {
+    if (h && h->null_space == 1) return fail(SGPU_ERR_ARG, "eigs_LOBPCG_gen: the hierarchy knows the constant null space, so lambda = 0 is in the spectrum and the unconstrained solve breaks down; lock the normalised constant vector and call sgpu_eigs_LOBPCG_locked");
     return geig_lobpcg_run(h, B, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, nullptr, nullptr);
 }
 

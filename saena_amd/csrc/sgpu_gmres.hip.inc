@@ -189,6 +189,7 @@ int sgpu_debug_time_gs(int kind, const value_t *V, size_t ld, int ncols, value_t
 int sgpu_solve_FGMRES(sgpu_amg *h, value_t *u, const value_t *rhs, int restart, int precond, int *iters, value_t *hist, int cap, value_t *true_res) {
     CHK(need_ctx());
     if (!h || !u || !rhs) return fail(SGPU_ERR_ARG, "null argument");
+    if (h->null_space == 1) return fail(SGPU_ERR_ARG, "solve_FGMRES: the hierarchy knows the constant null space; symmetric solvers only (a nonsymmetric operator's left null vector need not be constant): sgpu_solve_pCG, sgpu_solve_CG, sgpu_solve, sgpu_solve_smoother");
     if (restart < 1 || restart > 64) return fail(SGPU_ERR_ARG, "solve_FGMRES: the restart length must be in 1..64 (got %d)", restart);
     if (precond != 0 && precond != 1) return fail(SGPU_ERR_ARG, "solve_FGMRES: precond is 0 (none) or 1 (one V-cycle), got %d", precond);
     if (!gs_aligned(u)) return fail(SGPU_ERR_ARG, "solve_FGMRES: u must be 16-byte aligned");

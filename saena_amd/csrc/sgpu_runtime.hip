@@ -19,6 +19,7 @@
 #include "devmem.h"
 #include "forms.h"
 #include "xwin_plan.h"
+#include "coarse_pinv.h"
 #include "host/dense_eig.h"
 #include "host/comm.h"
 #include "host/par.h"
@@ -94,6 +95,7 @@ struct Ctx {
     hipStream_t cs = nullptr, hs = nullptr;
     ncclComm_t  comm = nullptr;
     double     *partials = nullptr;   // dot partial sums
+    double     *cblk = nullptr;       // sgpu_block_center / the block solves of a null-space hierarchy: [n_partials][8] partial sums, then 8 sums
     double     *dscalar = nullptr;    // device scalars (dot result)
     double     *hscalar = nullptr;    // pinned host mirror
     int        *dint = nullptr;       // device int scratch (coarse CG iterations, barrier)
@@ -2052,6 +2054,19 @@ int pcg_direction_dev(int ia, int ib, const double *z, double *p, size_t n) {
     return SGPU_OK;
 }
 
+// y = x - mean(x) over this rank's n rows (y may be x): the sum on the dot's grid into the dots' partial sums, S[CENTER_SLOT], then
+// the subtraction.  Three launches, nothing comes down.  Slot 3 is no solver's: sgpu_dot has 0, the Krylov loops 4..7, global_sum 8..
+constexpr int CENTER_SLOT = 3;
+int center_async(const double *x, double *y, size_t n) {
+    if (n == 0) return SGPU_OK;
+    const int nb = dot_nblocks(n);
+    SGPU_LAUNCH(sk::k_sum_partial, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, n, g.partials);
+    SGPU_LAUNCH(sk::k_reduce_partials, dim3(1), dim3(sk::BLOCK), 0, g.cs, g.partials, nb, g.dscalar + CENTER_SLOT);
+    SGPU_LAUNCH(sk::k_center, dim3(grid_for(2 * n)), dim3(sk::BLOCK), 0, g.cs, (const double *)(g.dscalar + CENTER_SLOT), x, y, n);
+    HIPCHK(hipGetLastError());
+    return SGPU_OK;
+}
+
 const double JACOBI_OMEGA_REF = (double)(float)(2.0 / 3);   // saena_matrix.h:182
 
 int global_sum(double *v, int n) {
@@ -2162,6 +2177,7 @@ int sgpu_init(int device_id, int rank, int nranks, const void *uid) {
         HIPCHK(hipStreamCreateWithPriority(&g.hs, hipStreamNonBlocking, prio));
     }
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&g.partials), g.n_partials * sizeof(double)));
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&g.cblk), ((size_t)g.n_partials + 1) * 8 * sizeof(double)));
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&g.dscalar), 16 * sizeof(double)));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&g.hscalar), 16 * sizeof(double), hipHostMallocDefault));
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&g.dint), 16 * sizeof(int)));
@@ -2218,7 +2234,7 @@ int sgpu_finalize(void) {
     hipDeviceSynchronize();
     if (g.comm) { ncclCommDestroy(g.comm); g.comm = nullptr; }
     if (g.tk0) { hipEventDestroy(g.tk0); hipEventDestroy(g.tk1); g.tk0 = g.tk1 = nullptr; }
-    hipFree(g.partials); hipFree(g.dscalar); hipHostFree(g.hscalar); hipFree(g.dint); hipHostFree(g.hint);
+    hipFree(g.partials); hipFree(g.cblk); hipFree(g.dscalar); hipHostFree(g.hscalar); hipFree(g.dint); hipHostFree(g.hint);
     if (g.flag_x) hipFree(g.flag_x);
     if (g.flag_h) hipFree(g.flag_h);
     if (g.kflag_x) hipFree(g.kflag_x);
@@ -2298,6 +2314,19 @@ int sgpu_dot(const value_t *x, const value_t *y, size_t n, value_t *out) {
     HIPCHK(hipStreamSynchronize(g.cs));
     if (g.xchg) CHK(host_allreduce(g.hscalar, 1));
     *out = g.hscalar[0];
+    return SGPU_OK;
+}
+int sgpu_vec_center(const value_t *x, value_t *y, size_t n, value_t *mean_host) {
+    CHK(need_ctx());
+    if (!x || !y) return fail(SGPU_ERR_ARG, "sgpu_vec_center: null argument");
+    if (g.nranks > 1) return fail(SGPU_ERR_ARG, "sgpu_vec_center: the mean is taken over this rank's rows; one rank only (this context has %d)", g.nranks);
+    if (n == 0) { if (mean_host) *mean_host = 0.0; return SGPU_OK; }
+    CHK(center_async(x, y, n));
+    if (mean_host) {
+        HIPCHK(hipMemcpyAsync(g.hscalar + CENTER_SLOT, g.dscalar + CENTER_SLOT, sizeof(double), hipMemcpyDeviceToHost, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
+        *mean_host = g.hscalar[CENTER_SLOT] / (double)n;       // k_center's division
+    }
     return SGPU_OK;
 }
 
@@ -3293,6 +3322,11 @@ struct sgpu_amg {
     DevArr<double> r, rho, hh, p;
     DevArr<double> Ainv;      // dense inverse of the coarsest operator (coarse_solver == 1)
     bool coarse_local = true; // the coarsest operator has no halo on any rank
+    // sgpu_amg_create_null_space: 0 none; 1 every level's operator annihilates constants.  Under 1 Ainv holds the pseudo-inverse, the CG
+    // coarsest solvers get a centred right-hand side, and the solvers iterate on the centred right-hand side and centre u at the end
+    int null_space = 0;
+    DevArr<double> nsw;       // kind 1: level-0 work vector, the centred right-hand side where the caller's must stay as it is
+    DevArr<double> ncw;       // kind 1 with a CG coarsest solver: the centred coarsest right-hand side when it is not the level's own buffer
     // captured V-cycles, one per (u, rhs) pointer pair (single rank): replaying a hipGraph removes
     // the ~70 launch gaps of a V-cycle, which weigh as much as a whole coarse level
     std::vector<CapturedCycle> graphs;
@@ -3383,6 +3417,15 @@ int coarse_solve(sgpu_amg *h, double *u, const double *rhs, int *iters) {
         HIPCHK(hipGetLastError());
         if (iters) *iters = 0;
         return SGPU_OK;
+    }
+    if (h->null_space == 1 && A->M > 0) {
+        // the constant null space: CG on the centred right-hand side (from a zero iterate on a symmetric operator it stays in the
+        // complement of constants, so nothing is centred afterwards).  In place in the level's own buffer; a right-hand side that
+        // is the caller's (a one-level hierarchy, sgpu_coarsest_solve) is centred into a work vector
+        const int L = h->nlevels - 1;
+        double *c = (L >= 1 && rhs == h->rhs[L].get()) ? h->rhs[L].get() : h->ncw.get();
+        CHK(center_async(rhs, c, (size_t)A->M));
+        rhs = c;
     }
     if (h->coarse_local && !h->coarse_host_driven) {
         if (A->M == 0) { if (iters) *iters = 0; return SGPU_OK; }      // this rank holds no coarsest rows
@@ -3522,28 +3565,58 @@ int vcycle0(sgpu_amg *h, double *u, const double *rhs, bool u_zero = false) {
 
 // dense inverse of a small one-rank operator by Gauss-Jordan with partial pivoting, on the host (the direct coarsest solve of
 // sgpu_amg_create and sgpu_amg_set_operator); inv: row-major M x M
-int dense_inverse(const sgpu_op *Ac, std::vector<double> &inv) {
+int dense_inverse(const sgpu_op *Ac, std::vector<double> &inv, bool pinv = false) {
     const int n = Ac->M;
     std::vector<double> a((size_t)n * n, 0.0);
-    inv.assign((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) {
-        inv[(size_t)i * n + i] = 1.0;
+    for (int i = 0; i < n; ++i)
         for (int k = Ac->loc.h_rp[i]; k < Ac->loc.h_rp[i + 1]; ++k) a[(size_t)i * n + Ac->loc.h_col[k]] = Ac->h_val[k];
+    // the elimination itself: coarse_pinv.h.  pinv: the pseudo-inverse on the complement of constants (null_space == 1)
+    if (pinv) {
+        if (!coarse_pinv::pseudo_inverse(a, n, inv))
+            return fail(SGPU_ERR_ARG, "coarsest operator: no pseudo-inverse (the mean of its diagonal is not positive, or A + (s/n) 1 1^T is singular: a null space larger than the constants)");
+        return SGPU_OK;
     }
-    for (int c = 0; c < n; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < n; ++r) if (std::fabs(a[(size_t)r * n + c]) > std::fabs(a[(size_t)piv * n + c])) piv = r;
-        if (a[(size_t)piv * n + c] == 0.0) return fail(SGPU_ERR_ARG, "coarsest operator is singular");
-        if (piv != c) for (int j = 0; j < n; ++j) { std::swap(a[(size_t)piv * n + j], a[(size_t)c * n + j]); std::swap(inv[(size_t)piv * n + j], inv[(size_t)c * n + j]); }
-        const double d = 1.0 / a[(size_t)c * n + c];
-        for (int j = 0; j < n; ++j) { a[(size_t)c * n + j] *= d; inv[(size_t)c * n + j] *= d; }
-        for (int r = 0; r < n; ++r) {
-            if (r == c) continue;
-            const double f = a[(size_t)r * n + c];
-            if (f == 0.0) continue;
-            for (int j = 0; j < n; ++j) { a[(size_t)r * n + j] -= f * a[(size_t)c * n + j]; inv[(size_t)r * n + j] -= f * inv[(size_t)c * n + j]; }
-        }
+    if (!coarse_pinv::gauss_jordan_inverse(a, n, inv)) return fail(SGPU_ERR_ARG, "coarsest operator is singular");
+    return SGPU_OK;
+}
+
+// how far a one-rank operator is from annihilating constants: max_i |(A 1)_i| / max_i |a_ii|, A 1 through sgpu_spmv on a vector of
+// ones, downloaded.  The diagonal from inv_diag where the operator has one, from its CSR arrays otherwise.  Setup time only
+int null_defect(sgpu_op *A, double *defect) {
+    const size_t n = (size_t)A->M;
+    *defect = 0.0;
+    if (n == 0) return SGPU_OK;
+    DevArr<double> one, w;
+    CHK(dev_alloc(one, n)); CHK(dev_alloc(w, n));
+    CHK(sgpu_vec_fill(one, 1.0, n));
+    CHK(sgpu_spmv(A, one, w));
+    std::vector<double> hw(n);
+    CHK(sgpu_vec_download(hw.data(), w, n));
+    double num = 0.0, den = 0.0;
+    for (size_t i = 0; i < n; ++i) num = std::fabs(hw[i]) > num || hw[i] != hw[i] ? std::fabs(hw[i]) : num;      // (a NaN stays)
+    if (A->inv_diag) {
+        CHK(sgpu_vec_download(hw.data(), A->inv_diag, n));
+        for (size_t i = 0; i < n; ++i) den = std::max(den, std::fabs(1.0 / hw[i]));
+    } else {
+        const size_t nnz = (size_t)A->loc.nnz;
+        std::vector<int> rp(n + 1), col(nnz);
+        std::vector<double> val(nnz);
+        HIPCHK(hipMemcpyAsync(rp.data(), A->loc.csr.row_ptr, (n + 1) * sizeof(int), hipMemcpyDeviceToHost, g.cs));
+        if (nnz) HIPCHK(hipMemcpyAsync(col.data(), A->loc.csr.col, nnz * sizeof(int), hipMemcpyDeviceToHost, g.cs));
+        if (nnz) HIPCHK(hipMemcpyAsync(val.data(), A->loc.csr.val, nnz * sizeof(double), hipMemcpyDeviceToHost, g.cs));
+        HIPCHK(hipStreamSynchronize(g.cs));
+        for (size_t i = 0; i < n; ++i)
+            for (int k = rp[i]; k < rp[i + 1]; ++k) if ((size_t)col[k] == i) den = std::max(den, std::fabs(val[k]));
     }
+    *defect = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
+    return SGPU_OK;
+}
+const double NULL_DEFECT_MAX = 1e-10;     // 3.5 orders above what the setup's own hierarchies show, far below a pinned row's 1/6
+int null_defect_check(sgpu_op *A, int level, const char *what) {
+    double d = 0.0;
+    CHK(null_defect(A, &d));
+    if (!(d <= NULL_DEFECT_MAX))
+        return fail(SGPU_ERR_ARG, "%s: the operator of level %d does not annihilate constants: max|A 1| / max|a_ii| = %.3e exceeds %.0e", what, level, d, NULL_DEFECT_MAX);
     return SGPU_OK;
 }
 
@@ -3562,10 +3635,19 @@ int sgpu_amg_default_params(sgpu_amg_params *p) {
 
 int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *const *R, const value_t *eig_max,
                     const sgpu_amg_params *params, sgpu_amg **out) {
+    return sgpu_amg_create_null_space(nlevels, A, P, R, eig_max, params, 0, out);
+}
+
+int sgpu_amg_create_null_space(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *const *R, const value_t *eig_max,
+                               const sgpu_amg_params *params, int null_space, sgpu_amg **out) {
     CHK(need_ctx());
     if (nlevels < 1 || !A || !out) return fail(SGPU_ERR_ARG, "bad hierarchy");
+    if (null_space != 0 && null_space != 1) return fail(SGPU_ERR_ARG, "sgpu_amg_create_null_space: null_space is 0 (none) or 1 (constants), got %d", null_space);
+    if (null_space == 1 && (g.nranks > 1 || g.multi()))
+        return fail(SGPU_ERR_ARG, "sgpu_amg_create_null_space: a hierarchy that knows the constant null space runs on one rank (this context has %d)", g.nranks);
     std::unique_ptr<sgpu_amg> h(new sgpu_amg());
     h->nlevels = nlevels;
+    h->null_space = null_space;
     if (params) h->prm = *params; else sgpu_amg_default_params(&h->prm);
     for (int l = 0; l < nlevels; ++l) {
         if (!A[l]) return fail(SGPU_ERR_ARG, "A[%d] is null", l);
@@ -3579,6 +3661,13 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
             h->P.push_back(P[l]); h->R.push_back(R[l]);
             if (!A[l]->inv_diag && A[l]->M > 0) return fail(SGPU_ERR_ARG, "A[%d] has no inv_diag", l);   // (no rows of this level on this rank: fine)
             if (h->prm.smoother == 1 && !(h->eig[l] > 0.0)) return fail(SGPU_ERR_ARG, "chebyshev needs eig_max[%d] > 0", l);
+        }
+    }
+    if (null_space == 1) {
+        // level 0 defines the problem, the coarsest level is the one that gets solved: both must annihilate constants
+        for (int l = 0; l < nlevels; l += std::max(1, nlevels - 1)) {
+            if (A[l]->has_remote || A[l]->recvSize || A[l]->vIndexSize) return fail(SGPU_ERR_ARG, "sgpu_amg_create_null_space: A[%d] has a remote part; one rank only", l);
+            CHK(null_defect_check(A[l], l, "sgpu_amg_create_null_space"));
         }
     }
     h->res.resize(nlevels); h->rhs.resize(nlevels); h->u.resize(nlevels); h->alt.resize(nlevels);
@@ -3606,8 +3695,12 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
     if (h->prm.coarse_solver == 1 && coarse_local && A[nlevels - 1]->M > 0 && !h->coarse_host_driven) {
         // dense inverse by Gauss-Jordan with partial pivoting (host, once)
         std::vector<double> inv;
-        CHK(dense_inverse(A[nlevels - 1], inv));
+        CHK(dense_inverse(A[nlevels - 1], inv, null_space == 1));
         CHK(dev_upload(h->Ainv, inv.data(), inv.size()));
+    }
+    if (null_space == 1) {                         // (no allocation may happen inside a graph capture)
+        HIPCHK(alloc_vec(h->nsw, (size_t)A[0]->M));
+        if (!h->Ainv) HIPCHK(alloc_vec(h->ncw, (size_t)A[nlevels - 1]->M));
     }
     for (int l = 0; l < nlevels - 1; ++l)          // no allocation may happen inside a graph capture
         if (h->prm.smoother == 1) CHK(ensure_d(A[l]));
@@ -3631,6 +3724,12 @@ int sgpu_amg_destroy(sgpu_amg *h) {
     if (!h) return SGPU_OK;
     if (g.live) hipDeviceSynchronize();
     delete h;
+    return SGPU_OK;
+}
+
+int sgpu_amg_get_null_space(const sgpu_amg *h, int *kind) {
+    if (!h || !kind) return fail(SGPU_ERR_ARG, "sgpu_amg_get_null_space: null argument");
+    *kind = h->null_space;
     return SGPU_OK;
 }
 
@@ -3687,6 +3786,7 @@ int sgpu_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value_t 
     if (!h || !u || !rhs) return fail(SGPU_ERR_ARG, "null argument");
     sgpu_op *A = h->A[0];
     const size_t sz = (size_t)A->M;
+    if (h->null_space == 1) { CHK(center_async(rhs, h->nsw, sz)); rhs = h->nsw; }      // A u = rhs - mean(rhs): rhs is read every iteration, a centred copy
     CHK(sgpu_vec_fill(u, 0.0, sz));                                   // :1926
     CHK(sgpu_residual(A, u, rhs, h->r));                              // :1942
     double init_dot = 0, current_dot = 0;
@@ -3701,6 +3801,7 @@ int sgpu_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value_t 
         if (hist && i + 1 < cap) hist[i + 1] = std::sqrt(current_dot);
         if (current_dot < THRSHLD) break;
     }
+    if (h->null_space == 1) CHK(center_async(u, u, sz));              // the solution of zero mean
     const bool conv = current_dot < THRSHLD;
     if (i == h->prm.solver_max_iter) --i;
     if (iters) *iters = i + 1;
@@ -3715,6 +3816,7 @@ int sgpu_solve_smoother(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters,
     const size_t sz = (size_t)A->M;
     if (h->prm.smoother == 1 && !(h->eig[0] > 0.0)) return fail(SGPU_ERR_ARG, "chebyshev needs eig_max[0] > 0");
     if (h->prm.smoother == 1) CHK(ensure_d(A));
+    if (h->null_space == 1) { CHK(center_async(rhs, h->nsw, sz)); rhs = h->nsw; }
     CHK(sgpu_vec_fill(u, 0.0, sz));                                   // :2051
     CHK(sgpu_residual(A, u, rhs, h->r));                              // :2060
     double init_dot = 0, current_dot = 0;
@@ -3732,6 +3834,7 @@ int sgpu_solve_smoother(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters,
         if (hist && i + 1 < cap) hist[i + 1] = std::sqrt(current_dot);
         if (current_dot < THRSHLD) break;
     }
+    if (h->null_space == 1) CHK(center_async(u, u, sz));
     const bool conv = current_dot < THRSHLD;
     if (i == h->prm.solver_max_iter) --i;
     if (iters) *iters = i + 1;
@@ -3747,6 +3850,7 @@ int sgpu_solve_pCG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, valu
     double *r = h->r, *rho = h->rho, *hh = h->hh, *p = h->p;
     CHK(sgpu_vec_fill(u, 0.0, sz));                                   // :2482
     CHK(sgpu_residual(A, u, rhs, r));                                 // :2497
+    if (h->null_space == 1) CHK(center_async(r, r, sz));              // r_0 = rhs - mean(rhs); nothing is centred per iteration
     double init_dot = 0, current_dot = 0;
     CHK(sgpu_dot(r, r, sz, &init_dot));
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
@@ -3773,6 +3877,7 @@ int sgpu_solve_pCG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, valu
         CHK(pcg_direction_dev(b, a, rho, p, sz));                     // beta = r.rho / rho_res; :2665-2667  p = rho + beta p
         std::swap(a, b);
     }
+    if (h->null_space == 1) CHK(center_async(u, u, sz));              // the solution of zero mean
     const bool conv = current_dot < THRSHLD;
     if (i == h->prm.solver_max_iter) i--;
     if (iters) *iters = i + 1;
@@ -3788,6 +3893,7 @@ int sgpu_solve_CG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value
     double *r = h->r, *hh = h->hh, *p = h->p;
     CHK(sgpu_vec_fill(u, 0.0, sz));
     CHK(sgpu_residual(A, u, rhs, r));
+    if (h->null_space == 1) CHK(center_async(r, r, sz));
     double init_dot = 0, current_dot = 0;
     CHK(sgpu_dot(r, r, sz, &init_dot));
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
@@ -3807,6 +3913,7 @@ int sgpu_solve_CG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value
         CHK(pcg_direction_dev(b, a, r, p, sz));                       // beta = current_dot / rho_res; p = r + beta p
         std::swap(a, b);
     }
+    if (h->null_space == 1) CHK(center_async(u, u, sz));
     const bool conv = current_dot < THRSHLD;
     if (i == h->prm.solver_max_iter) i--;
     if (iters) *iters = i + 1;
@@ -3949,6 +4056,8 @@ extern "C" int sgpu_amg_set_operator(sgpu_amg *h, int level, sgpu_op *A_new, val
     if (A_new->has_remote || A_new->recvSize || A_new->vIndexSize) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator has a remote part; runs on one rank only");
     if (!coarsest && !A_new->inv_diag && A_new->M > 0) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator has no inv_diag");
     if (!coarsest && h->prm.smoother == 1 && !(eig_max > 0.0)) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: chebyshev needs eig_max > 0");
+    // a hierarchy that knows the constant null space: the incoming operator of level 0 or of the coarsest level must annihilate constants too
+    if (h->null_space == 1 && (level == 0 || coarsest)) CHK(null_defect_check(A_new, level, "sgpu_amg_set_operator"));
     // nothing in flight, then no captured launch that names the outgoing operator's arrays
     HIPCHK(hipStreamSynchronize(g.cs));
     HIPCHK(hipStreamSynchronize(g.hs));
@@ -3959,7 +4068,7 @@ extern "C" int sgpu_amg_set_operator(sgpu_amg *h, int level, sgpu_op *A_new, val
     if (direct) {
         if (A_new->h_val.size() != A_new->loc.h_col.size()) return fail(SGPU_ERR_ARG, "sgpu_amg_set_operator: the operator keeps no host copy of its values to factor");
         std::vector<double> inv;
-        CHK(dense_inverse(A_new, inv));
+        CHK(dense_inverse(A_new, inv, h->null_space == 1));
         CHK(dev_upload(Ainv, inv.data(), inv.size()));
     }
     if (coarsest && h->coarse_device_cg && A_new->M > sk::CG_MAXN) CHK(ensure_dcg(h, A_new->M));    // (kept: the row count is the outgoing operator's)

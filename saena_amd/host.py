@@ -93,6 +93,7 @@ HOST_SYMBOLS.update({
     "saena_amg_update": (C.c_int, [_VP, _VP, C.c_int]),
     "saena_amg_set_device_eig": (C.c_int, [_VP, C.c_int]),
     "saena_amg_set_coarse_solver": (C.c_int, [_VP, C.c_char_p]),
+    "saena_amg_set_null_space": (C.c_int, [_VP, C.c_char_p]),
     "saena_amg_num_levels": (C.c_int, [_VP]),
     "saena_amg_level_info": (C.c_int, [_VP, C.c_int, _PI, C.POINTER(C.c_long), C.POINTER(C.c_long), _PD]),
     "saena_amg_level_aggregates": (C.c_int, [_VP, C.c_int, _PI, _PI]),
@@ -505,17 +506,22 @@ OPTIONS001 = dict(solver_max_iter=50, relative_tol=1e-8, smoother="jacobi", preS
 class AmgSolver:
     """saena::amg mirror (reference include/saena.hpp:195-265): set_matrix on the host, solve on the GPU."""
 
-    def __init__(self, A: Matrix, opts: OptionsC, device_eig=None, coarse_solver=None):
+    def __init__(self, A: Matrix, opts: OptionsC, device_eig=None, coarse_solver=None, null_space=None):
         """device_eig: True lets the one-rank setup and the updates take eig_max from the device estimate (saena_amg_set_device_eig);
         None leaves the library's default (off, unless SAENA_DEVICE_EIG=1).
         coarse_solver: "direct", "cg" or "device_cg" (saena_amg_set_coarse_solver), read by to_device; None leaves the library's
-        default ("direct", unless SAENA_COARSE_SOLVER names another)"""
+        default ("direct", unless SAENA_COARSE_SOLVER names another)
+        null_space: "constant" (saena_amg_set_null_space), read by to_device: A annihilates constants (assemble it after
+        set_remove_boundary(False)); the solves solve A u = rhs - mean(rhs) and return the solution of zero mean, eigs the smallest
+        nonzero pairs.  None / "none": the solver as ever"""
         self.A, self.L = A, A.L
         self.h = self.L.saena_amg_new()
         if device_eig is not None:
             self.set_device_eig(device_eig)
         if coarse_solver is not None:
             self.set_coarse_solver(coarse_solver)
+        if null_space is not None:
+            self.set_null_space(null_space)
         _check(self.L, self.L.saena_amg_set_matrix(self.h, A.h, C.byref(opts)))
         self.opts = opts
 
@@ -525,6 +531,10 @@ class AmgSolver:
 
     def set_coarse_solver(self, name):
         _check(self.L, self.L.saena_amg_set_coarse_solver(self.h, str(name).encode()))
+        return self
+
+    def set_null_space(self, name):
+        _check(self.L, self.L.saena_amg_set_null_space(self.h, str(name).encode()))
         return self
 
     def update(self, A_new: Matrix, mode):
