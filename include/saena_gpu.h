@@ -303,8 +303,8 @@ int sgpu_amg_create(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *
  * or of the coarsest level has max_i |(A 1)_i| / max_i |a_ii| > 1e-10 (computed once through sgpu_spmv on a vector of ones and a
  * download; the message names the level and the value).  The smoothed-aggregation setup keeps constants on every level to 1e-14; a
  * pinned row or a reaction term is orders above the threshold.  Any other value of null_space is SGPU_ERR_ARG.  Not covered: more than
- * one rank, null spaces other than constants (a disconnected graph passes the check above and is NOT detected), nonsymmetric singular operators, a right-hand side that is constant (zero after
- * centring). */
+ * one rank, null spaces other than constants (a disconnected graph passes the check above and is NOT detected), nonsymmetric singular operators.
+ * A right-hand side that is constant is a zero right-hand side: rule 2 of "Degenerate right-hand sides" below. */
 int sgpu_amg_create_null_space(int nlevels, sgpu_op *const *A, sgpu_op *const *P, sgpu_op *const *R,
                                const value_t *eig_max, const sgpu_amg_params *params, int null_space, sgpu_amg **out);
 /* kind: the null_space the hierarchy was created with (0 for sgpu_amg_create) */
@@ -313,6 +313,29 @@ int sgpu_amg_destroy(sgpu_amg *h);       /* does not destroy the operators */
 /* saena_object::vcycle (saena_object_solve.cpp:961-1431) on level 0.  On a hierarchy created with null_space 1 only the coarsest
  * solve is restricted to the complement of constants: neither rhs nor u is centred on level 0 */
 int sgpu_vcycle(sgpu_amg *h, value_t *u, const value_t *rhs);
+/* ---- Degenerate right-hand sides: one contract for every solve ---------------
+ * sgpu_solve, sgpu_solve_smoother, sgpu_solve_CG, sgpu_solve_pCG, sgpu_solve_pCG_block (per column) and sgpu_solve_FGMRES, at every
+ * rank count they support, with use_graph 0 and 1.  ||r_0||^2 is the dot of the initial residual (of the centred right-hand side
+ * under null_space 1), summed over the ranks: every rank holds the same bits, takes the same branch and returns together.
+ *  1. Zero.  ||r_0||^2 == 0: u = 0 (every entry +0), *iters = 0, res_hist[0] = 0.0, SGPU_OK.  After the initial residual and its dot
+ *     no V-cycle, smoother sweep or matrix product is launched.
+ *  2. Constant, null_space 1.  With n rows, m the mean the centring computed (its sum / n) and k the roundings on the longest path
+ *     of that sum (tests/solver_ref.dot_roundings(n): the grid of sgpu_dot), a right-hand side with
+ *         ||rhs - m||^2 <= n (k u |m|)^2,   u = 2^-53,
+ *     is a zero right-hand side and returns rule 1's result: its centred part is not above the rounding error of its own mean
+ *     (DESIGN 20 derives the bound: the centred entries of c 1 are at most k u |m| each).  The mean comes down with ||r_0||^2, in front
+ *     of the same synchronisation.  Per column in the block solve.
+ *  3. Non-finite.  The solve stops at the first ||r_k||^2 that is not finite (a NaN or Inf in rhs, a breakdown p.Ap = 0), k = 0
+ *     included: SGPU_ERR_NOCONV, sgpu_last_error() says "non-finite residual at iteration k", *iters = k (the iterations completed),
+ *     res_hist[k] holds the non-finite value and nothing further is launched (u is not centred either); for k = 0, u = 0.  In the
+ *     block solve that column is frozen at that iteration (u = 0 for k = 0) and counts as failed; the other columns go on to their own
+ *     thresholds with the bits they have without it, and the message names the first such column.  sgpu_solve_FGMRES tests k = 0 this
+ *     way; later its Hessenberg column is not finite and it stops with its breakdown message, *iters = k.
+ *  4. Nothing else moves.  For a finite non-zero right-hand side every bit of u and res_hist, every iteration count and every launch
+ *     count is as without these rules: they test values the loops already hold on the host and add neither a launch nor a
+ *     synchronisation.
+ * res_hist is written up to entry min(*iters, hist_cap - 1) and never past hist_cap - 1; *iters does not depend on hist_cap; iters
+ * and res_hist may be NULL. */
 /* saena_object::solve (saena_object_solve.cpp:1883-2014): u is zeroed, then V-cycles until
  * ||r||^2 < ||r0||^2 tol^2.  res_hist[k] = ||r_k||, k = 0..iters (capacity hist_cap). */
 int sgpu_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value_t *res_hist, int hist_cap);
@@ -382,9 +405,9 @@ int sgpu_prolong_correct_block(sgpu_op *P, const value_t *E_coarse, value_t *U, 
 int sgpu_vcycle_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K);
 /* sgpu_solve_pCG's recurrence on K columns in lockstep, every column with its own scalars and threshold.  A column stops
  * at the iteration at which its ||r||^2 drops below its own threshold and is not written again; iters[j] and
- * res_hist[j*hist_cap + k] are those of a scalar solve of column j.  A column whose right-hand side is exactly zero
- * returns u = 0, iters[j] = 0, res_hist[j*hist_cap] = 0.  SGPU_ERR_NOCONV if any column is still above its threshold after
- * solver_max_iter iterations (all iterates stay valid).  One host synchronisation per iteration. */
+ * res_hist[j*hist_cap + k] are those of a scalar solve of column j, a zero, constant or non-finite column included ("Degenerate
+ * right-hand sides" above).  SGPU_ERR_NOCONV if any column is still above its threshold after solver_max_iter iterations or
+ * met a non-finite residual (all other iterates stay valid).  One host synchronisation per iteration. */
 int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K,
                          int *iters /*[K]*/, value_t *res_hist /*[K][hist_cap]*/, int hist_cap);
 

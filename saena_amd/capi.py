@@ -660,7 +660,7 @@ class Amg:
         st = fn(self.h, u.ptr, rhs.ptr, C.byref(it), hist.ctypes.data_as(_PD), cap)
         if st not in (0, -6):
             check(st)
-        return it.value, hist[~np.isnan(hist)], st == 0
+        return it.value, hist[:min(it.value + 1, cap)], st == 0     # entries 0..iters as written: a non-finite one stays visible
 
     def solve(self, u, rhs):
         return self._solve(lib().sgpu_solve, u, rhs)
@@ -707,7 +707,7 @@ class Amg:
         st = lib().sgpu_solve_pCG_block(self.h, U.ptr, RHS.ptr, K, it, hist.ctypes.data_as(_PD), cap)
         if st not in (0, -6):
             check(st)
-        return [int(v) for v in it], [h[~np.isnan(h)] for h in hist], st == 0
+        return [int(v) for v in it], [h[:min(int(k) + 1, cap)] for h, k in zip(hist, it)], st == 0
 
     # the block dot and the block pCG updates on the caller's device vectors (sgpu_debug_block_*): n rows of K interleaved columns
     def debug_block_dot(self, X, Y, n, K, active, out):

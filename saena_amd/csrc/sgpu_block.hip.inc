@@ -706,17 +706,24 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
     if (h->null_space == 1) CHK(center_block_async(r, r, sz, K));        // r_0 = RHS - its column means; nothing is centred per iteration
     CHK(dot_block(B, r, r, sz, Srr, all));
     CHK(rank_sum_block(B, Srr, all));
+    // under null_space 1 the K sums the centring left come down in front of the same synchronisation (one rank: slots 8.. are free)
+    if (h->null_space == 1) HIPCHK(hipMemcpyAsync(g.hscalar + 8, g.cblk + (size_t)g.n_partials * 8, K * sizeof(double), hipMemcpyDeviceToHost, g.cs));
     CHK(fetch(Srr));
     double thr[8], cur[8];
     int it[8];
     unsigned active = 0, failed = 0;
+    int bad_col = -1, bad_it = 0;                  // the first column with a non-finite dot (rule 3), for the message
     for (int j = 0; j < K; ++j) {
         const double init = B.hS[j];
         if (hist && cap > 0) hist[(size_t)j * cap] = std::sqrt(init);
         thr[j] = init * h->prm.solver_tol * h->prm.solver_tol;
         cur[j] = init;
         it[j] = 0;
-        if (init != 0.0) active |= 1u << j;       // a zero right-hand side: u = 0 is the solution, frozen at iteration 0 (the scalar solve divides 0 by 0 there)
+        // rules 1 to 3 of include/saena_gpu.h per column, as sgpu_solve_pCG takes them: a zero right-hand side, or one that is zero
+        // after centring up to the rounding of its mean, has u = 0 as its solution; a non-finite one fails.  All are frozen at iteration 0
+        if (!std::isfinite(init)) { failed |= 1u << j; if (bad_col < 0) bad_col = j; }
+        else if (init == 0.0 || (h->null_space == 1 && centred_is_dust(init, g.hscalar[8 + j], sz))) { if (hist && cap > 0) hist[(size_t)j * cap] = 0.0; }
+        else active |= 1u << j;
     }
     if (active && h->prm.solver_max_iter > 0) {
         CHK(vcycle_block0(h, B, rho, r, true));
@@ -736,6 +743,10 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
                 it[j] = i + 1;
                 if (hist && i + 1 < cap) hist[(size_t)j * cap + i + 1] = std::sqrt(cur[j]);
                 if (cur[j] < thr[j]) active &= ~(1u << j);
+                else if (!std::isfinite(cur[j])) {                 // rule 3: frozen here and failed; the others go on
+                    active &= ~(1u << j); failed |= 1u << j;
+                    if (bad_col < 0) { bad_col = j; bad_it = i + 1; }
+                }
             }
             if (!active || i + 1 == h->prm.solver_max_iter) break;
             CHK(vcycle_block0(h, B, rho, r, true));
@@ -746,8 +757,9 @@ int sgpu_solve_pCG_block(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int
         }
     }
     if (h->null_space == 1) CHK(center_block_async(U, U, sz, K));    // every column: the solution of zero mean
-    failed = active;                               // still above their thresholds at solver_max_iter
+    failed |= active;                              // still above their thresholds at solver_max_iter
     if (iters) for (int j = 0; j < K; ++j) iters[j] = it[j];
+    if (bad_col >= 0) return fail(SGPU_ERR_NOCONV, "solve_pCG_block: non-finite residual at iteration %d (column %d)", bad_it, bad_col);
     return failed ? SGPU_ERR_NOCONV : SGPU_OK;
 }
 

@@ -216,6 +216,7 @@ int sgpu_solve_FGMRES(sgpu_amg *h, value_t *u, const value_t *rhs, int restart, 
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
     if (true_res) *true_res = std::sqrt(init_dot);
     if (init_dot == 0.0) return SGPU_OK;                           // u = 0 is the solution
+    if (!std::isfinite(init_dot)) return fail(SGPU_ERR_NOCONV, "solve_FGMRES: non-finite residual at iteration 0");   // u = 0, nothing more is launched
     const double thr = init_dot * h->prm.solver_tol * h->prm.solver_tol;
     std::vector<double> H((size_t)(m + 1) * m, 0.0), cs((size_t)m), sn((size_t)m), gv((size_t)m + 1), y((size_t)m);
     double cur_dot = init_dot;

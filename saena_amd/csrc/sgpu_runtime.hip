@@ -3780,6 +3780,47 @@ int sgpu_coarsest_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters)
     return coarse_solve(h, u, rhs, iters);
 }
 
+// ---- right-hand sides that give the outer loops nothing to iterate on (include/saena_gpu.h, "Degenerate right-hand sides") ----
+// Roundings on the longest path from an element to the sum of k_sum_partial + k_reduce_partials on n elements, counted as
+// tests/solver_ref.dot_roundings counts sgpu_dot's (the same grid and the same order of summation)
+int sum_roundings(size_t n) {
+    const size_t nb = (size_t)dot_nblocks(n);
+    return (int)((n + sk::BLOCK * nb - 1) / (sk::BLOCK * nb)) + 1 + 6 + 4 + (int)((nb + sk::BLOCK - 1) / sk::BLOCK) + 6 + 4 + 1;
+}
+// Rule 2: is ||x - mean(x)||^2 = dot no more than the rounding error of the mean itself?  sum: what the centring's reduction left
+// (n mean).  With k = sum_roundings(n) the centred entries of c 1 are at most k u |mean| each: dot <= n (k u |mean|)^2.
+// False for a NaN on either side.
+bool centred_is_dust(double dot, double sum, size_t n) {
+    const double e = (double)sum_roundings(n) * 0x1p-53 * std::fabs(sum / (double)n);
+    return dot <= (double)n * e * e;
+}
+// Rules 1 to 3 on the initial ||r_0||^2 (the rank-summed value, so every rank takes the same branch).  -> true: the solve ends at
+// iteration 0 with *st (u is the zero vector the caller filled, nothing more is launched); false: iterate
+bool solve_ends_at_start(const sgpu_amg *h, const char *who, double init_dot, size_t n, int *iters, value_t *hist, int cap, int *st) {
+    if (!std::isfinite(init_dot)) {
+        if (iters) *iters = 0;
+        *st = fail(SGPU_ERR_NOCONV, "%s: non-finite residual at iteration 0", who);
+        return true;
+    }
+    if (init_dot == 0.0 || (h->null_space == 1 && centred_is_dust(init_dot, g.hscalar[CENTER_SLOT], n))) {
+        if (iters) *iters = 0;
+        if (hist && cap > 0) hist[0] = 0.0;
+        *st = SGPU_OK;
+        return true;
+    }
+    return false;
+}
+// under null_space 1 the centring's sum comes down with the next sgpu_dot: one copy more in front of the same synchronisation
+int fetch_center_sum(const sgpu_amg *h) {
+    if (h->null_space == 1) HIPCHK(hipMemcpyAsync(g.hscalar + CENTER_SLOT, g.dscalar + CENTER_SLOT, sizeof(double), hipMemcpyDeviceToHost, g.cs));
+    return SGPU_OK;
+}
+// rule 3 inside a loop: the dot after iteration k (1-based) is not finite
+int nonfinite_stop(const char *who, int k, int *iters) {
+    if (iters) *iters = k;
+    return fail(SGPU_ERR_NOCONV, "%s: non-finite residual at iteration %d", who, k);
+}
+
 // saena_object::solve (src/saena_object_solve.cpp:1883-2014)
 int sgpu_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value_t *hist, int cap) {
     CHK(need_ctx());
@@ -3790,8 +3831,11 @@ int sgpu_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value_t 
     CHK(sgpu_vec_fill(u, 0.0, sz));                                   // :1926
     CHK(sgpu_residual(A, u, rhs, h->r));                              // :1942
     double init_dot = 0, current_dot = 0;
+    CHK(fetch_center_sum(h));
     CHK(sgpu_dot(h->r, h->r, sz, &init_dot));
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
+    int st = SGPU_OK;
+    if (solve_ends_at_start(h, "solve", init_dot, sz, iters, hist, cap, &st)) return st;
     const double THRSHLD = init_dot * h->prm.solver_tol * h->prm.solver_tol;
     int i = 0;
     for (; i < h->prm.solver_max_iter; ++i) {                         // :1957-1970
@@ -3800,6 +3844,7 @@ int sgpu_solve(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value_t 
         CHK(sgpu_dot(h->r, h->r, sz, &current_dot));
         if (hist && i + 1 < cap) hist[i + 1] = std::sqrt(current_dot);
         if (current_dot < THRSHLD) break;
+        if (!std::isfinite(current_dot)) return nonfinite_stop("solve", i + 1, iters);
     }
     if (h->null_space == 1) CHK(center_async(u, u, sz));              // the solution of zero mean
     const bool conv = current_dot < THRSHLD;
@@ -3820,9 +3865,12 @@ int sgpu_solve_smoother(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters,
     CHK(sgpu_vec_fill(u, 0.0, sz));                                   // :2051
     CHK(sgpu_residual(A, u, rhs, h->r));                              // :2060
     double init_dot = 0, current_dot = 0;
+    CHK(fetch_center_sum(h));
     CHK(sgpu_dot(h->r, h->r, sz, &init_dot));
     current_dot = init_dot;
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
+    int st = SGPU_OK;
+    if (solve_ends_at_start(h, "solve_smoother", init_dot, sz, iters, hist, cap, &st)) return st;
     const double THRSHLD = init_dot * h->prm.solver_tol * h->prm.solver_tol;
     int i = 0;
     for (; i < h->prm.solver_max_iter; ++i) {                         // :2072-2081
@@ -3833,6 +3881,7 @@ int sgpu_solve_smoother(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters,
         CHK(sgpu_dot(h->r, h->r, sz, &current_dot));
         if (hist && i + 1 < cap) hist[i + 1] = std::sqrt(current_dot);
         if (current_dot < THRSHLD) break;
+        if (!std::isfinite(current_dot)) return nonfinite_stop("solve_smoother", i + 1, iters);
     }
     if (h->null_space == 1) CHK(center_async(u, u, sz));
     const bool conv = current_dot < THRSHLD;
@@ -3852,8 +3901,11 @@ int sgpu_solve_pCG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, valu
     CHK(sgpu_residual(A, u, rhs, r));                                 // :2497
     if (h->null_space == 1) CHK(center_async(r, r, sz));              // r_0 = rhs - mean(rhs); nothing is centred per iteration
     double init_dot = 0, current_dot = 0;
+    CHK(fetch_center_sum(h));
     CHK(sgpu_dot(r, r, sz, &init_dot));
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
+    int st = SGPU_OK;
+    if (solve_ends_at_start(h, "solve_pCG", init_dot, sz, iters, hist, cap, &st)) return st;
     CHK(vcycle0(h, rho, r, true));                                    // :2536-2537 (rho = 0, V-cycle)
     CHK(sgpu_vec_copy(p, rho, sz));
     const double THRSHLD = init_dot * h->prm.solver_tol * h->prm.solver_tol;
@@ -3872,6 +3924,7 @@ int sgpu_solve_pCG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, valu
         CHK(pcg_update_dev(a, 5, p, hh, u, r, sz, 6, &current_dot));  // alpha = rho_res / pdoth; :2593-2596; :2603
         if (hist && i + 1 < cap) hist[i + 1] = std::sqrt(current_dot);
         if (current_dot < THRSHLD) break;                             // :2620
+        if (!std::isfinite(current_dot)) return nonfinite_stop("solve_pCG", i + 1, iters);
         CHK(vcycle0(h, rho, r, true));                                // :2640-2641 (rho = 0, V-cycle)
         CHK(dot_dev(r, rho, sz, b));                                  // :2655
         CHK(pcg_direction_dev(b, a, rho, p, sz));                     // beta = r.rho / rho_res; :2665-2667  p = rho + beta p
@@ -3895,8 +3948,11 @@ int sgpu_solve_CG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value
     CHK(sgpu_residual(A, u, rhs, r));
     if (h->null_space == 1) CHK(center_async(r, r, sz));
     double init_dot = 0, current_dot = 0;
+    CHK(fetch_center_sum(h));
     CHK(sgpu_dot(r, r, sz, &init_dot));
     if (hist && cap > 0) hist[0] = std::sqrt(init_dot);
+    int st = SGPU_OK;
+    if (solve_ends_at_start(h, "solve_CG", init_dot, sz, iters, hist, cap, &st)) return st;
     CHK(sgpu_vec_copy(p, r, sz));
     const double THRSHLD = init_dot * h->prm.solver_tol * h->prm.solver_tol;
     current_dot = init_dot;
@@ -3910,6 +3966,7 @@ int sgpu_solve_CG(sgpu_amg *h, value_t *u, const value_t *rhs, int *iters, value
         CHK(pcg_update_dev(a, 5, p, hh, u, r, sz, b, &current_dot));
         if (hist && i + 1 < cap) hist[i + 1] = std::sqrt(current_dot);
         if (current_dot < THRSHLD) break;
+        if (!std::isfinite(current_dot)) return nonfinite_stop("solve_CG", i + 1, iters);
         CHK(pcg_direction_dev(b, a, r, p, sz));                       // beta = current_dot / rho_res; p = r + beta p
         std::swap(a, b);
     }

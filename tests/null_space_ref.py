@@ -15,7 +15,7 @@ CPU that the restatements stay inside every bound tests/test_gpu_null_space.py a
 import numpy as np
 import scipy.sparse as sp
 
-from tests import solver_ref as sr
+from tests import degenerate_ref as dg, solver_ref as sr
 
 U = sr.U
 OMEGA = float(np.float32(2.0 / 3.0))     # JACOBI_OMEGA_REF
@@ -274,7 +274,12 @@ def vcycle(H, rhs, smoother="jacobi", coarse="direct", u=None, pre=3, post=3):
 
 
 def _finish(u, hist, conv):
-    return dict(u=center(u)[0], iters=len(hist) - 1, hist=np.array(hist), converged=conv)
+    return dict(u=center(u)[0], iters=len(hist) - 1, hist=np.array(hist), converged=conv, stopped=None)
+
+
+def _nonfinite(u, hist):
+    """rule 3 of include/saena_gpu.h's "Degenerate right-hand sides": stopped where the dot is not finite, u as it is (not centred)"""
+    return dict(u=u, iters=len(hist) - 1, hist=np.array(hist), converged=False, stopped="nonfinite")
 
 
 def pcg(H, rhs, smoother="jacobi", coarse="direct", tol=TOL, max_iter=MAX_ITER, precond=True):
@@ -282,8 +287,11 @@ def pcg(H, rhs, smoother="jacobi", coarse="direct", tol=TOL, max_iter=MAX_ITER, 
     A = H["A"][0]
     M = (lambda r: vcycle(H, r, smoother, coarse)) if precond else (lambda r: r)
     u = np.zeros(A.shape[0])
-    r = center(-np.asarray(rhs, np.float64))[0]
+    r, mean = center(-np.asarray(rhs, np.float64))
     init = float(r @ r)
+    kind = dg.at_start(init, len(r), mean, null_space=True)          # rules 1 to 3 at iteration 0
+    if kind:
+        return dg.start_result(kind, len(r), init)
     hist, thr = [np.sqrt(init)], init * tol * tol
     rho = M(r)
     p = rho.copy()
@@ -299,6 +307,8 @@ def pcg(H, rhs, smoother="jacobi", coarse="direct", tol=TOL, max_iter=MAX_ITER, 
         if cur < thr:
             conv = True
             break
+        if not np.isfinite(cur):
+            return _nonfinite(u, hist)
         rho = M(r)
         rr_new = float(r @ rho)
         p = rho + (rr_new / rr) * p
@@ -309,10 +319,13 @@ def pcg(H, rhs, smoother="jacobi", coarse="direct", tol=TOL, max_iter=MAX_ITER, 
 def stationary(H, rhs, smoother="jacobi", coarse="direct", tol=TOL, max_iter=MAX_ITER, with_coarse=True, pre=3):
     """sgpu_solve (V-cycles) / sgpu_solve_smoother (pre sweeps of the smoother) under null_space 1: the right-hand side is centred once"""
     A = H["A"][0]
-    b = center(np.asarray(rhs, np.float64))[0]
+    b, mean = center(np.asarray(rhs, np.float64))
     u = np.zeros(A.shape[0])
     r = A @ u - b
     init = float(r @ r)
+    kind = dg.at_start(init, len(b), mean, null_space=True)
+    if kind:
+        return dg.start_result(kind, len(b), init)
     hist, thr = [np.sqrt(init)], init * tol * tol
     conv = False
     for _ in range(max_iter):
@@ -323,6 +336,8 @@ def stationary(H, rhs, smoother="jacobi", coarse="direct", tol=TOL, max_iter=MAX
         if cur < thr:
             conv = True
             break
+        if not np.isfinite(cur):
+            return _nonfinite(u, hist)
     return _finish(u, hist, conv)
 
 
