@@ -140,7 +140,7 @@ __global__ __launch_bounds__(BLOCK) void k_eig_residual(const double *__restrict
     }
 }
 
-// the residual of the generalised problem (sgpu_geig.hip.inc): R = AX - BX diag(lambda) with the bits of k_eig_residual called with
+// the residual of the generalised problem (sgpu_eig.hip.inc): R = AX - BX diag(lambda) with the bits of k_eig_residual called with
 // BX in X's place, and in the same pass the partial sums of ||r_j||^2 (partial_r) AND of ||(BX)_j||^2 (partial_b), both in
 // k_dot_block_partial's order: the bits of the block dot of R with R and of BX with BX.  Launch it on the dot's grid;
 // partial_*[block * K + j].  It moves 24 n K bytes (two block vectors read, one written).

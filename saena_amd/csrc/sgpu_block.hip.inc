@@ -286,13 +286,9 @@ int center_block_async(const double *X, double *Y, size_t n, int K) {
     if (n == 0) return SGPU_OK;
     const int nb = dot_nblocks(n), gd = grid_for(2 * n);
     double *part = g.cblk, *S = g.cblk + (size_t)g.n_partials * 8;
-    if (K == 2) SGPU_LAUNCH(sk::k_sum_block_partial<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
-    else if (K == 4) SGPU_LAUNCH(sk::k_sum_block_partial<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
-    else SGPU_LAUNCH(sk::k_sum_block_partial<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
+    SGPU_LAUNCH_COLS("k_sum_block_partial", K, per_K(K, [](auto k) { return sk::k_sum_block_partial<k()>; }), dim3(nb), dim3(sk::BLOCK), 0, g.cs, X, n, part);
     SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)part, nb, K, S, (1u << K) - 1u);
-    if (K == 2) SGPU_LAUNCH(sk::k_center_block<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
-    else if (K == 4) SGPU_LAUNCH(sk::k_center_block<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
-    else SGPU_LAUNCH(sk::k_center_block<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
+    SGPU_LAUNCH_COLS("k_center_block", K, per_K(K, [](auto k) { return sk::k_center_block<k()>; }), dim3(gd), dim3(sk::BLOCK), 0, g.cs, (const double *)S, X, Y, n);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
 }
@@ -344,8 +340,8 @@ int coarse_solve_block(sgpu_amg *h, AmgBlock &B, double *u, const double *rhs, b
     if (n == 0) return SGPU_OK;
     if (h->Ainv) {
         const int C = std::min(K, pow2floor(std::max(1, sk::DS_CAP / n)));
-        auto fn = C >= 8 ? sk::k_dense_solve_block<8> : C == 4 ? sk::k_dense_solve_block<4> : C == 2 ? sk::k_dense_solve_block<2> : sk::k_dense_solve_block<1>;
-        SGPU_LAUNCH(fn, dim3(1), dim3(sk::CG_BLOCK), 0, g.cs, (const double *)h->Ainv, rhs, u, n, K);
+        SGPU_LAUNCH_COLS("k_dense_solve_block", C, (among<1, 2, 4, 8>(C, [](auto c) { return sk::k_dense_solve_block<c()>; })), dim3(1), dim3(sk::CG_BLOCK), 0, g.cs,
+                         (const double *)h->Ainv, rhs, u, n, K);
         HIPCHK(hipGetLastError());
         return SGPU_OK;
     }
@@ -454,9 +450,7 @@ int rank_sum_block(AmgBlock &B, double *out, unsigned active) {
 // out[j] = x_j . y_j on the columns of `active` (the others keep what they hold); this rank's rows
 int dot_block(AmgBlock &B, const double *x, const double *y, size_t n, double *out, unsigned active) {
     const int nb = dot_nblocks(n), K = B.K;
-    if (K == 2) SGPU_LAUNCH(sk::k_dot_block_partial<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
-    else if (K == 4) SGPU_LAUNCH(sk::k_dot_block_partial<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
-    else SGPU_LAUNCH(sk::k_dot_block_partial<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
+    SGPU_LAUNCH_COLS("k_dot_block_partial", K, per_K(K, [](auto k) { return sk::k_dot_block_partial<k()>; }), dim3(nb), dim3(sk::BLOCK), 0, g.cs, x, y, n, B.partials);
     SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)B.partials, nb, K, out, active);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
@@ -467,9 +461,7 @@ int dot_block(AmgBlock &B, const double *x, const double *y, size_t n, double *o
 int pcg_update_block(AmgBlock &B, const double *num, const double *den, const double *p, const double *hh, double *u, double *r, size_t n,
                      unsigned active, double *out) {
     const int nb = dot_nblocks(n), K = B.K;
-    if (K == 2) SGPU_LAUNCH(sk::k_pcg_update_block<2>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
-    else if (K == 4) SGPU_LAUNCH(sk::k_pcg_update_block<4>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
-    else SGPU_LAUNCH(sk::k_pcg_update_block<8>, dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
+    SGPU_LAUNCH_COLS("k_pcg_update_block", K, per_K(K, [](auto k) { return sk::k_pcg_update_block<k()>; }), dim3(nb), dim3(sk::BLOCK), 0, g.cs, num, den, p, hh, u, r, n, active, B.partials);
     SGPU_LAUNCH(sk::k_reduce_partials_block, dim3(K), dim3(sk::BLOCK), 0, g.cs, (const double *)B.partials, nb, K, out, active);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
@@ -478,9 +470,7 @@ int pcg_update_block(AmgBlock &B, const double *num, const double *den, const do
 // beta_j = num[j] / den[j]; p = z + beta p on the columns of `active`
 int pcg_direction_block(AmgBlock &B, const double *num, const double *den, const double *z, double *p, size_t n, unsigned active) {
     const int gd = grid_for(2 * n), K = B.K;
-    if (K == 2) SGPU_LAUNCH(sk::k_pcg_direction_block<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
-    else if (K == 4) SGPU_LAUNCH(sk::k_pcg_direction_block<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
-    else SGPU_LAUNCH(sk::k_pcg_direction_block<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
+    SGPU_LAUNCH_COLS("k_pcg_direction_block", K, per_K(K, [](auto k) { return sk::k_pcg_direction_block<k()>; }), dim3(gd), dim3(sk::BLOCK), 0, g.cs, num, den, z, p, n, active);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
 }
@@ -499,46 +489,26 @@ int debug_block_args(sgpu_amg *h, int K, unsigned active, const char *what, AmgB
 extern "C" {
 
 // ---- measurement (tests/perf_block.py): sgpu_time_kernel's loop for the block kernel and for whole V-cycles, scalar or block:
-// `reps` back-to-back enqueues inside the library between two events of their own ----
-static hipEvent_t g_bt0 = nullptr, g_bt1 = nullptr;
-static int block_timer_events() {
-    if (!g_bt0) { HIPCHK(hipEventCreate(&g_bt0)); HIPCHK(hipEventCreate(&g_bt1)); }
-    return SGPU_OK;
-}
+// `reps` back-to-back enqueues inside the library between the context's two events (time_reps) ----
 int sgpu_debug_time_block(sgpu_op *op, int kind, const value_t *X, const value_t *RHS, value_t *Y, int K, int reps, float *ms) {
     CHK(need_ctx());
     if (!op || !X || !Y || !ms || reps < 1 || (kind != 0 && kind != 1)) return fail(SGPU_ERR_ARG, "bad argument");
     if (kind == 1 && (!RHS || !op->inv_diag)) return fail(SGPU_ERR_ARG, "a Jacobi sweep needs rhs and inv_diag");
     CHK(block_check(op, K, "time_block"));
-    CHK(block_timer_events());
-    HIPCHK(hipEventRecord(g_bt0, g.cs));
-    for (int i = 0; i < reps; ++i) {
+    return time_reps(reps, ms, [&]() -> int {
         EpiArgs e;
         if (kind == 1) { e.rhs = RHS; e.inv_diag = op->inv_diag; e.u = X; e.c0 = JACOBI_OMEGA_REF; }
-        CHK(apply_block(op, kind == 1 ? sk::EPI_JACOBI : sk::EPI_SPMV, X, Y, e, K));
-    }
-    HIPCHK(hipEventRecord(g_bt1, g.cs));
-    HIPCHK(hipEventSynchronize(g_bt1));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
-    *ms = t / reps;
-    return SGPU_OK;
+        return apply_block(op, kind == 1 ? sk::EPI_JACOBI : sk::EPI_SPMV, X, Y, e, K);
+    });
 }
 int sgpu_debug_time_vcycle(sgpu_amg *h, value_t *U, const value_t *RHS, int K, int reps, float *ms) {
     CHK(need_ctx());
     if (!h || !U || !RHS || !ms || reps < 1) return fail(SGPU_ERR_ARG, "bad argument");
     AmgBlock *B = nullptr;
     if (K != 0) { CHK(amg_block_check(h, K, "time_vcycle")); CHK(amg_block(h, K, &B)); }
-    CHK(block_timer_events());
-    CHK(K ? vcycle_block0(h, *B, U, RHS) : vcycle0(h, U, RHS));          // (captures the graph outside the interval)
-    HIPCHK(hipEventRecord(g_bt0, g.cs));
-    for (int i = 0; i < reps; ++i) CHK(K ? vcycle_block0(h, *B, U, RHS) : vcycle0(h, U, RHS));
-    HIPCHK(hipEventRecord(g_bt1, g.cs));
-    HIPCHK(hipEventSynchronize(g_bt1));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
-    *ms = t / reps;
-    return SGPU_OK;
+    auto once = [&]() -> int { return K ? vcycle_block0(h, *B, U, RHS) : vcycle0(h, U, RHS); };
+    CHK(once());                                                        // (captures the graph outside the interval)
+    return time_reps(reps, ms, once);
 }
 
 // ---- tests (include/saena_gpu_debug.h): the launch code of the block dot and of the two pCG updates on the caller's vectors ----

@@ -85,16 +85,9 @@ extern "C" int sgpu_debug_dcg_matvec_time(sgpu_amg *h, const value_t *x, value_t
     a.row_ptr = A->loc.csr.row_ptr; a.col = A->loc.csr.col; a.val = A->loc.csr.val; a.n = A->M;
     a.dir = x; a.mt = y; a.PA = PA; a.F = F;
     HIPCHK(hipMemsetAsync(F, 0, sk::DCG_NFLAG * sizeof(int), g.cs));
-    hipEvent_t &e0 = g.tk0, &e1 = g.tk1;
-    if (!e0) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); }
-    SGPU_LAUNCH(mv, dim3(nba), dim3(sk::BLOCK), 0, g.cs, a);                      // warm-up launch (code object load)
-    HIPCHK(hipEventRecord(e0, g.cs));
-    for (int i = 0; i < reps; ++i) SGPU_LAUNCH(mv, dim3(nba), dim3(sk::BLOCK), 0, g.cs, a);
-    HIPCHK(hipEventRecord(e1, g.cs));
-    HIPCHK(hipEventSynchronize(e1));
+    auto once = [&]() -> int { SGPU_LAUNCH(mv, dim3(nba), dim3(sk::BLOCK), 0, g.cs, a); return SGPU_OK; };
+    CHK(once());                                                                  // warm-up launch (code object load)
+    CHK(time_reps(reps, ms, once));
     HIPCHK(hipGetLastError());
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    *ms = t / reps;
     return SGPU_OK;
 }

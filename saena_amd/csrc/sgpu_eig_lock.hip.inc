@@ -1,9 +1,9 @@
 // sgpu_eig_lock.hip.inc -- hard locking for LOBPCG (include/saena_gpu.h): sgpu_eigs_LOBPCG_locked, the block solve of
-// sgpu_eig.hip.inc / sgpu_geig.hip.inc constrained to the B-orthogonal complement of up to 64 locked vectors, and
-// sgpu_eigs_LOBPCG_many, the driver that sweeps it to more than K eigenpairs.  Part of sgpu_runtime.hip, after sgpu_geig.hip.inc;
+// sgpu_eig.hip.inc constrained to the B-orthogonal complement of up to 64 locked vectors, and
+// sgpu_eigs_LOBPCG_many, the driver that sweeps it to more than K eigenpairs.  Part of sgpu_runtime.hip, after sgpu_eig.hip.inc;
 // kernels: kernels_eig_lock.hip.h; the sweep bookkeeping: eig_lock_plan.h (pure host); DESIGN.md section 18.
 //
-// The two loops are the unconstrained ones (eig_lobpcg_run, geig_lobpcg_run) with a locked set handed in: X <- X - Q (Z^T X) twice
+// The loop is the unconstrained one (lobpcg_run, either problem) with a locked set handed in: X <- X - Q (Z^T X) twice
 // before the start orthonormalisation, W <- W - Q (Z^T W) once right after W = M R; Z = Q, or B Q for the generalised problem.  The
 // coefficients Z^T W go from the reduce kernel to the projection through device memory: a locked iteration has the three host
 // synchronisations of an unlocked one.  The lock kernels are eager launches; the V-cycle keeps its fixed (R, W) pair and its graph.
@@ -23,20 +23,10 @@ int amg_lock(sgpu_amg *h, AmgLock **out) {
 }
 
 using LockGramFn = void (*)(const double *, size_t, const double *, size_t, double *);
-template <int K>
-LockGramFn lock_gram_fn_k(int nc) {
-    switch (nc) {
-    case 1: return sk::k_lock_gram_partial<K, 1>;
-    case 2: return sk::k_lock_gram_partial<K, 2>;
-    case 3: return sk::k_lock_gram_partial<K, 3>;
-    case 4: return sk::k_lock_gram_partial<K, 4>;
-    case 5: return sk::k_lock_gram_partial<K, 5>;
-    case 6: return sk::k_lock_gram_partial<K, 6>;
-    case 7: return sk::k_lock_gram_partial<K, 7>;
-    default: return sk::k_lock_gram_partial<K, 8>;
-    }
+LockGramFn lock_gram_fn(int K, int nc) {
+    return per_K(K, [&](auto k) { return among<1, 2, 3, 4, 5, 6, 7, 8>(nc, [](auto c) -> LockGramFn { return sk::k_lock_gram_partial<decltype(k)::value, c()>; }); });
 }
-LockGramFn lock_gram_fn(int K, int nc) { return K == 2 ? lock_gram_fn_k<2>(nc) : K == 4 ? lock_gram_fn_k<4>(nc) : lock_gram_fn_k<8>(nc); }
+static_assert(sk::LOCK_C == 8, "the list above names 1 .. 8 locked columns a pass");
 
 // out[l * K + b] (device) = Z[:, l] . Y[:, b], l < L: ceil(L / 8) passes into slots of their own, one reduce
 int lock_gram(AmgLock &Lk, const double *Z, size_t ld, int L, const double *Y, size_t n, int K, double *out) {
@@ -45,7 +35,7 @@ int lock_gram(AmgLock &Lk, const double *Z, size_t ld, int L, const double *Y, s
     const size_t slot = (size_t)g.n_partials * sk::LOCK_C * K;
     for (int l = 0, pass = 0; l < L; l += sk::LOCK_C, ++pass) {
         const int nc = std::min(sk::LOCK_C, L - l);
-        SGPU_LAUNCH(lock_gram_fn(K, nc), dim3(nb), dim3(sk::BLOCK), 0, g.cs, Z + (size_t)l * ld, ld, Y, n, Lk.part + (size_t)pass * slot);
+        SGPU_LAUNCH_COLS("k_lock_gram_partial", K, lock_gram_fn(K, nc), dim3(nb), dim3(sk::BLOCK), 0, g.cs, Z + (size_t)l * ld, ld, Y, n, Lk.part + (size_t)pass * slot);
     }
     SGPU_LAUNCH(sk::k_gram_reduce, dim3(L * K), dim3(sk::BLOCK), 0, g.cs, (const double *)Lk.part, nb, sk::LOCK_C * K, slot, out);
     HIPCHK(hipGetLastError());
@@ -56,9 +46,7 @@ int lock_gram(AmgLock &Lk, const double *Z, size_t ld, int L, const double *Y, s
 int lock_project(const double *Q, size_t ld, const double *C, int L, double *W, size_t n, int K) {
     if (!n || L <= 0) return SGPU_OK;
     const int gd = (int)std::min<size_t>(2048, (n + sk::BLOCK - 1) / sk::BLOCK);
-    if (K == 2) SGPU_LAUNCH(sk::k_lock_project<2>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, Q, ld, C, L, W, n);
-    else if (K == 4) SGPU_LAUNCH(sk::k_lock_project<4>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, Q, ld, C, L, W, n);
-    else SGPU_LAUNCH(sk::k_lock_project<8>, dim3(gd), dim3(sk::BLOCK), 0, g.cs, Q, ld, C, L, W, n);
+    SGPU_LAUNCH_COLS("k_lock_project", K, per_K(K, [](auto k) { return sk::k_lock_project<k()>; }), dim3(gd), dim3(sk::BLOCK), 0, g.cs, Q, ld, C, L, W, n);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
 }
@@ -141,18 +129,10 @@ int sgpu_debug_time_lock(sgpu_amg *h, int kind, const value_t *Q, size_t ld, int
     AmgLock *Lk = nullptr;
     CHK(amg_lock(h, &Lk));
     CHK(sgpu_vec_fill(Lk->coef, 0.0, (size_t)sk::LOCK_MAX * 8));
-    CHK(block_timer_events());
     auto once = [&]() -> int { return kind == 0 ? lock_gram(*Lk, Q, ld, L, Y, n, K, Lk->coef) : lock_project(Q, ld, Lk->coef, L, Y, n, K); };
     CHK(once());
     if (kind == 0) CHK(sgpu_vec_fill(Lk->coef, 0.0, (size_t)sk::LOCK_MAX * 8));
-    HIPCHK(hipEventRecord(g_bt0, g.cs));
-    for (int i = 0; i < reps; ++i) CHK(once());
-    HIPCHK(hipEventRecord(g_bt1, g.cs));
-    HIPCHK(hipEventSynchronize(g_bt1));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
-    *ms = t / reps;
-    return SGPU_OK;
+    return time_reps(reps, ms, once);
 }
 
 int sgpu_eigs_LOBPCG_locked(sgpu_amg *h, sgpu_op *B, const value_t *Q, const value_t *BQ, size_t ld, int nlocked, value_t *X, int K, int nev,
@@ -164,8 +144,7 @@ int sgpu_eigs_LOBPCG_locked(sgpu_amg *h, sgpu_op *B, const value_t *Q, const val
     CHK(lobpcg_check(h, K, "eigs_LOBPCG_locked"));
     CHK(lock_args_check("eigs_LOBPCG_locked", (size_t)h->A[0]->M, K, Q, BQ, B != nullptr, ld, nlocked));
     const EigLock lk{Q, B ? BQ : Q, ld, nlocked};
-    if (B) return geig_lobpcg_run(h, B, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, &lk, leading);
-    return eig_lobpcg_run(h, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, &lk, leading);
+    return lobpcg_run(h, B, X, K, nev, max_iter, tol, precond, lambda, res, iters, res_hist, hist_cap, &lk, leading);
 }
 
 int sgpu_eigs_LOBPCG_many(sgpu_amg *h, sgpu_op *B, value_t *Q, size_t ld, int nev, int K, int sweep_nev, const value_t *X0, int max_iter,
@@ -201,8 +180,7 @@ int sgpu_eigs_LOBPCG_many(sgpu_amg *h, sgpu_op *B, value_t *Q, size_t ld, int ne
         double bl[8], br[8];
         int it = 0, lead = 0;
         const EigLock lk{Q, B ? BQ.get() : Q, ld, L};
-        const int st = B ? geig_lobpcg_run(h, B, X, K, want, max_iter - total, tol, precond, bl, br, &it, nullptr, 0, &lk, &lead)
-                         : eig_lobpcg_run(h, X, K, want, max_iter - total, tol, precond, bl, br, &it, nullptr, 0, &lk, &lead);
+        const int st = lobpcg_run(h, B, X, K, want, max_iter - total, tol, precond, bl, br, &it, nullptr, 0, &lk, &lead);
         total += it;
         ++sweeps;
         if (st != SGPU_OK && st != SGPU_ERR_NOCONV) { status = st; break; }

@@ -15,29 +15,22 @@ bool gs_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) =
 using GsDotsFn = void (*)(const double *, size_t, const double *, size_t, double *);
 using GsUpdateFn = void (*)(const double *, size_t, const double *, double *, size_t, double *);
 GsDotsFn gs_dots_fn(int nc) {
-    switch (nc) {
-        case 1: return sk::k_gs_dots_partial<1>; case 2: return sk::k_gs_dots_partial<2>; case 3: return sk::k_gs_dots_partial<3>;
-        case 4: return sk::k_gs_dots_partial<4>; case 5: return sk::k_gs_dots_partial<5>; case 6: return sk::k_gs_dots_partial<6>;
-        case 7: return sk::k_gs_dots_partial<7>; default: return sk::k_gs_dots_partial<8>;
-    }
+    return among<1, 2, 3, 4, 5, 6, 7, 8>(nc, [](auto c) -> GsDotsFn { return sk::k_gs_dots_partial<c()>; });
 }
 template <bool NORM>
 GsUpdateFn gs_update_fn(int nc) {
-    switch (nc) {
-        case 1: return sk::k_gs_update<1, NORM>; case 2: return sk::k_gs_update<2, NORM>; case 3: return sk::k_gs_update<3, NORM>;
-        case 4: return sk::k_gs_update<4, NORM>; case 5: return sk::k_gs_update<5, NORM>; case 6: return sk::k_gs_update<6, NORM>;
-        case 7: return sk::k_gs_update<7, NORM>; default: return sk::k_gs_update<8, NORM>;
-    }
+    return among<1, 2, 3, 4, 5, 6, 7, 8>(nc, [](auto c) -> GsUpdateFn { return sk::k_gs_update<c(), NORM>; });
 }
-static_assert(sk::GS_C == 8, "the two switches above name 1 .. 8 columns");
+static_assert(sk::GS_C == 8, "the two lists above name 1 .. 8 columns");
 
 // out[c] = V[:,c] . w for c < ncols (device): one pass over w per GS_C columns, then one workgroup per column over the partials
 int gs_dots(const double *V, size_t ld, int ncols, const double *w, size_t n, double *partials, double *out) {
     if (ncols <= 0) return SGPU_OK;
     const int nb = gs_nblocks(n);
-    for (int c0 = 0; c0 < ncols; c0 += sk::GS_C)
-        SGPU_LAUNCH(gs_dots_fn(std::min(sk::GS_C, ncols - c0)), dim3(nb), dim3(sk::BLOCK), 0, g.cs, V + (size_t)c0 * ld, ld, w, n,
-                    partials + (size_t)c0 * sk::GS_MAXBLK);
+    for (int c0 = 0; c0 < ncols; c0 += sk::GS_C) {
+        const int nc = std::min(sk::GS_C, ncols - c0);
+        SGPU_LAUNCH_COLS("k_gs_dots_partial", nc, gs_dots_fn(nc), dim3(nb), dim3(sk::BLOCK), 0, g.cs, V + (size_t)c0 * ld, ld, w, n, partials + (size_t)c0 * sk::GS_MAXBLK);
+    }
     SGPU_LAUNCH(sk::k_gs_reduce, dim3(ncols), dim3(sk::BLOCK), 0, g.cs, (const double *)partials, nb, out);
     HIPCHK(hipGetLastError());
     return SGPU_OK;
@@ -51,8 +44,8 @@ int gs_update(const double *V, size_t ld, int ncols, const double *h, double *w,
     for (int c0 = 0; c0 < ncols; c0 += sk::GS_C) {
         const int nc = std::min(sk::GS_C, ncols - c0);
         const bool fused = norm2 && c0 + sk::GS_C >= ncols;                // the last chunk also leaves the partial sums of the new w . w
-        SGPU_LAUNCH(fused ? gs_update_fn<true>(nc) : gs_update_fn<false>(nc), dim3(nb), dim3(sk::BLOCK), 0, g.cs, V + (size_t)c0 * ld, ld, h + c0, w, n,
-                    fused ? partials : (double *)nullptr);
+        SGPU_LAUNCH_COLS("k_gs_update", nc, fused ? gs_update_fn<true>(nc) : gs_update_fn<false>(nc), dim3(nb), dim3(sk::BLOCK), 0, g.cs, V + (size_t)c0 * ld, ld, h + c0, w, n,
+                         fused ? partials : (double *)nullptr);
     }
     if (norm2) SGPU_LAUNCH(sk::k_gs_reduce, dim3(1), dim3(sk::BLOCK), 0, g.cs, (const double *)partials, nb, norm2);
     HIPCHK(hipGetLastError());
@@ -168,17 +161,9 @@ int sgpu_debug_time_gs(int kind, const value_t *V, size_t ld, int ncols, value_t
     DevArr<double> partials, coef;
     CHK(dev_alloc(partials, (size_t)ncols * sk::GS_MAXBLK)); CHK(dev_alloc(coef, (size_t)ncols + 1));
     CHK(sgpu_vec_fill(coef, 0.0, (size_t)ncols + 1));
-    CHK(block_timer_events());
     auto once = [&]() { return kind == 0 ? gs_dots(V, ld, ncols, w, n, partials, coef) : gs_update(V, ld, ncols, coef, w, n, partials, coef + ncols); };
     if (kind == 1) CHK(once());                                // (after it the coefficients are still zero: the dots are not run)
-    HIPCHK(hipEventRecord(g_bt0, g.cs));
-    for (int i = 0; i < reps; ++i) CHK(once());
-    HIPCHK(hipEventRecord(g_bt1, g.cs));
-    HIPCHK(hipEventSynchronize(g_bt1));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, g_bt0, g_bt1));
-    *ms = t / reps;
-    return SGPU_OK;
+    return time_reps(reps, ms, once);
 }
 
 // Restarted flexible GMRES.  Per inner iteration j: z = M v_j (one V-cycle from zero through the fixed pair, or z = v_j), w = A z,

@@ -91,7 +91,7 @@ struct Ctx {
     bool        live = false;
     int         device = 0, rank = 0, nranks = 1;
     int         ncu = 256;            // compute units of the device (k_csr_xlds launches one workgroup per CU)
-    hipEvent_t  tk0 = nullptr, tk1 = nullptr;   // sgpu_time_kernel's events
+    hipEvent_t  tk0 = nullptr, tk1 = nullptr;   // time_reps' events: every timing entry point's
     hipStream_t cs = nullptr, hs = nullptr;
     ncclComm_t  comm = nullptr;
     double     *partials = nullptr;   // dot partial sums
@@ -1555,6 +1555,33 @@ BndKernelFn pick_bnd(int epi, int lanes) {
         if (!k_) return fail(SGPU_ERR_STATE, "no %s kernel for epilogue %d", family, epi);                           \
         SGPU_LAUNCH(k_, __VA_ARGS__);                                                                                \
     } while (0)
+// the same for the kernels templated on a column count (the block, eig, lock and Gram-Schmidt layers): `k` is what among<...>(cols, ...)
+// returned
+#define SGPU_LAUNCH_COLS(family, cols, k, ...)                                                                        \
+    do {                                                                                                             \
+        const auto k_ = (k);                                                                                         \
+        if (!k_) return fail(SGPU_ERR_STATE, "no %s kernel for %d columns", family, (int)(cols));                    \
+        SGPU_LAUNCH(k_, __VA_ARGS__);                                                                                \
+    } while (0)
+// K of a block vector into an instantiation: per_K(K, [](auto k) { return sk::kernel<k()>; }); null for a K that is not 2, 4 or 8
+template <class F>
+auto per_K(int K, F &&f) { return among<2, 4, 8>(K, f); }
+
+// measurement: `reps` back-to-back runs of once() between the context's two events, *ms = the time of one run.  The events are made
+// at the first use and destroyed with the context: not part of what a caller's wall clock around the call sees.  A warm-up run,
+// where a caller wants one, is the caller's
+template <class Once>
+int time_reps(int reps, float *ms, Once &&once) {
+    if (!g.tk0) { HIPCHK(hipEventCreate(&g.tk0)); HIPCHK(hipEventCreate(&g.tk1)); }
+    HIPCHK(hipEventRecord(g.tk0, g.cs));
+    for (int i = 0; i < reps; ++i) CHK(once());
+    HIPCHK(hipEventRecord(g.tk1, g.cs));
+    HIPCHK(hipEventSynchronize(g.tk1));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, g.tk0, g.tk1));
+    *ms = t / reps;
+    return SGPU_OK;
+}
 
 // what every SpMV launch shares: the vectors and the epilogue's operands; a form then sets its own fields, all others stay zero
 sk::SpmvArgs spmv_args(const double *x, double *y, const EpiArgs &e) {
@@ -3296,7 +3323,7 @@ struct AmgEig : CapturedGraph {
     PinArr<double> hmix, hlam, hdown;                // pinned: what goes up (coefficients, lambda), what comes down (norms, Gram blocks)
     uint64_t graph_gen = 0, block_gen = 0;
     int debug_stop = -1;                             // sgpu_debug_eig_stop: the iteration a test wants to look into
-    // A x = lambda B x (sgpu_geig.hip.inc): made at the first sgpu_eigs_LOBPCG_gen with this K, never by the standard solve
+    // A x = lambda B x (amg_geig): made at the first sgpu_eigs_LOBPCG_gen with this K, never by the standard solve
     bool gen = false;
     DevArr<double> BX, BW, BP;                       // B times X, W, P, carried
     DevArr<double> bpart, bnrm;                      // ||(Bx)_j||^2: partial sums [n_partials][K], the K sums
@@ -4071,23 +4098,14 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
     if (kind != 0 && !rhs) return fail(SGPU_ERR_ARG, "rhs needed");
     if ((kind == 1 || kind == 3) && !op->inv_diag) return fail(SGPU_ERR_ARG, "operator has no inv_diag");
     if (kind == 3) CHK(ensure_d(op));
-    hipEvent_t &e0 = g.tk0, &e1 = g.tk1;                       // created once per context: not part of what a caller's wall clock around this call sees
-    if (!e0) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); }
-    HIPCHK(hipEventRecord(e0, g.cs));
-    for (int i = 0; i < reps; ++i) {
+    return time_reps(reps, ms, [&]() -> int {
         EpiArgs e; e.rhs = rhs; e.inv_diag = op->inv_diag; e.u = x; e.d = op->dvec;
         int epi = sk::EPI_SPMV;
         if (kind == 1) { epi = sk::EPI_JACOBI; e.c0 = JACOBI_OMEGA_REF; }
         else if (kind == 2) epi = sk::EPI_RESIDUAL;
         else if (kind == 3) { epi = sk::EPI_CHEBYK; e.c0 = 0.5; e.c1 = 0.25; }
-        CHK(apply(op, epi, x, y, e));
-    }
-    HIPCHK(hipEventRecord(e1, g.cs));
-    HIPCHK(hipEventSynchronize(e1));
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    *ms = t / reps;
-    return SGPU_OK;
+        return apply(op, epi, x, y, e);
+    });
 }
 
 } // extern "C"
@@ -4095,7 +4113,6 @@ int sgpu_time_kernel(sgpu_op *op, int kind, const value_t *x, const value_t *rhs
 #include "sgpu_block.hip.inc"
 #include "sgpu_gmres.hip.inc"
 #include "sgpu_eig.hip.inc"
-#include "sgpu_geig.hip.inc"
 #include "sgpu_eig_lock.hip.inc"
 #include "sgpu_lanczos.hip.inc"
 #include "sgpu_coarse_cg.hip.inc"

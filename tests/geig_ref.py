@@ -2,7 +2,7 @@
 GPU, no oracle).
 
 The two mass matrices next to eig_ref.poisson(m) -- the 27-point consistent one with its closed-form generalised spectrum, and a lumped
-(diagonal) one with a jump --, a float64 numpy restatement of sgpu_eigs_LOBPCG_gen (saena_amd/csrc/sgpu_geig.hip.inc) built from
+(diagonal) one with a jump --, a float64 numpy restatement of sgpu_eigs_LOBPCG_gen (lobpcg_run with B, saena_amd/csrc/sgpu_eig.hip.inc) built from
 eig_ref's pieces, the restatement of k_geig_residual (saena_amd/csrc/kernels_eig.hip.h), and the bounds tests/test_gpu_geig.py
 asserts.  tests/test_geig_ref.py shows on the CPU that a correct implementation stays inside every one of them, and pins the numbers
 recorded below: they are this reference's, never the GPU's.

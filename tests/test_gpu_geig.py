@@ -372,3 +372,60 @@ def test_refusals(capi):
     assert not conv2 and it2 == 2
     assert np.all(np.isfinite(lam2)) and np.all(np.isfinite(res2)) and np.all(np.isfinite(dX.get())) and np.all(lam2 > 0)
     assert "above the tolerance" in lib.sgpu_last_error().decode()
+
+
+@pytest.mark.parametrize("precond", (True, False), ids=("vcycle", "plain"))
+def test_identity_mass_reproduces_the_standard_solve(capi, precond):
+    """the standard and the generalised solve are one loop with a metric, so with B = I (the n x n identity as an operator) the
+    generalised solve must reproduce the standard one bit for bit: after three iterations from the same start (tol = 0, so every
+    column stays active in both and the factor ||(Bx)_j||^2 of the generalised test decides nothing; P is in use for two of the
+    three) lambda, res, every column of the residual history, X and the solver's own AX, R, W, AW, P, AP are equal, and BX, BW, BP
+    have the bits of X, W, P.  This rests on I v = v exactly, which fails only for an entry -0.0 (0 + 1 * -0.0 = +0.0): the start
+    vectors hold none (np.signbit of their zeros, checked here on the host).
+
+    Which W: a solve that ends at max_iter has formed W = M R of the next iteration before the norms came down (the loop's first
+    step), while BW is still B times the W of the last completed iteration -- so at the return BX and BP are compared with X and P,
+    and BW with the W a second pair of solves shows when stopped after the orthonormalisation of that last iteration
+    (sgpu_debug_eig_stop, index 2), where all nine vectors are compared as well"""
+    m, K, nev = er.SHAPES[0]
+    G, _ = gpu(capi, m)
+    n = m ** 3
+    X0 = er.start_vectors(n, K)
+    assert not np.any(np.signbit(X0) & (X0 == 0.0))
+    B = op_of(sp.identity(n))
+    names = ("AX", "R", "W", "AW", "P", "AP", "BX", "BW", "BP")
+
+    def own(which):
+        dV = Blk(capi, np.full((n, K), np.nan))
+        G.debug_eig_vector(K, which, dV)
+        return dV.get().copy()
+
+    def run(Bh, stop):
+        dX = Blk(capi, X0)
+        if stop is not None:
+            G.debug_eig_stop(K, stop)
+        lam, res, it, hist, conv = G.lobpcg(dX, nev, max_iter=3, tol=0.0, precond=precond, B=Bh)
+        msg = capi.lib().sgpu_last_error().decode()
+        if stop is None:
+            assert not conv and it == 3 and "above the tolerance after 3 iterations" in msg, msg
+            assert all(len(h) == 4 for h in hist)
+        else:
+            assert not conv and it == stop and "stopped for inspection" in msg and "with P" in msg, msg
+        return lam, res, hist, dX.get().copy(), [own(w) for w in range(6 if Bh is None else 9)]
+
+    def compare(std, gen, what):
+        (lam, res, hist, X, V), (lam_g, res_g, hist_g, X_g, V_g) = std, gen
+        same_bits(lam_g, lam, what + "lambda"); same_bits(res_g, res, what + "res"); same_bits(X_g, X, what + "X")
+        for j in range(K):
+            same_bits(hist_g[j], hist[j], f"{what}history of column {j}")
+        for w in range(6):
+            same_bits(V_g[w], V[w], what + names[w])
+    full, full_g = run(None, None), run(B, None)
+    compare(full, full_g, "")
+    stopped, stopped_g = run(None, 2), run(B, 2)
+    compare(stopped, stopped_g, "stopped: ")
+    X_g, V_g = full_g[3], full_g[4]
+    Xs_g, Vs_g = stopped_g[3], stopped_g[4]
+    same_bits(V_g[6], X_g, "BX"); same_bits(V_g[8], V_g[4], "BP")
+    same_bits(V_g[7], Vs_g[2], "BW at the return, W of the last completed iteration")
+    same_bits(Vs_g[6], Xs_g, "stopped: BX"); same_bits(Vs_g[7], Vs_g[2], "stopped: BW"); same_bits(Vs_g[8], Vs_g[4], "stopped: BP")
